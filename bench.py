@@ -14,12 +14,18 @@ a result (``config.dead_cacnn_elided``, ``config.c1_elided``, ``config.patch_emb
   * the encoder's `fc1` 1x1 conv at 147^2 -> c1 (`backbones/encoders.py:44,55,68`), which `train.py:279` drops;
   * the second evaluation of the patch embedding (pass A computes it inside `get_intermediate_layers`, pass B again on the same
     input and frozen weights: `train.py:287,300`) — computed once and shared.
-``--all-reference-calls`` runs all three; without it the line still carries the figure of such a run as
+``--all-reference-calls`` runs all three; without it, ``--full`` adds the figure of such a run to the line as
 ``secondary.all_reference_calls`` (a short extra pass AFTER the timed region: 5 warm-up + 10 steps), next to ``secondary.bf16``
 (``--operand bf16`` on the same modules) and ``host_enqueue_ms_per_step`` (how long the host takes to enqueue one step with the
 GPU idle at the start: Python + ctypes + HIP launches; far below ms_per_step = the GPU is the limiter).
 Weights are random-init of the named architecture (no network: `adaptersis_amd.utils.weights`), data is synthetic of the
 named shape.
+
+A plain run sets up, warms up, times the steps and prints the line.  ``--full`` adds everything else the benchmark measures,
+all after the timed region: the single-stream roofline pass (``roofline``), the secondary passes (``secondary``,
+``host_enqueue_ms_per_step``) and the CPU oracle step (``cpu_baseline``); ``--no-kernel-timing`` / ``--no-secondary`` /
+``--no-cpu-baseline`` drop one of them again.  ``--dump-outputs DIR`` writes what the last timed step computed (see
+``dump_outputs``).
 
 Output: ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
@@ -273,6 +279,36 @@ def pmc_traffic(kernel: str, variants):
     return (round(tot / n) if n else None), src
 
 
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def dump_outputs(eng, loss, out_dir: str) -> None:
+    """``--dump-outputs DIR``: what the timed path hands its caller after its last step, as float32 ``DIR/<name>.npy``: the loss
+    and, for every flat bucket the step writes, its gradient (``<bucket>_grad``) and, when the optimiser applies it, the updated
+    weights (``<bucket>_weights``).  An array above its even share of DUMP_BUDGET_BYTES is a fixed sample: indices drawn with
+    replacement from a CPU generator seeded 0 and sorted, hence the same for the same length on every run."""
+    import numpy as np
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    stepped = [id(b) for b in eng.optimizer.buckets]
+    for name, attr in (("decoder", "bucket"), ("adapters", "adapter_bucket"), ("encoder", "encoder_bucket"),
+                       ("backbone", "vit_bucket")):
+        b = getattr(eng, attr, None)
+        if b is None:
+            continue
+        arrays[f"{name}_grad"] = b.grad
+        if id(b) in stepped:
+            arrays[f"{name}_weights"] = b.flat
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` without torchrun: run N ranks as children of this (GPU-free) process through
     ``python -m torch.distributed.run`` on 127.0.0.1, pass their stdout / stderr through (rank 0 prints the JSON line)
@@ -316,7 +352,14 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short extra passes after the timed region (secondary.all_reference_calls, secondary.bf16, host enqueue time)")
     ap.add_argument("--cpu-baseline-batch", type=int, default=1, help="batch of the timed CPU (oracle) step: 1 or 2")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also the roofline pass, the secondary passes and the CPU baseline (a plain run "
+                         "does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, gradients and updated weights of the last timed step to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # dmabuf IPC only on this pool: must be in the environment before the HIP runtime starts in THIS process too (a rank started
     # by the driver's torchrun inherits it from the driver; this is the default for any other launcher)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -343,9 +386,16 @@ def main():
         dist.destroy_process_group()
         return 0
     # the in-tree library is built (normally a no-op) BEFORE the first GPU call of this process: no compiler children
-    # under an initialised HIP runtime / a preloaded profiler.  File-locked: one rank builds, the others wait.
-    from adaptersis_amd.build import build_library
-    build_library()
+    # under an initialised HIP runtime / a preloaded profiler.  File-locked: one rank builds, the others wait.  A tree that
+    # build() prepared and this user may not write (the lock file cannot be created) runs the library build() left there.
+    from adaptersis_amd.build import LIB, build_library
+    try:
+        build_library()
+    except OSError as e:
+        if not os.path.exists(LIB):
+            raise
+        print(f"bench.py: build directory not writable ({e.strerror}): using {os.path.relpath(LIB, ROOT)} as built",
+              file=sys.stderr)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (HIP device); there is no CPU fallback")
     # ASIS_BENCH_BACKEND=gloo (rehearsal on a one-GPU box, tests/test_gpu_dist.py): every rank on device 0, collectives over gloo —
@@ -406,8 +456,10 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el)
     loss_v = float(loss)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(eng, loss, a.dump_outputs)   # before any later pass steps the weights again
     # ---- second pass of the same steps with a HIP event pair around every GEMM launch: the roofline figures ----
-    prof = None if a.no_kernel_timing else []
+    prof = None if (a.no_kernel_timing or not a.full) else []
     if prof is not None:
         ops.PROFILE = prof
         enc_stream, config.encoder_stream = config.encoder_stream, False   # one stream: a launch's event pair times that launch alone
@@ -425,7 +477,7 @@ def main():
 
     # ---- secondary figures (never inside the timed region): short passes of 5 warm-up + 10 steps each ----------------
     secondary, host_enqueue_ms = None, None
-    if not a.no_secondary:
+    if a.full and not a.no_secondary:
         def timed(e, warm=5, steps=10):
             for _ in range(warm):
                 e.train_step(img, tgt)
@@ -568,7 +620,7 @@ def main():
             out["secondary"] = secondary
         if roof:
             out["roofline"] = roof
-        if world == 1 and not a.no_cpu_baseline and a.config == 3:
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config == 3:
             out["cpu_baseline"] = cpu_baseline(a.arch, a.size, a.cpu_baseline_batch)
         print(json.dumps(out), flush=True)
     if world > 1:

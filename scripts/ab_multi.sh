@@ -4,6 +4,6 @@ rounds=$1; shift
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     if [ "$v" = "-" ]; then e=""; else e="$v"; fi
-    env $e python bench.py --no-cpu-baseline $BENCH_ARGS 2>/dev/null | python -c "import sys,json; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%-40s' % '$v', j['value'], 'img/s', j['ms_per_step'], 'ms  dense', j['roofline']['achieved'], 'TF/s')"
+    env $e python bench.py --full --no-cpu-baseline $BENCH_ARGS 2>/dev/null | python -c "import sys,json; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%-40s' % '$v', j['value'], 'img/s', j['ms_per_step'], 'ms  dense', j['roofline']['achieved'], 'TF/s')"
   done
 done

@@ -1,6 +1,6 @@
 """Idle time and concurrency of the step from a rocprofv3 --kernel-trace database (results.db):
    python scripts/timeline_gaps.py <results.db> [n_steps] [first_step]
-(bench.py's default run: warmup 3 + 10 timed steps, THEN a single-stream pass of the same steps for the roofline launch times —
+(`bench.py --full`: warmup 3 + 10 timed steps, THEN a single-stream pass of the same steps for the roofline launch times —
 first_step 4, n_steps 8 looks at the timed region).  The step boundary is the guarded-SGD launch; for the last n steps: wall time, union-busy time (any kernel running), idle time,
 per-queue busy time, and the largest idle gaps with the kernels on either side."""
 import re

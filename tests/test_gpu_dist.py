@@ -199,7 +199,7 @@ def test_bench_two_ranks_rehearsal_over_gloo(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(ASIS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--arch",
-                        "vit_tiny_test", "--size", "224", "--batch", "2", "--no-cpu-baseline"], env=env, capture_output=True,
+                        "vit_tiny_test", "--size", "224", "--batch", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

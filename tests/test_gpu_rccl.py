@@ -123,12 +123,11 @@ CHILD2 = textwrap.dedent('''
 ''')
 
 
-def _run_two_ranks(extra_env):
+def _run_two_ranks(extra_env, tmp_dir):
     env = dict(os.environ, ASIS_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    path = os.path.join(ROOT, "gpurun_out", "_rccl2_child.py")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = os.path.join(str(tmp_dir), "_rccl2_child.py")
     with open(path, "w") as f:
         f.write(CHILD2)
     return subprocess.run([sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1",
@@ -136,16 +135,16 @@ def _run_two_ranks(extra_env):
 
 
 @pytest.mark.parametrize("compress", ["none", "bf16"])
-def test_two_rank_body_over_gloo_on_one_card(compress):
+def test_two_rank_body_over_gloo_on_one_card(compress, tmp_path):
     """The body of the two-real-rank RCCL test below — two steps of the frozen-backbone engine and of the unfrozen one, then
     bit-equality of weights, running statistics and reduced gradients across the ranks — with both ranks on the one visible
     device over gloo, so that its logic executes on the one-GPU box too; ``compress``: the 16-bit gradient
     transport (ASIS_GRAD_COMPRESS) on every bucket."""
-    r = _run_two_ranks({"ASIS_2RANK_BACKEND": "gloo", "ASIS_GRAD_COMPRESS": compress})
+    r = _run_two_ranks({"ASIS_2RANK_BACKEND": "gloo", "ASIS_GRAD_COMPRESS": compress}, tmp_path)
     assert r.returncode == 0 and "RCCL_2RANK_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
-def test_two_real_ranks_over_rccl_when_two_devices_are_visible():
+def test_two_real_ranks_over_rccl_when_two_devices_are_visible(tmp_path):
     """N > 1 on real RCCL: two ranks, one device each, two steps of the frozen-backbone engine and of the
     unfrozen one (SyncBN exchanges, per-stage decoder all-reduces, chunked backbone bucket with blocks_per_bucket <
     n_last_blocks, adapter / encoder buckets) — weights, running statistics and reduced gradients must be identical on
@@ -153,5 +152,5 @@ def test_two_real_ranks_over_rccl_when_two_devices_are_visible():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs >= 2 visible GPUs (the driver's multi-GPU node)")
-    r = _run_two_ranks({"ASIS_2RANK_BACKEND": "nccl"})
+    r = _run_two_ranks({"ASIS_2RANK_BACKEND": "nccl"}, tmp_path)
     assert r.returncode == 0 and "RCCL_2RANK_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
