@@ -1628,6 +1628,48 @@ def augment(img_u8: torch.Tensor, mask_u8: torch.Tensor, tables: dict):
     return out, mout
 
 
+def frame_resize(frames_u8: Optional[torch.Tensor], masks_u8: Optional[torch.Tensor], size: int, lut=None):
+    """PIL-exact resize to ``size`` x ``size`` (csrc/frame_resize.hip): uint8 [B,H,W,3] frames (BILINEAR) and uint8 [B,H,W] masks
+    (NEAREST, then the 256-entry label table ``lut``; None = identity) -> (uint8 [B,S,S,3], uint8 [B,S,S]).  Either input may be
+    None (its output is then None).  Tables: ``tools.frame_resize``."""
+    import numpy as np
+    from .tools import frame_resize as _fr
+    ref = frames_u8 if frames_u8 is not None else masks_u8
+    if ref is None:
+        raise ValueError("frame_resize: no input")
+    _dev(frames_u8, masks_u8)
+    B, H, W = ref.shape[0], ref.shape[1], ref.shape[2]
+    if frames_u8 is not None and (frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3
+                                  or not frames_u8.is_contiguous()):
+        raise ValueError("frame_resize: frames must be contiguous uint8 [B,H,W,3]")
+    if masks_u8 is not None and (masks_u8.dtype != torch.uint8 or tuple(masks_u8.shape) != (B, H, W) or not masks_u8.is_contiguous()):
+        raise ValueError("frame_resize: masks must be contiguous uint8 [B,H,W] of the frames' size")
+    S = int(size)
+    if S < 1:
+        raise ValueError("frame_resize: size must be positive")
+    dev = ref.device
+    t = _fr.device_tables(H, W, S, dev)
+    out_img = out_mask = tmp = None
+    if frames_u8 is not None:
+        out_img = torch.empty((B, S, S, 3), device=dev, dtype=torch.uint8)
+        if H != S and W != S:
+            tmp = torch.empty((B, H, S, 3), device=dev, dtype=torch.uint8)
+    if masks_u8 is not None:
+        out_mask = torch.empty((B, S, S), device=dev, dtype=torch.uint8)
+    if lut is None:
+        lut = _fr.LUT_IDENTITY
+    if not torch.is_tensor(lut):
+        lut = torch.from_numpy(np.ascontiguousarray(np.asarray(lut, dtype=np.uint8)))
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256,):
+        raise ValueError("frame_resize: lut must be uint8 [256]")
+    lut = lut.to(dev).contiguous()
+    check(lib().asis_frame_resize(_stream(), _p(frames_u8), _p(masks_u8), t["xspan"].data_ptr(), t["xcoef"].data_ptr(),
+                                  int(t["xcoef"].shape[1]), t["yspan"].data_ptr(), t["ycoef"].data_ptr(), int(t["ycoef"].shape[1]),
+                                  t["ix"].data_ptr(), t["iy"].data_ptr(), lut.data_ptr(), _p(tmp), _p(out_img), _p(out_mask),
+                                  B, H, W, S, S), "asis_frame_resize")
+    return out_img, out_mask
+
+
 # ---- dropout of the MaskTransformer head (csrc/dropout.hip: counter-based masks, include/asis_hip.h) -----------------------------
 def dropout_f32(x: torch.Tensor, seed: int, site: int, p: float, res: Optional[torch.Tensor] = None, alpha: float = 1.0,
                 bias_n: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -39,14 +39,14 @@ _ENGINES = {}
 class _SegData(torch.utils.data.Dataset):
     """(img float[0,1] CHW, mask long HW, index) like `tools/dataset.py:127-167`."""
 
-    def __init__(self, path, split, imsize, n_synth=24):
+    def __init__(self, path, split, imsize, n_synth=24, num_classes=2):
         d = os.path.join(path, split)
         if os.path.isfile(os.path.join(d, "images.npy")):
             import numpy as np
             self.img = torch.from_numpy(np.load(os.path.join(d, "images.npy"))).float()
             self.msk = torch.from_numpy(np.load(os.path.join(d, "masks.npy"))).long()
         else:
-            self.img, self.msk = W.synthetic_batch(n_synth, imsize, 2, seed=1 if split == "train" else 2)
+            self.img, self.msk = W.synthetic_batch(n_synth, imsize, num_classes, seed=1 if split == "train" else 2)
 
     def __len__(self):
         return self.img.shape[0]
@@ -63,7 +63,11 @@ def _to_device_batch(inp, target, train: bool):
     """Batch from the loader -> (float [B,3,S,S] in [0,1], long [B,S,S]) on the device.  uint8 HWC batches (``tools.dataset.Robomis``
     without a host transform) go through the GPU augmentation pipeline (`train.py:139-163`) when training, and through the same
     kernel with identity parameters (= `/255`, `tools/dataset.py:159`; the reference's val transform is a no-op Resize to the
-    image size, `train.py:119-122`) when validating."""
+    image size, `train.py:119-122`) when validating.  A ``tools.dataset.collate_frames`` batch (native-size frames) is uploaded and
+    resized on the device first (``ops.frame_resize``, PIL-exact), then takes the same uint8 path."""
+    from .tools.dataset import FrameBatch
+    if isinstance(inp, FrameBatch):
+        inp, target = _resize_frames(inp)
     inp, target = inp.cuda(non_blocking=True), target.cuda(non_blocking=True)
     if inp.dtype != torch.uint8:
         return inp, target
@@ -73,6 +77,22 @@ def _to_device_batch(inp, target, train: bool):
     if aug is None:
         aug = _AUGMENTERS[S] = TrainAugment(size=S, seed=1000 + utils.get_rank())
     return aug(inp.contiguous(), target.to(torch.uint8).contiguous(), None if train else [dict(_IDENTITY) for _ in range(inp.shape[0])])
+
+
+def _resize_frames(fb):
+    """FrameBatch -> (uint8 [B,S,S,3], uint8 [B,S,S] labels) on the device; items the collate already resized on the host
+    are put back in their places."""
+    from . import ops
+    fb = fb.to("cuda", non_blocking=True)
+    img, msk = ops.frame_resize(fb.frames, fb.masks, fb.size, fb.lut)
+    if fb.host_pos.numel() == 0:
+        return img, msk
+    B, S = fb.shape[0], fb.size
+    full_img = torch.empty((B, S, S, 3), device=img.device, dtype=torch.uint8)
+    full_msk = torch.empty((B, S, S), device=img.device, dtype=torch.uint8)
+    full_img[fb.pos], full_msk[fb.pos] = img, msk
+    full_img[fb.host_pos], full_msk[fb.host_pos] = fb.host_frames, fb.host_masks
+    return full_img, full_msk
 
 
 def _open_datasets(args):
@@ -124,17 +144,23 @@ def broadcast_module_states(modules, src: int = 0, group=None) -> None:
 
 
 def _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=0.01, momentum=0.99, weight_decay=3e-5,
-                mode="reference_exact", train_encoder=False):
+                mode="reference_exact", train_encoder=False, num_classes=2, loss="dice"):
     key = id(seg_decoder)
     if key not in _ENGINES:
         _ENGINES[key] = SegEngine(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=momentum,
-                                  weight_decay=weight_decay, mode=mode, train_encoder=train_encoder)
+                                  weight_decay=weight_decay, mode=mode, train_encoder=train_encoder, num_classes=num_classes,
+                                  loss=loss)
     return _ENGINES[key]
 
 
-def train_seg(args, head: str = "feature"):
+def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = "dice", open_datasets=None, validate=None):
     """``head``: "feature" = `train.py` (FeatureDecoder, SGD lr / 0.99 / 3e-5, `train.py:178-191`); "mla" = `train_mla.py`
-    (DecoderMLA, SGD lr * batch * world / 16, momentum 0.9, no weight decay, `train_mla.py:178-184`)."""
+    (DecoderMLA, SGD lr * batch * world / 16, momentum 0.9, no weight decay, `train_mla.py:178-184`).
+    ``num_classes`` (head and engine), ``loss`` (a key of ``SegEngine.LOSSES``), ``open_datasets(args) -> (train set, val set,
+    collate_fn)`` and ``validate`` (signature of ``validate_network``) are what `train_multi_class.py` changes; the defaults
+    are `train.py`'s."""
+    open_datasets = open_datasets or _open_datasets
+    validate = validate or validate_network
     utils.init_distributed_mode(args)
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda", args.gpu)
@@ -154,22 +180,23 @@ def train_seg(args, head: str = "feature"):
     cross_vit = CAViT(dim=D, n_levels=3, num_heads=8, init_values=0.0, n_points=4).to(dev)
     cross_cnn = CACNN(dim=D, n_levels=1, num_heads=8, n_points=4, with_cffn=True, cffn_ratio=0.25).to(dev)
     if head == "mla":
-        seg_decoder = DecoderMLA(img_size=args.imsize, mla_channels=D, num_classes=2).to(dev)
+        seg_decoder = DecoderMLA(img_size=args.imsize, mla_channels=D, num_classes=num_classes).to(dev)
     else:
-        seg_decoder = FeatureDecoder(embed_dim=D, num_classes=2, features=[D, 512, 256, 128, 64]).to(dev)
+        seg_decoder = FeatureDecoder(embed_dim=D, num_classes=num_classes, features=[D, 512, 256, 128, 64]).to(dev)
     # the reference wraps these four modules in DistributedDataParallel (`train.py:84-116`), whose constructor broadcasts
     # rank 0's parameters and buffers: without it every rank would train its own randomly initialised copy
     broadcast_module_states([backbone_encoder, cross_vit, cross_cnn, seg_decoder])
     if head == "mla":
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
-        engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9, weight_decay=0.0)
+        engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9, weight_decay=0.0,
+                             num_classes=num_classes, loss=loss)
     else:
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=args.lr,
                              mode="train_adapters" if getattr(args, "train_adapters", False) else "reference_exact",
-                             train_encoder=getattr(args, "train_encoder", False))
+                             train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss)
     optimizer = engine.optimizer
 
-    dataset_train, dataset_val, collate = _open_datasets(args)
+    dataset_train, dataset_val, collate = open_datasets(args)
     workers = args.num_workers if collate is not None else 0      # PNG decode runs in loader workers; tensors in memory do not need any
     if getattr(args, "shard_val", False) and utils.get_world_size() > 1:
         # the reference lets all ranks evaluate the whole val set; here every rank takes every world-th batch
@@ -216,7 +243,7 @@ def train_seg(args, head: str = "feature"):
                                   state_dict=seg_decoder, **extra, optimizer=optimizer, scheduler=scheduler)
     start_epoch, best_acc = to_restore["epoch"], to_restore["best_acc"]
     if args.evaluate:
-        stats = validate_network(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_decoder,
+        stats = validate(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_decoder,
                                  args.n_last_blocks, args.avgpool_patchtokens)
         print(f"Accuracy of the network on the {len(dataset_val)} test images: {stats['acc1']:.1f}%")
         return stats
@@ -228,7 +255,7 @@ def train_seg(args, head: str = "feature"):
         scheduler.step()
         log_stats = {**{f"train_{k}": v for k, v in train_stats.items()}, "epoch": epoch}
         if epoch % args.val_freq == 0 or epoch == args.epochs - 1:
-            test_stats = validate_network(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn,
+            test_stats = validate(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn,
                                           seg_decoder, args.n_last_blocks, args.avgpool_patchtokens)
             print(f"Accuracy at epoch {epoch} of the network on the {len(dataset_val)} test images: {test_stats['acc1']:.1f}%")
             best_acc = max(best_acc, test_stats["acc1"])

@@ -684,6 +684,17 @@ int asis_clahe(void* stream, const uint8_t* rgb, const int32_t* clahe, const uin
                const uint16_t* tab_l2yf, const int32_t* tab_ab2xz, const uint8_t* tab_invgamma, const int32_t* coef_fwd,
                const int32_t* coef_inv, uint8_t* luts, const uint8_t* lut, float* out, int B, int S, int tiles);
 
+/* Frame resize of the datasets' host path (tools/dataset.py:51-53: PIL resize((S, S), BILINEAR) for the frame, NEAREST for the
+ * mask), bit-identical to Pillow's 8-bit resample; csrc/frame_resize.hip, tables from adaptersis_amd/tools/frame_resize.py.
+ *   img uint8 [B,Hi,Wi,3] -> out_img uint8 [B,Ho,Wo,3]: horizontal pass (xspan int32 [Wo,2] = (first tap, taps), xcoef int32
+ *     [Wo,kx], 22 fractional bits) rounded to uint8 into tmp [B,Hi,Wo,3] (needed only when both axes change), then the vertical
+ *     pass (yspan [Ho,2], ycoef [Ho,ky]); an axis whose size does not change is skipped.  img / out_img NULL: masks only.
+ *   mask uint8 [B,Hi,Wi] -> out_mask uint8 [B,Ho,Wo] = lut[mask[b, iy[y], ix[x]]] (ix int32 [Wo], iy int32 [Ho], lut uint8 [256]);
+ *     mask / out_mask NULL: frames only. */
+int asis_frame_resize(void* stream, const uint8_t* img, const uint8_t* mask, const int32_t* xspan, const int32_t* xcoef, int kx,
+                      const int32_t* yspan, const int32_t* ycoef, int ky, const int32_t* ix, const int32_t* iy, const uint8_t* lut,
+                      uint8_t* tmp, uint8_t* out_img, uint8_t* out_mask, int B, int Hi, int Wi, int Ho, int Wo);
+
 /* ---------------------------------------------------------------------------------------------
  * Dropout of the MaskTransformer decode head (backbones/masktrans_block.py:11-89: nn.Dropout(p) on the attention probabilities,
  * the projection output, behind GELU and behind fc2; eval_dinov2_masktrans.py:136-139 builds it with p = 0.1).  csrc/dropout.hip.
