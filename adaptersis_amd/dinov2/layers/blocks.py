@@ -104,24 +104,26 @@ class _Packed(nn.Module):
         if gamma is None:
             return 0
         # reading max|gamma| is a device-to-host sync: a frozen gamma pays it once; a TRAINED one (``optimize_backbone``) moves a
-        # little every step, and k is only a range choice (any nearby power of two is exact), so it is re-read every
-        # _LS_POW2_REFRESH changes of the parameter instead of 2 syncs per block per step inside the overlapped backward
+        # little every step, and k is only a range choice (any nearby power of two is exact), so the optimizer's changes (the
+        # fused SGD marks them by ``_asis_gen`` alone) are counted and max|gamma| is re-read every _LS_POW2_REFRESH of them
+        # instead of 2 syncs per block per step inside the overlapped backward.  A write through torch (``load_state_dict``,
+        # ``copy_``, ``fill_``: a new ``_version``) can move gamma by any factor, so it is re-read at once.
         tag = (gamma.data_ptr(), gamma.device, config.operand_dtype)
-        gen = (gamma._version, getattr(gamma, "_asis_gen", 0))
+        ver, gen = gamma._version, getattr(gamma, "_asis_gen", 0)
         ent = self._cache.get(key)
-        if ent is not None and ent[0] == tag:
-            st = ent[1]                       # [k, generation seen at the last read, changes since]
-            if st[1] == gen:
+        if ent is not None and ent[0] == tag and ent[1][1] == ver:
+            st = ent[1]                       # [k, _version at the last read, _asis_gen seen last, optimizer changes since]
+            if st[2] == gen:
                 return st[0]
-            if st[2] + 1 < _LS_POW2_REFRESH:
-                st[1], st[2] = gen, st[2] + 1
+            if st[3] + 1 < _LS_POW2_REFRESH:
+                st[2], st[3] = gen, st[3] + 1
                 return st[0]
         m = float(gamma.detach().abs().max())
         k = 0 if not (m > 0.0 and m < float("inf")) else -int(math.floor(math.log2(m)))
         if ent is not None and ent[0] == tag and ent[1][0] != k:
             for stale in [c for c in self._cache if c.endswith(f"@{ent[1][0]}") or c.endswith(f"@{-ent[1][0]}")]:
                 del self._cache[stale]        # the 2^k-scaled weight packs of the old k
-        self._cache[key] = (tag, [k, gen, 0])
+        self._cache[key] = (tag, [k, ver, gen, 0])
         return k
 
     def _nw_pow2(self, key: str, w: torch.Tensor, pow2: int) -> torch.Tensor:

@@ -77,6 +77,44 @@ def test_layerscale_pow2_is_not_a_host_sync_per_step():
     assert k == 0
 
 
+def test_layerscale_pow2_rereads_gamma_after_an_out_of_band_write():
+    """Block._ls_pow2: a write through torch (``load_state_dict``, ``copy_``, ``fill_``: a new ``_version``) can move gamma by
+    any factor and is re-read at once — a stale k = 17 behind gamma = 0.5 packs 2^17 * 0.5 W past fp16's range; a change
+    marked by ``_asis_gen`` alone (the fused optimizer) stays lazy and is re-read after _LS_POW2_REFRESH of them"""
+    from adaptersis_amd.dinov2.layers import blocks as B
+    blk = B.Block(64, 1, qkv_bias=True, init_values=1e-5)
+    g = blk.ls1.gamma
+    assert blk._ls_pow2("ls1.k", g) == 17
+    sd = {k: v.clone() for k, v in blk.state_dict().items()}
+    sd["ls1.gamma"] = torch.full((64,), 0.5)
+    blk.load_state_dict(sd)
+    assert blk.ls1.gamma is g
+    assert blk._ls_pow2("ls1.k", g) == 1                                             # 0.5 * 2^1 = 1
+    with torch.no_grad():
+        g.copy_(torch.full((64,), 3e-4))
+    assert blk._ls_pow2("ls1.k", g) == 12
+    with torch.no_grad():
+        g.fill_(1e-5)
+    assert blk._ls_pow2("ls1.k", g) == 17
+    # the second branch keeps its own state
+    assert blk._ls_pow2("ls2.k", blk.ls2.gamma) == 17
+    # the optimizer's marker alone: k is a range choice, re-read only every _LS_POW2_REFRESH changes
+    v0 = g._version
+    g.data.fill_(0.3)                                                                # 0.3 * 2^2 = 1.2; leaves _version alone
+    assert g._version == v0
+    for i in range(B._LS_POW2_REFRESH - 1):
+        g._asis_gen = getattr(g, "_asis_gen", 0) + 1
+        assert blk._ls_pow2("ls1.k", g) == 17, i
+    g._asis_gen += 1
+    assert blk._ls_pow2("ls1.k", g) == 2
+    assert blk._ls_pow2("ls2.k", blk.ls2.gamma) == 17
+    # and an out-of-band write right after an optimizer change is still seen at once
+    g._asis_gen += 1
+    with torch.no_grad():
+        g.fill_(4.0)
+    assert blk._ls_pow2("ls1.k", g) == -2
+
+
 def test_modules_refuse_cpu_inputs():
     from adaptersis_amd.dinov2.models import vision_transformer as vits
     m = vits.vit_tiny_test(img_size=518, init_values=1e-5)

@@ -105,20 +105,32 @@ def test_transpose_tokens(dev):
     assert float(t[:, :, N:].abs().sum()) == 0
 
 
-def _block_case(dev, arch, B, N, dt):
+def _ls_state_dict(arch, init):
+    """"kernel": gamma in [0.05, 0.5]; "init": the reference's 1e-5 (k = 17 on both branches); "mixed": ls1 = 1e-5 (k = 17) and
+    ls2 in [0.25, 0.35] (k = 2) on the block under test"""
+    sd = W.make_vit_state_dict(arch, layerscale="init" if init == "init" else "kernel")
+    if init == "mixed":
+        D = sd["blocks.1.ls1.gamma"].numel()
+        sd["blocks.1.ls1.gamma"] = torch.full((D,), 1e-5)
+        sd["blocks.1.ls2.gamma"] = W.tensor("blkb.ls2.mixed", (D,), 0.05, 0.3)
+    return sd
+
+
+def _oracle_block_grads(sd, x, dy, heads, ref_dtype):
+    """oracle block output, dL/dx and every parameter gradient of blocks.1 under autograd in ``ref_dtype``"""
+    osd = {k: v.to(ref_dtype).clone().requires_grad_(True) for k, v in sd.items() if k.startswith("blocks.1.")}
+    xr = x.to(ref_dtype).clone().requires_grad_(True)
+    (O.block(xr, osd, "blocks.1", heads) * dy.to(ref_dtype)).sum().backward()
+    with torch.no_grad():
+        y_ref = O.block(x.to(ref_dtype), {k: v.detach() for k, v in osd.items()}, "blocks.1", heads)
+    return y_ref, xr.grad, {k: v.grad for k, v in osd.items()}
+
+
+def _block_fwd_bwd(blk, x, dy, dt):
+    """forward_train + eval forward + backward with every parameter gradient, on ``dt`` operands"""
     from adaptersis_amd import config
-    from adaptersis_amd.dinov2.models import vision_transformer as vits
-    D, depth, heads, ffn = W.VIT_CONFIGS[arch]
-    sd = W.make_vit_state_dict(arch, layerscale="kernel")
-    model = vits.__dict__[arch](patch_size=14, img_size=518, init_values=1e-5, ffn_layer=ffn, block_chunks=0)
-    model.load_state_dict(sd)
-    blk = model.blocks[1].to(dev)
-    x = W.tensor(f"blkb.x{B}{N}", (B, N, D), 1.0)
-    dy = W.tensor(f"blkb.dy{B}{N}", (B, N, D), 1.0)
-    # oracle autograd
-    osd = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith("blocks.1.")}
-    xr = x.clone().requires_grad_(True)
-    (O.block(xr, osd, "blocks.1", heads) * dy).sum().backward()
+    B, N, D = x.shape
+    dev = next(blk.parameters()).device
     old = config.operand_dtype
     config.set_operand_dtype(dt)
     try:
@@ -129,9 +141,21 @@ def _block_case(dev, arch, B, N, dt):
         dx = blk.backward(saved, (dy * S).to(dev).view(B * N, D).contiguous(), 1.0 / S, grads, "blocks.1")
     finally:
         config.set_operand_dtype(old)
-    with torch.no_grad():
-        y_ref = O.block(x, {k: v.detach() for k, v in osd.items()}, "blocks.1", heads)
-    return y, y_eval, y_ref, dx / S, xr.grad, grads, {k: v.grad for k, v in osd.items()}
+    return y, y_eval, dx / S, grads
+
+
+def _block_case(dev, arch, B, N, dt, init="kernel", ref_dtype=torch.float32):
+    from adaptersis_amd.dinov2.models import vision_transformer as vits
+    D, depth, heads, ffn = W.VIT_CONFIGS[arch]
+    sd = _ls_state_dict(arch, init)
+    model = vits.__dict__[arch](patch_size=14, img_size=518, init_values=1e-5, ffn_layer=ffn, block_chunks=0)
+    model.load_state_dict(sd)
+    blk = model.blocks[1].to(dev)
+    x = W.tensor(f"blkb.x{B}{N}", (B, N, D), 1.0)
+    dy = W.tensor(f"blkb.dy{B}{N}", (B, N, D), 1.0)
+    y_ref, dx_ref, gref = _oracle_block_grads(sd, x, dy, heads, ref_dtype)
+    y, y_eval, dx, grads = _block_fwd_bwd(blk, x, dy, dt)
+    return y, y_eval, y_ref, dx, dx_ref, grads, gref
 
 
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
@@ -158,6 +182,51 @@ def test_swiglu_block_forward_train_and_backward(dev):
     errs = {k: rel_l2(grads[k], gref[k]) for k in grads}
     print("swiglu block: dx %.2e" % rel_l2(dx.view_as(dx_ref), dx_ref), {k.replace("blocks.1.", ""): "%.1e" % v for k, v in errs.items()})
     assert rel_l2(dx.view_as(dx_ref), dx_ref) < 3e-3 and max(errs.values()) < 3e-3, errs
+
+
+@pytest.mark.parametrize("init", ["init", "mixed"])
+@pytest.mark.parametrize("arch,B,N,dt", [("vit_tiny_test", 2, 70, torch.float16), ("vit_tiny_test", 2, 70, torch.bfloat16),
+                                         ("vit_tiny_test", 2, 150, torch.float16), ("vit_tiny_test", 2, 150, torch.bfloat16),
+                                         ("vit_tiny_swiglu", 2, 45, torch.float16), ("vit_tiny_swiglu", 2, 45, torch.bfloat16)])
+def test_block_backward_layerscale_pow2(dev, arch, B, N, dt, init):
+    """LayerScale at the reference's init (gamma = 1e-5: k = 17 on both branches, Block._ls_pow2) and mixed (k = 17 / 2): the
+    2^k-scaled branch gradients through Block.backward — separate gelu16 backward (R = 140), GELU' in the fc2 dgrad epilogue
+    (R = 300, ACT_GELU_GRAD), swiglu_bwd — against float64 oracle autograd: dx and every parameter gradient, gammas included"""
+    y, y_eval, y_ref, dx, dx_ref, grads, gref = _block_case(dev, arch, B, N, dt, init, torch.float64)
+    f16 = dt == torch.float16
+    assert bool(torch.isfinite(dx).all()) and all(bool(torch.isfinite(g).all()) for g in grads.values())
+    assert rel_l2(y, y_ref) < (5e-4 if f16 else 4e-3)
+    e_dx = rel_l2(dx.view_as(dx_ref), dx_ref)
+    errs = {k: rel_l2(grads[k], gref[k]) for k in grads}
+    print(arch, B * N, dt, init, "dx", "%.2e" % e_dx, {k.replace("blocks.1.", ""): "%.1e" % v for k, v in errs.items()})
+    tol = 3e-3 if f16 else 2.5e-2
+    assert e_dx < tol
+    assert max(errs.values()) < tol, errs
+
+
+def test_block_backward_after_layerscale_reload(dev):
+    """a backward at the init gamma (k = 17), then ``load_state_dict`` with gamma in [0.05, 0.5] (k = 1 .. 4): the next backward
+    must use the new k at once — a stale 2^17 behind gamma = 0.5 overflows fp16's dh / dO"""
+    from adaptersis_amd.dinov2.models import vision_transformer as vits
+    arch, B, N, dt = "vit_tiny_test", 2, 70, torch.float16
+    D, depth, heads, ffn = W.VIT_CONFIGS[arch]
+    model = vits.__dict__[arch](patch_size=14, img_size=518, init_values=1e-5, ffn_layer=ffn, block_chunks=0)
+    x = W.tensor(f"blkb.x{B}{N}", (B, N, D), 1.0)
+    dy = W.tensor(f"blkb.dy{B}{N}", (B, N, D), 1.0)
+    blk = model.blocks[1]
+    for init in ("init", "kernel"):
+        sd = _ls_state_dict(arch, init)
+        blk.load_state_dict({k[len("blocks.1."):]: v for k, v in sd.items() if k.startswith("blocks.1.")})
+        blk.to(dev)
+        y_ref, dx_ref, gref = _oracle_block_grads(sd, x, dy, heads, torch.float64)
+        y, y_eval, dx, grads = _block_fwd_bwd(blk, x, dy, dt)
+        assert bool(torch.isfinite(dx).all()), init
+        bad = [k for k, g in grads.items() if not bool(torch.isfinite(g).all())]
+        assert not bad, (init, bad)
+        e_dx = rel_l2(dx.view_as(dx_ref), dx_ref)
+        errs = {k: rel_l2(grads[k], gref[k]) for k in grads}
+        print(init, "dx", "%.2e" % e_dx, "worst grad %.2e" % max(errs.values()))
+        assert rel_l2(y, y_ref) < 5e-4 and e_dx < 3e-3 and max(errs.values()) < 3e-3, (init, errs)
 
 
 def test_block_backward_input_gradient_only(dev):
