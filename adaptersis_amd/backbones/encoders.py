@@ -31,6 +31,9 @@ class FeatureEncoder(_Packed):
         if inplanes % 8:
             raise ValueError("inplanes must be a multiple of 8")
         self.with_cp = with_cp
+        # forward_tokens moves the BatchNorm running buffers like the reference's train-mode encoder; SegEngine.predict sets
+        # this to False around its forward (the outputs never depend on them)
+        self.update_running_stats = True
         self.inplanes, self.embed_dim = inplanes, embed_dim
         self.compute_c1 = True  # the reference computes c1 although train.py never uses it
         BN = nn.BatchNorm2d  # same state_dict keys as nn.SyncBatchNorm
@@ -73,7 +76,7 @@ class FeatureEncoder(_Packed):
             raw = ops.conv_gemm_split(x16, x_lo, self._wconv(key, conv), self._wconv(key, conv, 1), 3, 3, s, p, stats=stats)
         else:
             raw = ops.conv_gemm(x16, self._wconv(key, conv), 3, 3, s, p, stats=stats)
-        scale, shift, _, _, _ = _bn.finalize(stats, B * OH * OW, bn, sync)
+        scale, shift, _, _, _ = _bn.finalize(stats, B * OH * OW, bn, sync, update=self.update_running_stats)
         return raw, scale, shift
 
     @staticmethod
@@ -103,7 +106,8 @@ class FeatureEncoder(_Packed):
         D = self.embed_dim
         st = self.stem
         raw = ops.conv3x3_c3(x, self._f32("stem0", st[0].weight), 2, 1)
-        scale, shift, _, _, _ = _bn.finalize(ops.colstats(raw), raw.numel() // raw.shape[-1], st[1], sync_bn)
+        scale, shift, _, _, _ = _bn.finalize(ops.colstats(raw), raw.numel() // raw.shape[-1], st[1], sync_bn,
+                                                update=self.update_running_stats)
         # the two 64 -> 64 stem convolutions (stride 1, pad 1, 294^2 for a 588^2 image: 77 GF each, the encoder's largest) take MX
         # lo operands on the halo-tile kernel where that path is on: their inputs come out of bn_act in the MX form
         def stem_act(raw, scale, shift, conv):

@@ -802,6 +802,25 @@ class SegEngine(nn.Module):
         loss1, _, _ = ops.dice_fwd(logits, target, 1, 10e-20, 1.0)
         return (m, loss1, counts) if with_counts else (m, loss1)
 
+    @torch.no_grad()
+    def predict(self, inp: torch.Tensor, size=None, **kw):
+        """Masks of ``inp`` (float [B,3,S,S] as validation feeds it) at ``size`` = (H, W) (None: the input's own), uint8 [B,H,W]:
+        ``ops.predict_mask`` (keywords: ``encode``, ``frames`` / ``palette`` / ``alpha`` for the overlay, ``target`` / ``lut``
+        for the per-class counts) on the logits ``validate_step`` sees — decoder in eval mode and restored afterwards, the
+        encoder's SyncBatchNorm in train mode as validation leaves it, so a frame's mask depends on the batch it is predicted
+        in exactly as the validation metrics do.  Forward only: no optimizer state, BatchNorm running buffer
+        or saved activation of a training step is touched."""
+        enc = self.backbone_encoder
+        was, upd = self.seg_decoder.training, enc.update_running_stats
+        self.seg_decoder.eval()
+        enc.update_running_stats = False
+        try:
+            logits = self.eval_logits(inp)
+        finally:
+            self.seg_decoder.train(was)
+            enc.update_running_stats = upd
+        return ops.predict_mask(logits, tuple(inp.shape[-2:]) if size is None else size, **kw)
+
 
 def make_vit_bucket(model, blocks_per_bucket: int, process_group, momentum: bool = False, min_first_blocks: int = 0,
                     compress: Optional[str] = None):

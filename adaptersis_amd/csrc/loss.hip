@@ -13,40 +13,9 @@
 // then softmax^T twice, written at (H, W); asis_resize_bilinear_bwd gathers it back to the
 // decoder's (h, w) grid as the 16-bit operand of the dgrad / wgrad GEMMs.
 #include "asis_common.h"
+#include "bilinear_tap.h"  // MAXC, Tap, tap_ac_false, sample_logits
 
 namespace {
-
-constexpr int MAXC = 16;
-
-struct Tap {
-  int i0, i1;
-  float l0, l1;
-};
-// area_pixel_compute_source_index(align_corners=False): src = scale*(dst+0.5)-0.5, clamped at 0
-__device__ __forceinline__ Tap tap_ac_false(int dst, float scale, int in) {
-  float s = scale * ((float)dst + 0.5f) - 0.5f;
-  if (s < 0.f) s = 0.f;
-  Tap t;
-  t.i0 = (int)s;
-  if (t.i0 > in - 1) t.i0 = in - 1;
-  t.i1 = t.i0 + ((t.i0 < in - 1) ? 1 : 0);
-  t.l1 = s - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-// interpolated logits of output pixel (y, x) -> z[C]
-__device__ __forceinline__ void sample_logits(const float* __restrict__ lg, int h, int w, int C, int y, int x, float sh,
-                                              float sw, float* z) {
-  const Tap ty = tap_ac_false(y, sh, h), tx = tap_ac_false(x, sw, w);
-  const float* p00 = lg + ((int64_t)ty.i0 * w + tx.i0) * C;
-  const float* p01 = lg + ((int64_t)ty.i0 * w + tx.i1) * C;
-  const float* p10 = lg + ((int64_t)ty.i1 * w + tx.i0) * C;
-  const float* p11 = lg + ((int64_t)ty.i1 * w + tx.i1) * C;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) z[c] = ty.l0 * (tx.l0 * p00[c] + tx.l1 * p01[c]) + ty.l1 * (tx.l0 * p10[c] + tx.l1 * p11[c]);
-}
 
 __device__ __forceinline__ void softmax_c(float* z, int C) {
   float m = -INFINITY;

@@ -1670,6 +1670,66 @@ def frame_resize(frames_u8: Optional[torch.Tensor], masks_u8: Optional[torch.Ten
     return out_img, out_mask
 
 
+def _u8_table(t, shape, name: str, dev) -> torch.Tensor:
+    import numpy as np
+    if not torch.is_tensor(t):
+        arr = np.asarray(t)
+        if arr.dtype.kind not in "iu" or arr.size and (arr.min() < 0 or arr.max() > 255):
+            raise ValueError(f"predict_mask: {name} must hold integers in 0..255")
+        t = torch.from_numpy(np.ascontiguousarray(arr.astype(np.uint8)))
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"predict_mask: {name} must be uint8 {list(shape)}, got {t.dtype} {list(t.shape)}")
+    return t.to(dev).contiguous()
+
+
+def predict_mask(logits: torch.Tensor, size, encode=None, *, frames: Optional[torch.Tensor] = None, palette=None, alpha=None,
+                 target: Optional[torch.Tensor] = None, lut=None):
+    """Native-size masks from the decoder's logits in one pass (csrc/predict.hip): fp32 NHWC [B,h,w,C] -> uint8 [B,H,W] =
+    ``encode[argmax_c F.interpolate(logits, (H, W), bilinear)]``, ties to the lowest class, equal to the argmax over
+    ``resize_bilinear_fwd`` bit for bit.  ``size``: (H, W) or an int; ``encode``: uint8 [C] class -> pixel value (None = the class
+    index; named tables in ``tools.frame_resize.ENCODINGS``).
+      ``frames`` uint8 [B,H,W,3] (+ ``palette`` uint8 [C,3], ``alpha`` uint8 [C]; defaults: green, 128 for every class but 0)
+          -> also ``overlay`` uint8 [B,H,W,3] = (frame * (255 - a) + palette * a + 127) // 255 with a = alpha of the pixel's class
+      ``target`` uint8 [B,H,W] raw masks + ``lut`` uint8 [256] (the dataset's label table) -> also ``counts`` int64 [C,3] =
+          #(pred == c and label == c), #(pred == c), #(label == c) over the batch (labels >= C count in no class)
+    -> mask, or (mask[, overlay][, counts])."""
+    _dev(logits, frames, target)
+    if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("predict_mask: logits must be a contiguous float32 NHWC tensor [B,h,w,C]")
+    B, h, w, Cc = logits.shape
+    if not 1 <= Cc <= 16:
+        raise ValueError(f"predict_mask: logits have C={Cc} classes, supported 1..16")
+    if isinstance(size, int):
+        size = (size, size)
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError(f"predict_mask: size must be a positive int or (H, W), got {size!r}")
+    H, W = int(size[0]), int(size[1])
+    dev = logits.device
+    from .tools import frame_resize as _fr
+    enc = _u8_table(_fr.ENCODE_INDEX[:Cc] if encode is None else encode, (Cc,), "encode", dev)
+    if frames is None and (palette is not None or alpha is not None):
+        raise ValueError("predict_mask: palette / alpha given without frames")
+    if (target is None) != (lut is None):
+        raise ValueError("predict_mask: target (raw masks) and lut (their label table) go together")
+    mask = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    overlay = counts = pal = alp = None
+    if frames is not None:
+        if frames.dtype != torch.uint8 or tuple(frames.shape) != (B, H, W, 3) or not frames.is_contiguous():
+            raise ValueError(f"predict_mask: frames must be contiguous uint8 [B,H,W,3] = {[B, H, W, 3]}, got {list(frames.shape)}")
+        pal = _u8_table(_fr.default_palette(Cc) if palette is None else palette, (Cc, 3), "palette", dev)
+        alp = _u8_table(_fr.default_alpha(Cc) if alpha is None else alpha, (Cc,), "alpha", dev)
+        overlay = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)
+    if target is not None:
+        if target.dtype != torch.uint8 or tuple(target.shape) != (B, H, W) or not target.is_contiguous():
+            raise ValueError(f"predict_mask: target must be contiguous uint8 [B,H,W] = {[B, H, W]}, got {list(target.shape)}")
+        lut = _u8_table(lut, (256,), "lut", dev)
+        counts = torch.zeros((Cc, 3), device=dev, dtype=torch.int64)
+    check(lib().asis_predict_mask(_stream(), logits.data_ptr(), B, h, w, Cc, H, W, enc.data_ptr(), mask.data_ptr(), _p(frames),
+                                  _p(pal), _p(alp), _p(overlay), _p(target), _p(lut), _p(counts)), "asis_predict_mask")
+    out = (mask,) + ((overlay,) if overlay is not None else ()) + ((counts,) if counts is not None else ())
+    return mask if len(out) == 1 else out
+
+
 # ---- dropout of the MaskTransformer head (csrc/dropout.hip: counter-based masks, include/asis_hip.h) -----------------------------
 def dropout_f32(x: torch.Tensor, seed: int, site: int, p: float, res: Optional[torch.Tensor] = None, alpha: float = 1.0,
                 bias_n: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -33,6 +33,36 @@ LUT_BINARY = (np.arange(256) > 0).astype(np.uint8)          # x > 0 -> 1
 LUT_MULTI = (np.arange(256) >> 5).astype(np.uint8)          # floor(x / 32): instruments_masks 0, 32, ..., 224 -> 0..7
 LUT_IDENTITY = np.arange(256, dtype=np.uint8)
 
+# class index -> pixel value of the mask files (``ops.predict_mask``): each the inverse of the label table its dataset reads with
+ENCODE_INDEX = np.arange(16, dtype=np.uint8)                        # c
+ENCODE_BINARY255 = np.array([0, 255], dtype=np.uint8)               # Robust-MIS, EndoVis 2018, AutoLaparo, EndoVis 2017 binary_masks
+ENCODE_ENDOVIS2017 = (np.arange(8) * 32).astype(np.uint8)           # 32 c: instruments_masks (instruments_factor)
+# name -> (encode table, the label table it inverts)
+ENCODINGS = {"index": (ENCODE_INDEX, LUT_IDENTITY), "binary255": (ENCODE_BINARY255, LUT_BINARY),
+             "endovis2017": (ENCODE_ENDOVIS2017, LUT_MULTI)}
+
+
+def encode_table(name: str, num_classes: int) -> np.ndarray:
+    """uint8 [num_classes] of the named encoding; raises when the encoding has fewer classes."""
+    if name not in ENCODINGS:
+        raise ValueError(f"encode must be one of {sorted(ENCODINGS)}, got {name!r}")
+    enc = ENCODINGS[name][0]
+    if not 1 <= num_classes <= len(enc):
+        raise ValueError(f"encoding {name!r} covers {len(enc)} classes, the model has {num_classes}")
+    return enc[:num_classes].copy()
+
+
+def default_palette(num_classes: int) -> np.ndarray:
+    """uint8 [C, 3]: green for every class, the reference's ``draw_segmentation_masks(colors="green")``."""
+    return np.tile(np.array([[0, 128, 0]], dtype=np.uint8), (num_classes, 1))
+
+
+def default_alpha(num_classes: int, alpha: float = 0.5) -> np.ndarray:
+    """uint8 [C]: class 0 leaves the frame untouched, every other class blends with round(255 * alpha) (reference: .5)."""
+    a = np.full(num_classes, int(round(255 * float(alpha))), dtype=np.uint8)
+    a[0] = 0
+    return a
+
 
 @lru_cache(maxsize=64)
 def bilinear_tables(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -153,17 +153,10 @@ def _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=0
     return _ENGINES[key]
 
 
-def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = "dice", open_datasets=None, validate=None):
-    """``head``: "feature" = `train.py` (FeatureDecoder, SGD lr / 0.99 / 3e-5, `train.py:178-191`); "mla" = `train_mla.py`
-    (DecoderMLA, SGD lr * batch * world / 16, momentum 0.9, no weight decay, `train_mla.py:178-184`).
-    ``num_classes`` (head and engine), ``loss`` (a key of ``SegEngine.LOSSES``), ``open_datasets(args) -> (train set, val set,
-    collate_fn)`` and ``validate`` (signature of ``validate_network``) are what `train_multi_class.py` changes; the defaults
-    are `train.py`'s."""
-    open_datasets = open_datasets or _open_datasets
-    validate = validate or validate_network
-    utils.init_distributed_mode(args)
-    print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
-    dev = torch.device("cuda", args.gpu)
+def build_modules(args, head: str, num_classes: int, dev):
+    """The five modules of `train.py:170-191` on ``dev``, constructed in the reference's order (so a seeded run draws the same
+    initial weights wherever it is called from: ``train_seg`` and ``adaptersis_amd.predict``):
+    -> (model, backbone_encoder, cross_vit, cross_cnn, seg_decoder)."""
     arch = args.arch if args.arch in ARCH_FFN else "vit_large"
     D = W.VIT_CONFIGS[arch][0]
     # dinov2/eval/setup.py:62-75 + models/__init__.py:14-29 (teacher, img_size 518, layerscale 1e-5, block_chunks 0)
@@ -175,7 +168,6 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = 
         model.load_state_dict(W.make_vit_state_dict(arch, patch_size=args.patch_size, layerscale="init"))
         print("No pretrained weights: deterministic synthetic initialisation (adaptersis_amd.utils.weights)")
     model = model.to(dev).eval()
-    feature_model = model  # ModelWithIntermediateLayers(model, 4, autocast) collapses into the engine's pass A
     backbone_encoder = FeatureEncoder(embed_dim=D).to(dev)
     cross_vit = CAViT(dim=D, n_levels=3, num_heads=8, init_values=0.0, n_points=4).to(dev)
     cross_cnn = CACNN(dim=D, n_levels=1, num_heads=8, n_points=4, with_cffn=True, cffn_ratio=0.25).to(dev)
@@ -183,6 +175,22 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = 
         seg_decoder = DecoderMLA(img_size=args.imsize, mla_channels=D, num_classes=num_classes).to(dev)
     else:
         seg_decoder = FeatureDecoder(embed_dim=D, num_classes=num_classes, features=[D, 512, 256, 128, 64]).to(dev)
+    return model, backbone_encoder, cross_vit, cross_cnn, seg_decoder
+
+
+def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = "dice", open_datasets=None, validate=None):
+    """``head``: "feature" = `train.py` (FeatureDecoder, SGD lr / 0.99 / 3e-5, `train.py:178-191`); "mla" = `train_mla.py`
+    (DecoderMLA, SGD lr * batch * world / 16, momentum 0.9, no weight decay, `train_mla.py:178-184`).
+    ``num_classes`` (head and engine), ``loss`` (a key of ``SegEngine.LOSSES``), ``open_datasets(args) -> (train set, val set,
+    collate_fn)`` and ``validate`` (signature of ``validate_network``) are what `train_multi_class.py` changes; the defaults
+    are `train.py`'s."""
+    open_datasets = open_datasets or _open_datasets
+    validate = validate or validate_network
+    utils.init_distributed_mode(args)
+    print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
+    dev = torch.device("cuda", args.gpu)
+    model, backbone_encoder, cross_vit, cross_cnn, seg_decoder = build_modules(args, head, num_classes, dev)
+    feature_model = model  # ModelWithIntermediateLayers(model, 4, autocast) collapses into the engine's pass A
     # the reference wraps these four modules in DistributedDataParallel (`train.py:84-116`), whose constructor broadcasts
     # rank 0's parameters and buffers: without it every rank would train its own randomly initialised copy
     broadcast_module_states([backbone_encoder, cross_vit, cross_cnn, seg_decoder])

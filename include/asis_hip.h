@@ -695,6 +695,19 @@ int asis_frame_resize(void* stream, const uint8_t* img, const uint8_t* mask, con
                       const int32_t* yspan, const int32_t* ycoef, int ky, const int32_t* ix, const int32_t* iy, const uint8_t* lut,
                       uint8_t* tmp, uint8_t* out_img, uint8_t* out_mask, int B, int Hi, int Wi, int Ho, int Wo);
 
+/* Prediction (csrc/predict.hip): native-size label masks from the decoder's logits in one pass, the reference's
+ * F.interpolate(bilinear, align_corners=False) -> argmax -> pixel value (train.py:422,616,624-640) without the fp32 [B,H,W,C] map.
+ *   logits fp32 NHWC [B,h,w,C] (1 <= C <= 16), any output size (H, W) -> mask uint8 [B,H,W] = encode[argmax_c], encode uint8 [C];
+ *     ties go to the lowest class; the samples are those of asis_resize_bilinear_fwd bit for bit.
+ *   overlay (optional, NULL = off): frames uint8 [B,H,W,3], palette uint8 [C][3], alpha uint8 [C] -> overlay uint8 [B,H,W,3] =
+ *     (frame * (255 - a) + palette[c] * a + 127) / 255 in integers, a = alpha[c] of the pixel's class c.
+ *   counts (optional, NULL = off): target uint8 [B,H,W] raw mask, lut uint8 [256] its label table (asis_frame_resize's) ->
+ *     counts int64 [C][3] += #(pred == c and label == c), #(pred == c), #(label == c); labels >= C count in no class.  The call
+ *     adds to the buffer (zero it first; several batches may accumulate into one). */
+int asis_predict_mask(void* stream, const float* logits, int B, int h, int w, int C, int H, int W, const uint8_t* encode,
+                      uint8_t* mask, const uint8_t* frames, const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay,
+                      const uint8_t* target, const uint8_t* lut, int64_t* counts);
+
 /* ---------------------------------------------------------------------------------------------
  * Dropout of the MaskTransformer decode head (backbones/masktrans_block.py:11-89: nn.Dropout(p) on the attention probabilities,
  * the projection output, behind GELU and behind fc2; eval_dinov2_masktrans.py:136-139 builds it with p = 0.1).  csrc/dropout.hip.
