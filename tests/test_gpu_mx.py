@@ -11,25 +11,9 @@ import torch.nn.functional as F
 from adaptersis_amd import config, ops
 from adaptersis_amd.utils import weights as W
 from tests.conftest import rel_l2
+from tests.mx_helpers import decode as _decode
 
 pytestmark = pytest.mark.gpu
-
-
-def _e4m3(b: torch.Tensor) -> torch.Tensor:
-    b = b.to(torch.int32)
-    s, e, m = (b >> 7) & 1, (b >> 3) & 15, b & 7
-    v = torch.where(e == 0, m.float() / 8.0 * 2.0 ** -6, (1.0 + m.float() / 8.0) * torch.exp2(e.float() - 7.0))
-    return torch.where(s == 1, -v, v)
-
-
-def _decode(mx: torch.Tensor, amax: float, dt, wside: bool):
-    """MX tensor (16-bit container) -> (hi, lo) float tensors"""
-    import math
-    by = mx.contiguous().view(torch.uint8).view(*mx.shape, 2)
-    e = math.floor(math.log2(amax))
-    lo_shift = 18 if dt == torch.float16 else 15
-    b_hi, b_lo = (by[..., 1], by[..., 0]) if wside else (by[..., 0], by[..., 1])
-    return _e4m3(b_hi) * 2.0 ** -(7 - e), _e4m3(b_lo) * 2.0 ** -(lo_shift - e)
 
 
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
