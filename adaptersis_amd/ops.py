@@ -1670,15 +1670,15 @@ def frame_resize(frames_u8: Optional[torch.Tensor], masks_u8: Optional[torch.Ten
     return out_img, out_mask
 
 
-def _u8_table(t, shape, name: str, dev) -> torch.Tensor:
+def _u8_table(t, shape, name: str, dev, op: str = "predict_mask") -> torch.Tensor:
     import numpy as np
     if not torch.is_tensor(t):
         arr = np.asarray(t)
         if arr.dtype.kind not in "iu" or arr.size and (arr.min() < 0 or arr.max() > 255):
-            raise ValueError(f"predict_mask: {name} must hold integers in 0..255")
+            raise ValueError(f"{op}: {name} must hold integers in 0..255")
         t = torch.from_numpy(np.ascontiguousarray(arr.astype(np.uint8)))
     if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"predict_mask: {name} must be uint8 {list(shape)}, got {t.dtype} {list(t.shape)}")
+        raise ValueError(f"{op}: {name} must be uint8 {list(shape)}, got {t.dtype} {list(t.shape)}")
     return t.to(dev).contiguous()
 
 
@@ -1728,6 +1728,83 @@ def predict_mask(logits: torch.Tensor, size, encode=None, *, frames: Optional[to
                                   _p(pal), _p(alp), _p(overlay), _p(target), _p(lut), _p(counts)), "asis_predict_mask")
     out = (mask,) + ((overlay,) if overlay is not None else ()) + ((counts,) if counts is not None else ())
     return mask if len(out) == 1 else out
+
+
+SURFACE_MAX_TOLERANCES = 8
+SURFACE_WORKSPACE_BYTES = 512 << 20    # bound on the vertical-distance maps of one asis_surface_stats call (csrc/surface.hip)
+
+
+def surface_thresholds(tolerances) -> list:
+    """Tolerances in pixels -> the integer bounds floor(tau^2) that the squared distances are compared with."""
+    import math
+    tol = [float(t) for t in tolerances]
+    if len(tol) > SURFACE_MAX_TOLERANCES:
+        raise ValueError(f"surface_stats: {len(tol)} tolerances, at most {SURFACE_MAX_TOLERANCES} are supported")
+    for t in tol:
+        if not (0.0 <= t <= 32768.0):     # also refuses nan
+            raise ValueError(f"surface_stats: tolerance {t!r} must be a non-negative number of pixels (at most 32768)")
+    return [int(math.floor(t * t)) for t in tol]
+
+
+def surface_plan(B: int, H: int, W: int, C: int, budget: Optional[int] = None):
+    """-> (frames per call, classes per call): the largest whose vertical-distance maps (uint16, both sides) fit ``budget``
+    (default ``SURFACE_WORKSPACE_BYTES``); one class of one frame is always allowed."""
+    budget = SURFACE_WORKSPACE_BYTES if budget is None else int(budget)
+    per_class = 2 * H * W * 2
+    nc = max(1, min(C, budget // per_class))
+    nb = max(1, min(B, budget // (per_class * nc))) if nc == C else 1
+    return nb, nc
+
+
+def surface_stats(pred: torch.Tensor, target: torch.Tensor, num_classes: int, tolerances, *, pred_lut=None, lut=None,
+                  return_d2: Optional[str] = None):
+    """Boundary statistics of label maps against their ground truth (csrc/surface.hip; definitions in include/asis_hip.h).
+    ``pred``, ``target``: contiguous uint8 [B,H,W] raw pixel values on the device; ``pred_lut`` / ``lut``: uint8 [256] label tables
+    (None = identity; a value >= C is no class); ``tolerances`` in pixels, at most 8.
+    -> ints int64 [B, C, 7 + 2 T] = inter, n_pred, n_lab, e_pred, e_lab, max_pred, max_lab, hit_pred[T], hit_lab[T] and
+       sums float64 [B, C, 2] = sum over E(P) of sqrt(d2_G), sum over E(G) of sqrt(d2_P) (bit-identical between calls);
+       with ``return_d2`` = "pred" / "target" also the exact squared-distance field of that side's edge pixels, int32 [B,C,H,W]
+       (-1 where the class has no edge pixel on that side of the frame).
+    Frames and classes are processed in chunks so that the intermediate maps stay under ``SURFACE_WORKSPACE_BYTES``."""
+    _dev(pred, target)
+    for name, t in (("pred", pred), ("target", target)):
+        if t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError(f"surface_stats: {name} must be contiguous uint8 [B,H,W], got {t.dtype} {list(t.shape)}")
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"surface_stats: pred {list(pred.shape)} and target {list(target.shape)} differ in shape")
+    if pred.device != target.device:
+        raise ValueError(f"surface_stats: pred on {pred.device}, target on {target.device}")
+    Cc = int(num_classes)
+    if not 1 <= Cc <= 16:
+        raise ValueError(f"surface_stats: num_classes={num_classes}, supported 1..16")
+    B, H, W = (int(v) for v in pred.shape)
+    if B < 1 or H < 1 or W < 1 or H > 16384 or W > 16384:
+        raise ValueError(f"surface_stats: shape {[B, H, W]}: sizes must be in 1..16384")
+    if return_d2 not in (None, "pred", "target"):
+        raise ValueError(f"surface_stats: return_d2={return_d2!r} must be None, 'pred' or 'target'")
+    thr = surface_thresholds(tolerances)
+    T = len(thr)
+    dev = pred.device
+    from .tools import frame_resize as _fr
+    plut = _u8_table(_fr.LUT_IDENTITY if pred_lut is None else pred_lut, (256,), "pred_lut", dev, "surface_stats")
+    glut = _u8_table(_fr.LUT_IDENTITY if lut is None else lut, (256,), "lut", dev, "surface_stats")
+    ints = torch.zeros((B, Cc, 7 + 2 * T), device=dev, dtype=torch.int64)
+    sums = torch.zeros((B, Cc, 2), device=dev, dtype=torch.float64)
+    d2 = torch.full((B, Cc, H, W), -1, device=dev, dtype=torch.int32) if return_d2 else None
+    nb, nc = surface_plan(B, H, W, Cc)
+    edges = torch.empty((nb, 2, H, W), device=dev, dtype=torch.uint8)
+    g = torch.empty((nb, 2, nc, H, W), device=dev, dtype=torch.int16)     # uint16 on the device
+    partial = torch.empty((nb, 2, nc, H), device=dev, dtype=torch.float64)
+    thr_c = (C.c_int32 * max(T, 1))(*thr)
+    for b0 in range(0, B, nb):
+        n = min(nb, B - b0)
+        for c0 in range(0, Cc, nc):
+            check(lib().asis_surface_stats(_stream(), pred[b0:b0 + n].data_ptr(), target[b0:b0 + n].data_ptr(), plut.data_ptr(),
+                                           glut.data_ptr(), n, H, W, Cc, c0, min(nc, Cc - c0), thr_c, T, edges.data_ptr(),
+                                           g.data_ptr(), partial.data_ptr(), ints[b0:b0 + n].data_ptr(), sums[b0:b0 + n].data_ptr(),
+                                           _p(d2[b0:b0 + n]) if d2 is not None else None, 1 if return_d2 == "target" else 0),
+                  "asis_surface_stats")
+    return (ints, sums, d2) if d2 is not None else (ints, sums)
 
 
 # ---- dropout of the MaskTransformer head (csrc/dropout.hip: counter-based masks, include/asis_hip.h) -----------------------------

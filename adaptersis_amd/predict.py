@@ -10,7 +10,9 @@ times 255, ``draw_segmentation_masks(alpha=.5, colors="green")``, ``imsave``), a
 as uint8, resized on the device (``ops.frame_resize``, PIL-exact) and normalised by the validation path of
 ``train._to_device_batch``; ``SegEngine.predict`` makes the masks at native size in one fused pass (``ops.predict_mask``:
 bilinear resize of the logits, argmax, pixel value; optionally the overlay and the per-class pixel counts against the ground
-truth); PNGs are written by a small thread pool under ``--pred_dir`` with the input's relative path and stem.
+truth); with ``--surface`` the boundary statistics of every frame are made from that mask and the ground truth where they already
+are, on the device (``ops.surface_stats``: exact distance transform; Dice, normalised surface distance, Hausdorff and mean
+surface distance per class under ``"surface"`` in ``metrics.json``, ``segloss/surface.py``); PNGs are written by a small thread pool under ``--pred_dir`` with the input's relative path and stem.
 
 Batches: frames are grouped by native size, sizes in ascending order, paths sorted inside a size, ``--batch_size_per_gpu``
 frames per batch (the last batch of a size may be short).  The composition is a function of the file list and the batch size
@@ -45,6 +47,7 @@ from .tools import frame_resize as _fr
 IMAGE_EXT = (".png", ".jpg", ".bmp")
 DATASETS = ("endovis2017", "endovis2018", "autolapro", "robomis")
 MAX_WRITERS = 8
+DEFAULT_TOLERANCES = (1.0, 2.0, 5.0)
 
 
 def get_args_parser():
@@ -68,6 +71,10 @@ def get_args_parser():
     p.add_argument("--masks", nargs="?", const="dataset", default=None,
                    help="score against native ground truth: with --dataset the dataset's own masks (no value needed), otherwise a "
                         "directory mirroring --input; writes per-class IoU, mean IoU and pixel accuracy to <pred_dir>/metrics.json")
+    p.add_argument("--surface", nargs="*", type=float, default=None, metavar="TAU",
+                   help="with --masks: per-frame Dice and boundary metrics (normalised surface distance at these tolerances, in "
+                        "pixels at native size; Hausdorff; mean surface distance) under 'surface' in metrics.json; no value = "
+                        + " ".join(f"{t:g}" for t in DEFAULT_TOLERANCES))
     p.add_argument("--seed", default=None, type=int,
                    help="torch seed the TRAINING process was given before it built its modules; required when the checkpoint lacks "
                         "cross_vit / cross_cnn / backbone_encoder (the training command lines do not seed, so only a caller that "
@@ -279,6 +286,28 @@ def predict_batch(engine: SegEngine, frames_u8: torch.Tensor, masks_u8: Optional
     return out if isinstance(out, tuple) else (out,)
 
 
+def surface_tolerances(args) -> Optional[List[float]]:
+    """The tolerances of ``--surface`` (None = not asked for; no value = ``DEFAULT_TOLERANCES``), checked: argument errors are
+    raised here, before any file is read or any model is built."""
+    if getattr(args, "surface", None) is None:
+        return None
+    if args.masks is None:
+        raise ValueError("--surface needs --masks: boundary metrics are made against the ground truth")
+    tol = [float(t) for t in args.surface] or list(DEFAULT_TOLERANCES)
+    from . import ops
+    ops.surface_thresholds(tol)
+    return tol
+
+
+def surface_batch(meter, mask: torch.Tensor, target: torch.Tensor, args, lut) -> None:
+    """Boundary statistics of one batch, on the device: ``mask`` as ``SegEngine.predict`` encoded it (read back through the label
+    table that ``--encode`` inverts), ``target`` the raw ground truth with the dataset's table.  Only the statistics come to the
+    host, into ``meter``."""
+    from . import ops
+    ints, sums = ops.surface_stats(mask, target, args.num_classes, meter.tol, pred_lut=_fr.ENCODINGS[args.encode][1], lut=lut)
+    meter.update(ints.cpu().numpy(), sums.cpu().numpy())
+
+
 def metrics_from_counts(counts: np.ndarray) -> dict:
     """int64 [C,3] = (pred == c and label == c, pred == c, label == c) -> per-class IoU (None where the class occurs in neither),
     their mean over the classes that occur, and pixel accuracy (labels outside 0..C-1 count as wrong)."""
@@ -289,6 +318,12 @@ def metrics_from_counts(counts: np.ndarray) -> dict:
     total = int(pred.sum())
     return {"per_class_iou": iou, "mean_iou": float(np.mean(seen)) if seen else None,
             "pixel_accuracy": float(inter.sum()) / total if total else None, "pixels": total, "counts": counts.tolist()}
+
+
+def surface_line(s: dict) -> str:
+    nsd = " ".join(f"{t:g}px " + ("-" if v is None else f"{v:.4f}") for t, v in zip(s["tolerances"], s["mean_nsd"]))
+    return (f"* boundary (classes 1..): Dice {s['mean_dice']}  NSD [{nsd}]  Hausdorff {s['mean_hd']}  mean surface distance "
+            f"{s['mean_assd']}  unmatched (frame, class) pairs {sum(p['unmatched'] for p in s['per_class'])}")
 
 
 def _save_png(arr: np.ndarray, mode: str, path: str) -> float:
@@ -305,6 +340,11 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     """-> {"files": mask paths relative to --pred_dir, "metrics": dict or None, "seconds" (wall), "encode_seconds" (summed over
     the writer threads), "drain_seconds" (waiting for the writers after the last batch), "frames_per_second"}."""
     _fr.encode_table(args.encode, args.num_classes)          # argument errors before any model is built
+    tolerances = surface_tolerances(args)
+    meter = None
+    if tolerances is not None:
+        from .segloss.surface import SurfaceMeter
+        meter = SurfaceMeter(args.num_classes, tolerances)
     frames = _Frames(args)
     batches = plan_batches(frames.sizes, args.batch_size_per_gpu)
     engine = engine or build_engine(args)
@@ -314,7 +354,11 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     with cf.ThreadPoolExecutor(max_workers=MAX_WRITERS) as pool:
         for idx in batches:
             fr, mk = frames.load_batch(idx)
+            if mk is not None and meter is not None:
+                mk = mk.cuda(non_blocking=True).contiguous()     # predict_batch's upload, made here to keep the device copy
             out = list(predict_batch(engine, fr, mk, args, frames.lut))
+            if meter is not None:
+                surface_batch(meter, out[0], mk, args, frames.lut)
             mask = out.pop(0).cpu().numpy()
             over = out.pop(0).cpu().numpy() if args.overlay else None
             if mk is not None:
@@ -333,11 +377,15 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     if total is not None:
         metrics = metrics_from_counts(total.cpu().numpy())
         metrics["frames"] = len(frames.rel)
+        if meter is not None:
+            metrics["surface"] = meter.result()
         os.makedirs(args.pred_dir, exist_ok=True)
         with open(os.path.join(args.pred_dir, "metrics.json"), "w") as f:
             json.dump(metrics, f, indent=1, sort_keys=True)
         iou = " ".join("-" if v is None else f"{v:.4f}" for v in metrics["per_class_iou"])
         print(f"* IoU per class [{iou}]  mean IoU {metrics['mean_iou']}  pixel accuracy {metrics['pixel_accuracy']}")
+        if meter is not None:
+            print(surface_line(metrics["surface"]))
     n = len(frames.rel)
     print(f"{n} frames in {len(batches)} batches -> {args.pred_dir}: {wall:.2f} s, {n / wall:.2f} frames/s; PNG encoding {enc_s:.2f} "
           f"worker-seconds on {MAX_WRITERS} threads ({100 * enc_s / MAX_WRITERS / wall:.0f} % of the wall time per thread), "

@@ -708,6 +708,26 @@ int asis_predict_mask(void* stream, const float* logits, int B, int h, int w, in
                       uint8_t* mask, const uint8_t* frames, const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay,
                       const uint8_t* target, const uint8_t* lut, int64_t* counts);
 
+/* Boundary metrics (csrc/surface.hip): exact squared Euclidean distance transform of the class boundaries at native size and the
+ * per (frame, class) statistics behind Dice, normalised surface distance, Hausdorff and mean surface distance.
+ *   pred, target uint8 [B,H,W] raw pixel values; pred_lut, lut uint8 [256] their label tables; P = (pred_lut[pred] == c),
+ *     G = (lut[target] == c), a table value >= C is no class.  1 <= C <= 16, H, W <= 16384 (squared distances fit int32).
+ *   Edge pixels E(M): mask pixels on the image border or with a 4-neighbour outside the mask.  d2_G(p) = min over E(G) of the
+ *     squared Euclidean distance to p, exact.
+ *   ints int64 [B][C][7 + 2 T] += inter, n_pred, n_lab, e_pred, e_lab, max_pred, max_lab, hit_pred[T], hit_lab[T]:
+ *     max_pred = max over E(P) of d2_G, hit_pred[j] = #{p in E(P): d2_G(p) <= thr[j]}, _lab with the roles swapped; maxima and
+ *     hits of a (frame, class) with e_pred == 0 or e_lab == 0 stay 0.  The call adds (maxima: takes the maximum): zero it first.
+ *   sums double [B][C][2] = sum over E(P) of sqrt(d2_G), sum over E(G) of sqrt(d2_P): written, in a fixed order of additions
+ *     (bit-identical between calls).  thr int32 [T] on the HOST, 0 <= T <= 8.
+ *   One call handles the classes c0 .. c0 + nc - 1 of every frame; the call with c0 == 0 also makes the edge maps and the five
+ *     counts of ALL classes, so the calls of one batch go in ascending c0 over one workspace:
+ *     edges uint8 [B][2][H][W], g uint16 [B][2][nc][H][W] (vertical distances), partial double [B][2][nc][H].
+ *   d2 (optional, NULL = off) int32 [B][C][H][W]: the field of side d2_side (0 = pred, 1 = target) for the classes of the call;
+ *     a (frame, class) without edge pixels on that side is left untouched. */
+int asis_surface_stats(void* stream, const uint8_t* pred, const uint8_t* target, const uint8_t* pred_lut, const uint8_t* lut, int B,
+                       int H, int W, int C, int c0, int nc, const int32_t* thr, int T, uint8_t* edges, uint16_t* g,
+                       double* partial, int64_t* ints, double* sums, int32_t* d2, int d2_side);
+
 /* ---------------------------------------------------------------------------------------------
  * Dropout of the MaskTransformer decode head (backbones/masktrans_block.py:11-89: nn.Dropout(p) on the attention probabilities,
  * the projection output, behind GELU and behind fc2; eval_dinov2_masktrans.py:136-139 builds it with p = 0.1).  csrc/dropout.hip.
