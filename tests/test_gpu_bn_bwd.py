@@ -55,17 +55,12 @@ import torch
 import torch.nn.functional as F
 
 from adaptersis_amd import _lib, ops
+from tests.bound_helpers import DT, HALF, PAIR, SUBN, ULP32, U_ELEM, U_SUM, _bound, _err, _gen
 from tests.conftest import rel_l2
 from tests.mx_helpers import decode, e4m3, mx_bytes
 
 gpu = pytest.mark.gpu
 EPS = 1e-5
-ULP32 = 2.0 ** -23
-U_ELEM, U_SUM = 4, 16
-DT = [torch.float16, torch.bfloat16]
-HALF = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
-PAIR = {torch.float16: 2.0 ** -21, torch.bfloat16: 2.0 ** -15}
-SUBN = {torch.float16: 2.0 ** -25, torch.bfloat16: 0.0}
 
 # C -> (CW, RW, channel tiles) of bn_bwd_shape, and the branch each width is here for
 SHAPES = {4: (1, 256, 1),       # one chunk: a block is 256 rows of one float4
@@ -89,12 +84,6 @@ def _check_grid(rows: int, C: int, partial: torch.Tensor, capped: bool) -> None:
     assert _lib.lib().asis_bn_bwd_nblk(rows, C) == want == partial.shape[0], (rows, C, want, partial.shape)
     CW, RW, tiles = SHAPES[C]
     assert capped == (want * RW < rows), (rows, C, want, "grid-stride path expected" if capped else "one row per thread expected")
-
-
-def _gen(*key) -> torch.Generator:
-    g = torch.Generator()
-    g.manual_seed(sum((i + 1) * 7919 * int(k) for i, k in enumerate(key)) % (1 << 31))
-    return g
 
 
 def _stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
@@ -187,15 +176,6 @@ def _stage_ref(kind, x, gamma, beta, dU, factor, dtype):
         else F.max_pool2d(a, 3, 2, 1)
     out.backward(dU.to(dtype).permute(0, 3, 1, 2))
     return y.grad.permute(0, 2, 3, 1), be.grad, ga.grad
-
-
-def _bound(f32: torch.Tensor, ref: torch.Tensor, ulps: int):
-    yard = float((f32.double() - ref).abs().max())
-    return max(4 * yard, ulps * ULP32 * float(ref.abs().max())), yard
-
-
-def _err(got: torch.Tensor, ref: torch.Tensor) -> float:
-    return float((got.detach().double().cpu() - ref).abs().max())
 
 
 def _report(name, case, err, bound, yard):
