@@ -573,13 +573,11 @@ __global__ __launch_bounds__(256) void dwconv_t_kernel(const float* __restrict__
 
 }  // namespace
 
-#define DT_OK(dtype, name) ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, name ": bad dtype %d", dtype)
-
 extern "C" int asis_msda_bwd(void* stream, int dtype, const void* value, const float* offaw, int64_t ld_offaw,
                              const float* ref, const int32_t* shapes, const int32_t* starts, const float* dout, float* dvalue,
                              float* doffaw, int B, int Lq, int Lin, int M, int L, int P, int Dh) {
   ASIS_REQUIRE(value && offaw && ref && shapes && starts && dout && doffaw, "asis_msda_bwd: null pointer");
-  DT_OK(dtype, "asis_msda_bwd");
+  ASIS_DT_OK(dtype, "asis_msda_bwd");
   ASIS_REQUIRE(Dh % 8 == 0 && M >= 1 && M <= MAX_M && L * P >= 1 && L * P <= MAX_LP && M * Dh / 8 <= 256,
                "asis_msda_bwd: need Dh %% 8 == 0, M <= %d, L*P <= %d, M*Dh <= 2048", MAX_M, MAX_LP);
   ASIS_REQUIRE(ld_offaw >= (int64_t)M * L * P * 3, "asis_msda_bwd: ld_offaw too small");
@@ -596,13 +594,11 @@ extern "C" int asis_msda_bwd(void* stream, int dtype, const void* value, const f
     if (Dh % c == 0 && (int64_t)Lin * c * 4 <= 128 * 1024) { CH = c; break; }
   const bool skip_dvalue = dvalue == nullptr;  // the caller takes d value from asis_msda_sampling_matrix + a GEMM
   const bool tiled = skip_dvalue || (CH != 0 && (int64_t)B * (M * Dh / (CH ? CH : 1)) <= 0x7fffffff);
-  if (dtype == ASIS_F16) {
-    if (tiled) hipLaunchKernelGGL((msda_bwd_kernel<f16, false>), dim3((unsigned)grid), dim3(threads), 0, s, reinterpret_cast<const f16*>(value), offaw, ld_offaw, ref, shapes, starts, dout, dvalue, doffaw, B, Lq, Lin, M, L, P, Dh);
-    else hipLaunchKernelGGL((msda_bwd_kernel<f16, true>), dim3((unsigned)grid), dim3(threads), 0, s, reinterpret_cast<const f16*>(value), offaw, ld_offaw, ref, shapes, starts, dout, dvalue, doffaw, B, Lq, Lin, M, L, P, Dh);
-  } else {
-    if (tiled) hipLaunchKernelGGL((msda_bwd_kernel<bf16, false>), dim3((unsigned)grid), dim3(threads), 0, s, reinterpret_cast<const bf16*>(value), offaw, ld_offaw, ref, shapes, starts, dout, dvalue, doffaw, B, Lq, Lin, M, L, P, Dh);
-    else hipLaunchKernelGGL((msda_bwd_kernel<bf16, true>), dim3((unsigned)grid), dim3(threads), 0, s, reinterpret_cast<const bf16*>(value), offaw, ld_offaw, ref, shapes, starts, dout, dvalue, doffaw, B, Lq, Lin, M, L, P, Dh);
-  }
+  if (int rc = asis_dispatch16(dtype, "asis_msda_bwd", [&](auto t) {
+        using T = decltype(t);
+        if (tiled) hipLaunchKernelGGL((msda_bwd_kernel<T, false>), dim3((unsigned)grid), dim3(threads), 0, s, static_cast<const T*>(value), offaw, ld_offaw, ref, shapes, starts, dout, dvalue, doffaw, B, Lq, Lin, M, L, P, Dh);
+        else hipLaunchKernelGGL((msda_bwd_kernel<T, true>), dim3((unsigned)grid), dim3(threads), 0, s, static_cast<const T*>(value), offaw, ld_offaw, ref, shapes, starts, dout, dvalue, doffaw, B, Lq, Lin, M, L, P, Dh);
+      })) return rc;
   if (tiled && !skip_dvalue) {
     const unsigned nb = (unsigned)(B * (M * Dh / CH));
     const size_t lds = (size_t)Lin * CH * 4;
@@ -635,7 +631,7 @@ extern "C" int asis_dwconv_gelu_bwd(void* stream, int dtype, const float* x, con
                                     const int32_t* shapes, const int32_t* starts, int L, const float* dy, float* g,
                                     float* partial, void* dx, int B, int Ntok, int C) {
   ASIS_REQUIRE(x && w9 && bias && shapes && starts && dy && g && partial && dx, "asis_dwconv_gelu_bwd: null pointer");
-  DT_OK(dtype, "asis_dwconv_gelu_bwd");
+  ASIS_DT_OK(dtype, "asis_dwconv_gelu_bwd");
   ASIS_REQUIRE(C % 4 == 0 && C >= 4 && C / 4 <= 256 && 256 % (C / 4) == 0,
                "asis_dwconv_gelu_bwd: C=%d must be 4*2^k <= 1024", C);
   ASIS_REQUIRE(L >= 1 && B > 0 && Ntok > 0, "asis_dwconv_gelu_bwd: bad shape");
@@ -647,12 +643,11 @@ extern "C" int asis_dwconv_gelu_bwd(void* stream, int dtype, const float* x, con
                      C, rpb);
   int64_t gsz = (rows * (C / 4) + 255) / 256;
   if (gsz > 65535 * 4) gsz = 65535 * 4;
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((dwconv_t_kernel<f16>), dim3((unsigned)gsz), dim3(256), 0, s, g, w9, shapes, starts, L, reinterpret_cast<f16*>(dx),
-                       B, Ntok, C);
-  else
-    hipLaunchKernelGGL((dwconv_t_kernel<bf16>), dim3((unsigned)gsz), dim3(256), 0, s, g, w9, shapes, starts, L,
-                       reinterpret_cast<bf16*>(dx), B, Ntok, C);
+  if (int rc = asis_dispatch16(dtype, "asis_dwconv_gelu_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dwconv_t_kernel<T>), dim3((unsigned)gsz), dim3(256), 0, s, g, w9, shapes, starts, L, static_cast<T*>(dx),
+                           B, Ntok, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_dwconv_gelu_bwd");
   return ASIS_OK;
 }
@@ -664,7 +659,7 @@ extern "C" int asis_msda_value_grad(void* stream, int dtype, const float* offaw,
                                     int32_t* cnt, int32_t* offs, void* rec, float* dvalue, int B, int Lq, int Lin, int M, int L,
                                     int P, int Dh) {
   ASIS_REQUIRE(offaw && ref && shapes && starts && dout16 && amax && cnt && offs && rec && dvalue, "asis_msda_value_grad: null pointer");
-  DT_OK(dtype, "asis_msda_value_grad");
+  ASIS_DT_OK(dtype, "asis_msda_value_grad");
   ASIS_REQUIRE(M >= 1 && L * P >= 1 && L * P <= MAX_LP && Dh >= 2 && Dh % 2 == 0, "asis_msda_value_grad: bad shape (L*P <= %d, Dh even)", MAX_LP);
   ASIS_REQUIRE(ld_offaw >= (int64_t)M * L * P * 3, "asis_msda_value_grad: ld_offaw too small");
   ASIS_REQUIRE((int64_t)B * M * Lin < (1ll << 31) && (int64_t)Lq * L * P * 4 < (1ll << 31), "asis_msda_value_grad: shape too large");
@@ -679,12 +674,11 @@ extern "C" int asis_msda_value_grad(void* stream, int dtype, const float* offaw,
   hipLaunchKernelGGL((msda_taps_kernel<true>), dim3((unsigned)g), dim3(256), 0, s, offaw, ld_offaw, ref, shapes, starts,
                      reinterpret_cast<int*>(cnt), reinterpret_cast<int2*>(rec), cap, B, Lq, Lin, M, L, P);
   const int64_t waves = (int64_t)B * M * Lin;
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((msda_vgrad_kernel<f16>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const int*>(offs),
-                       reinterpret_cast<const int2*>(rec), cap, reinterpret_cast<const f16*>(dout16), amax, dvalue, B, Lq, Lin, M, Dh);
-  else
-    hipLaunchKernelGGL((msda_vgrad_kernel<bf16>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const int*>(offs),
-                       reinterpret_cast<const int2*>(rec), cap, reinterpret_cast<const bf16*>(dout16), amax, dvalue, B, Lq, Lin, M, Dh);
+  if (int rc = asis_dispatch16(dtype, "asis_msda_value_grad", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((msda_vgrad_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const int*>(offs),
+                           reinterpret_cast<const int2*>(rec), cap, static_cast<const T*>(dout16), amax, dvalue, B, Lq, Lin, M, Dh);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_msda_value_grad");
   return ASIS_OK;
 }
@@ -693,18 +687,17 @@ extern "C" int asis_msda_sampling_matrix(void* stream, int dtype, const float* o
                                          const int32_t* shapes, const int32_t* starts, void* ST, int64_t ldt, int B, int Lq,
                                          int Lin, int M, int L, int P) {
   ASIS_REQUIRE(offaw && ref && shapes && starts && ST, "asis_msda_sampling_matrix: null pointer");
-  DT_OK(dtype, "asis_msda_sampling_matrix");
+  ASIS_DT_OK(dtype, "asis_msda_sampling_matrix");
   ASIS_REQUIRE(M >= 1 && L * P >= 1 && L * P <= MAX_LP && ldt >= Lq, "asis_msda_sampling_matrix: bad shape (L*P <= %d, ldt >= Lq)", MAX_LP);
   ASIS_REQUIRE(ld_offaw >= (int64_t)M * L * P * 3, "asis_msda_sampling_matrix: ld_offaw too small");
   int64_t g = ((int64_t)B * Lq * M + 255) / 256;
   if (g > 65535 * 8) g = 65535 * 8;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((msda_sampling_matrix_kernel<f16>), dim3((unsigned)g), dim3(256), 0, s, offaw, ld_offaw, ref, shapes, starts,
-                       reinterpret_cast<f16*>(ST), ldt, B, Lq, Lin, M, L, P);
-  else
-    hipLaunchKernelGGL((msda_sampling_matrix_kernel<bf16>), dim3((unsigned)g), dim3(256), 0, s, offaw, ld_offaw, ref, shapes, starts,
-                       reinterpret_cast<bf16*>(ST), ldt, B, Lq, Lin, M, L, P);
+  if (int rc = asis_dispatch16(dtype, "asis_msda_sampling_matrix", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((msda_sampling_matrix_kernel<T>), dim3((unsigned)g), dim3(256), 0, s, offaw, ld_offaw, ref, shapes, starts,
+                           static_cast<T*>(ST), ldt, B, Lq, Lin, M, L, P);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_msda_sampling_matrix");
   return ASIS_OK;
 }

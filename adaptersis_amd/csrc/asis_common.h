@@ -43,6 +43,23 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+// ----- host side: the one dtype dispatch and the one launch-grid rule of every entry point --------------------------------
+#define ASIS_DT_OK(dtype, entry) ASIS_REQUIRE((dtype) == ASIS_F16 || (dtype) == ASIS_BF16, entry ": bad dtype %d", dtype)
+// Calls fn(T{}) with T = f16 or bf16 as `dtype` says, so that a launch is written once (`using T = decltype(t)`,
+// `static_cast<T*>(p)`).  Any other dtype reaches no launch: the entry returns what this returns, ASIS_EINVAL.
+template <typename F> static inline int asis_dispatch16(int dtype, const char* entry, F&& fn) {
+  if (dtype == ASIS_F16) fn(f16{});
+  else if (dtype == ASIS_BF16) fn(bf16{});
+  else ASIS_FAIL(ASIS_EINVAL, "%s: bad dtype %d", entry, dtype);
+  return ASIS_OK;
+}
+// blocks of a grid-stride launch over `total` items: at least 1, at most `cap` (no default: the cap sets the order of the
+// partial sums of a reduction kernel, so every call site names its own)
+static inline int asis_grid(int64_t total, int block, int cap) {
+  const int64_t g = (total + block - 1) / block;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+
 template <typename T> struct T16;
 template <> struct T16<f16> {
   typedef f16x8 v8;

@@ -391,24 +391,22 @@ static int attention_fwd_impl(void* stream, int dtype, const void* q, const void
   ASIS_REQUIRE(ldo % 4 == 0 && ldo >= (int64_t)H * HD, "asis_attention_fwd: ldo=%ld must be a multiple of 4 and >= H*64", (long)ldo);
   ASIS_REQUIRE(asis_aligned16(q) && asis_aligned16(k) && asis_aligned16(vt) && (((uintptr_t)o) & 7) == 0,
                "asis_attention_fwd: pointers must be 16-byte aligned");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_attention_fwd: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_attention_fwd");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((N + QT - 1) / QT, H, B), block(256);
   const float sl = scale * 1.4426950408889634f;
   // one kernel, four forms: a pre-scaled q (the folded form: -m rides in the score chain) or the scale applied in the softmax;
   // V pre-transposed or row-major (transposing LDS reads)
   const bool fold = prescaled != 0;
-#define ASIS_ATTN_PIPE_LAUNCH(TT, SC, VR)                                                                                 \
-  hipLaunchKernelGGL((attn_fwd_pipe_kernel<TT, SC, VR>), grid, block, 0, s, reinterpret_cast<const TT*>(q),              \
-                     reinterpret_cast<const TT*>(k), ldqk, reinterpret_cast<const TT*>(vt), ldvt, reinterpret_cast<TT*>(o), \
-                     reinterpret_cast<TT*>(o_lo), ldo, H, N1, sl, lse2, B1, N2, prescaled, mx_amax)
-  if (dtype == ASIS_F16) {
-    if (vrows) { if (fold) ASIS_ATTN_PIPE_LAUNCH(f16, 3, true); else ASIS_ATTN_PIPE_LAUNCH(f16, 0, true); }
-    else { if (fold) ASIS_ATTN_PIPE_LAUNCH(f16, 3, false); else ASIS_ATTN_PIPE_LAUNCH(f16, 0, false); }
-  } else {
-    if (vrows) { if (fold) ASIS_ATTN_PIPE_LAUNCH(bf16, 3, true); else ASIS_ATTN_PIPE_LAUNCH(bf16, 0, true); }
-    else { if (fold) ASIS_ATTN_PIPE_LAUNCH(bf16, 3, false); else ASIS_ATTN_PIPE_LAUNCH(bf16, 0, false); }
-  }
+#define ASIS_ATTN_PIPE_LAUNCH(SC, VR)                                                                                  \
+  hipLaunchKernelGGL((attn_fwd_pipe_kernel<T, SC, VR>), grid, block, 0, s, static_cast<const T*>(q),                   \
+                     static_cast<const T*>(k), ldqk, static_cast<const T*>(vt), ldvt, static_cast<T*>(o),              \
+                     static_cast<T*>(o_lo), ldo, H, N1, sl, lse2, B1, N2, prescaled, mx_amax)
+  if (int rc = asis_dispatch16(dtype, "asis_attention_fwd", [&](auto t) {
+        using T = decltype(t);
+        if (vrows) { if (fold) ASIS_ATTN_PIPE_LAUNCH(3, true); else ASIS_ATTN_PIPE_LAUNCH(0, true); }
+        else { if (fold) ASIS_ATTN_PIPE_LAUNCH(3, false); else ASIS_ATTN_PIPE_LAUNCH(0, false); }
+      })) return rc;
 #undef ASIS_ATTN_PIPE_LAUNCH
   ASIS_CHECK_LAUNCH("asis_attention_fwd");
   return ASIS_OK;
@@ -494,12 +492,10 @@ __global__ __launch_bounds__(256) void transpose_tokens_kernel(const T* __restri
 
 }  // namespace
 
-#define DT_OK(dtype, name) ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, name ": bad dtype %d", dtype)
-
 extern "C" int asis_transpose_tokens(void* stream, int dtype, const void* src, int64_t ld, void* dst, int64_t ldt, int B,
                                      int N, int C) {
   ASIS_REQUIRE(src && dst, "asis_transpose_tokens: null pointer");
-  DT_OK(dtype, "asis_transpose_tokens");
+  ASIS_DT_OK(dtype, "asis_transpose_tokens");
   ASIS_REQUIRE(B > 0 && N > 0 && C > 0 && C % 64 == 0, "asis_transpose_tokens: C=%d must be a positive multiple of 64", C);
   ASIS_REQUIRE(ld % 8 == 0 && ld >= C, "asis_transpose_tokens: ld=%ld must be a multiple of 8 and >= C", (long)ld);
   ASIS_REQUIRE(ldt % 64 == 0 && ldt >= N, "asis_transpose_tokens: ldt=%ld must be a multiple of 64 and >= N=%d", (long)ldt, N);
@@ -507,12 +503,11 @@ extern "C" int asis_transpose_tokens(void* stream, int dtype, const void* src, i
   ASIS_REQUIRE(B <= 65535 && C / 64 <= 65535, "asis_transpose_tokens: B / C too large");
   dim3 grid((unsigned)(ldt / 64), C / 64, B), block(256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((transpose_tokens_kernel<f16>), grid, block, 0, s, reinterpret_cast<const f16*>(src), ld,
-                       reinterpret_cast<f16*>(dst), ldt, N, C);
-  else
-    hipLaunchKernelGGL((transpose_tokens_kernel<bf16>), grid, block, 0, s, reinterpret_cast<const bf16*>(src), ld,
-                       reinterpret_cast<bf16*>(dst), ldt, N, C);
+  if (int rc = asis_dispatch16(dtype, "asis_transpose_tokens", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((transpose_tokens_kernel<T>), grid, block, 0, s, static_cast<const T*>(src), ld,
+                           static_cast<T*>(dst), ldt, N, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_transpose_tokens");
   return ASIS_OK;
 }

@@ -429,7 +429,7 @@ extern "C" int asis_attention_bwd_rows(void* stream, int dtype, const void* q, c
                                        void* dq, void* dk, void* dv, int64_t lddq, int B1, int N1, int B2, int N2, int H,
                                        float scale) {
   ASIS_REQUIRE(q && k && v && o && dO && lse2 && D && dq && dk && dv, "asis_attention_bwd_rows: null pointer");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_attention_bwd_rows: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_attention_bwd_rows");
   ASIS_REQUIRE(B1 > 0 && B2 >= 0 && H > 0 && N1 > 0 && (B2 == 0 || N2 > 0) && B1 + B2 <= 65535 && H <= 65535,
                "asis_attention_bwd_rows: bad shape B1=%d N1=%d B2=%d N2=%d H=%d", B1, N1, B2, N2, H);
   ASIS_REQUIRE(scale > 0.f, "asis_attention_bwd_rows: scale must be positive");
@@ -444,10 +444,10 @@ extern "C" int asis_attention_bwd_rows(void* stream, int dtype, const void* q, c
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int ex;
   const bool cfold = frexpf(scale, &ex) == 0.5f;   // a power of two: c dO / c V are exact in 16 bits (barring subnormals)
-  if (dtype == ASIS_F16)
-    launch_rows<f16>(s, q, k, v, ld, o, ldo, dO, lddo, lse2, D, dq, dk, dv, lddq, B1, N1, B2, N2, H, scale, cfold);
-  else
-    launch_rows<bf16>(s, q, k, v, ld, o, ldo, dO, lddo, lse2, D, dq, dk, dv, lddq, B1, N1, B2, N2, H, scale, cfold);
+  if (int rc = asis_dispatch16(dtype, "asis_attention_bwd_rows", [&](auto t) {
+        using T = decltype(t);
+        launch_rows<T>(s, q, k, v, ld, o, ldo, dO, lddo, lse2, D, dq, dk, dv, lddq, B1, N1, B2, N2, H, scale, cfold);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_attention_bwd_rows");
   return ASIS_OK;
 }

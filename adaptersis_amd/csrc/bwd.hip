@@ -12,13 +12,6 @@
 
 namespace {
 
-inline int grid_for(int64_t total, int block = 256, int cap = 256 * 16) {
-  int64_t g = (total + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // source taps of output index o for align_corners=True (as upsample kernel in convmisc.hip)
 __device__ __forceinline__ void tap_ac_true(int o, float r, int in, int& i0, int& i1, float& l0, float& l1) {
   const float s = r * (float)o;
@@ -463,7 +456,7 @@ __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, int64
 
 }  // namespace
 
-extern "C" int asis_ew_blocks(int64_t total_chunks) { return grid_for(total_chunks); }
+extern "C" int asis_ew_blocks(int64_t total_chunks) { return asis_grid(total_chunks, 256, 256 * 16); }
 
 // block shape of the BatchNorm-backward kernels: CW channel chunks (4 channels each) x RW rows, CW*RW <= 256.
 // CW = C/4 when that divides 256 (every power-of-two width), else the largest divisor of C/4 that is <= 64
@@ -528,16 +521,15 @@ extern "C" int asis_maxpool_bn_relu_bwd(void* stream, const float* dy, const flo
 extern "C" int asis_dilate2(void* stream, int dtype, const void* in, const void* in_lo, void* out, void* out_lo, int B, int OH,
                             int OW, int Hd, int Wd, int C) {
   ASIS_REQUIRE(in && out && (in_lo == nullptr) == (out_lo == nullptr), "asis_dilate2: null pointer / lo halves go together");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_dilate2: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_dilate2");
   ASIS_REQUIRE(C % 8 == 0 && C > 0 && Hd >= 2 * OH - 1 && Wd >= 2 * OW - 1, "asis_dilate2: C %% 8 == 0 and Hd >= 2*OH-1 needed");
   const int64_t total = (int64_t)B * Hd * Wd * (C / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((dilate2_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, (const f16*)in, (const f16*)in_lo, (f16*)out,
-                       (f16*)out_lo, B, OH, OW, Hd, Wd, C);
-  else
-    hipLaunchKernelGGL((dilate2_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16*)in, (const bf16*)in_lo,
-                       (bf16*)out, (bf16*)out_lo, B, OH, OW, Hd, Wd, C);
+  if (int rc = asis_dispatch16(dtype, "asis_dilate2", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dilate2_kernel<T>), dim3(asis_grid(total, 256, 256 * 16)), dim3(256), 0, s, static_cast<const T*>(in), static_cast<const T*>(in_lo), static_cast<T*>(out),
+                           static_cast<T*>(out_lo), B, OH, OW, Hd, Wd, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_dilate2");
   return ASIS_OK;
 }
@@ -547,18 +539,17 @@ static int bn_bwd_apply_impl(void* stream, int dtype, const float* g, const floa
                              const float* mx_amax, float* partial, int64_t R, int C) {
   ASIS_REQUIRE(g && x && mean && invstd && gamma && dgamma && dbeta && out && partial, "asis_bn_bwd_apply: null pointer");
   ASIS_REQUIRE(C % 4 == 0 && C >= 4, "asis_bn_bwd_apply: C=%d must be a positive multiple of 4", C);
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_bn_bwd_apply: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_bn_bwd_apply");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const float inv_n = (float)(1.0 / count);
   int CW, RW, tiles;
   bn_bwd_shape(C, &CW, &RW, &tiles);
   const int nblk = asis_bn_bwd_nblk(R, C);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<f16>), dim3(nblk, tiles), dim3(CW * RW), 0, s, g, x, mean, invstd, gamma, dgamma,
-                       dbeta, inv_n, reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), partial, R, C, CW, RW, mx_amax);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16>), dim3(nblk, tiles), dim3(CW * RW), 0, s, g, x, mean, invstd, gamma, dgamma,
-                       dbeta, inv_n, reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), partial, R, C, CW, RW, mx_amax);
+  if (int rc = asis_dispatch16(dtype, "asis_bn_bwd_apply", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(nblk, tiles), dim3(CW * RW), 0, s, g, x, mean, invstd, gamma, dgamma,
+                           dbeta, inv_n, static_cast<T*>(out), static_cast<T*>(out_lo), partial, R, C, CW, RW, mx_amax);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_bn_bwd_apply");
   return ASIS_OK;
 }
@@ -596,10 +587,10 @@ extern "C" int asis_sgd_momentum(void* stream, float* p, const float* g, float* 
   ASIS_REQUIRE(p && g && buf && n >= 0, "asis_sgd_momentum: bad arguments");
   if (n == 0) return ASIS_OK;
   if (asis_aligned16(p) && asis_aligned16(g) && asis_aligned16(buf))
-    hipLaunchKernelGGL(sgd_vec_kernel, dim3(grid_for(n / 8 + 1, 256, 256 * 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
+    hipLaunchKernelGGL(sgd_vec_kernel, dim3(asis_grid(n / 8 + 1, 256, 256 * 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
                        g, buf, n, lr, momentum, weight_decay, inv_scale, first_step, (int*)nullptr, 0);
   else
-    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, buf, n, lr,
+    hipLaunchKernelGGL(sgd_kernel, dim3(asis_grid(n, 256, 256 * 16)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, buf, n, lr,
                        momentum, weight_decay, inv_scale, first_step);
   ASIS_CHECK_LAUNCH("asis_sgd_momentum");
   return ASIS_OK;
@@ -611,9 +602,9 @@ extern "C" int asis_grad_guard(void* stream, const float* g, int64_t n, int32_t*
   if (reset) ASIS_REQUIRE(hipMemsetAsync(guard, 0, sizeof(int32_t), s) == hipSuccess, "asis_grad_guard: memset failed");
   if (n == 0) return ASIS_OK;
   if (asis_aligned16(g))
-    hipLaunchKernelGGL(nonfinite_vec_kernel, dim3(grid_for(n / 16 + 1, 256, 256 * 32)), dim3(256), 0, s, g, n, reinterpret_cast<int*>(guard));
+    hipLaunchKernelGGL(nonfinite_vec_kernel, dim3(asis_grid(n / 16 + 1, 256, 256 * 32)), dim3(256), 0, s, g, n, reinterpret_cast<int*>(guard));
   else
-    hipLaunchKernelGGL(nonfinite_kernel, dim3(grid_for(n)), dim3(256), 0, s, g, n, reinterpret_cast<int*>(guard));
+    hipLaunchKernelGGL(nonfinite_kernel, dim3(asis_grid(n, 256, 256 * 16)), dim3(256), 0, s, g, n, reinterpret_cast<int*>(guard));
   ASIS_CHECK_LAUNCH("asis_grad_guard");
   return ASIS_OK;
 }
@@ -623,10 +614,10 @@ extern "C" int asis_sgd_momentum_guarded(void* stream, float* p, const float* g,
   ASIS_REQUIRE(p && g && buf && guard && n >= 0, "asis_sgd_momentum_guarded: bad arguments");
   if (n == 0) return ASIS_OK;
   if (asis_aligned16(p) && asis_aligned16(g) && asis_aligned16(buf))
-    hipLaunchKernelGGL(sgd_vec_kernel, dim3(grid_for(n / 8 + 1, 256, 256 * 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
+    hipLaunchKernelGGL(sgd_vec_kernel, dim3(asis_grid(n / 8 + 1, 256, 256 * 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
                        g, buf, n, lr, momentum, weight_decay, inv_scale, first_step, reinterpret_cast<int*>(guard), count_skip);
   else
-    hipLaunchKernelGGL(sgd_guarded_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, buf, n,
+    hipLaunchKernelGGL(sgd_guarded_kernel, dim3(asis_grid(n, 256, 256 * 16)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, buf, n,
                        lr, momentum, weight_decay, inv_scale, first_step, reinterpret_cast<int*>(guard), count_skip);
   ASIS_CHECK_LAUNCH("asis_sgd_momentum_guarded");
   return ASIS_OK;
@@ -658,7 +649,7 @@ extern "C" int asis_grad_pack_bf16(void* stream, const float* g, int64_t n, void
   ASIS_REQUIRE(g && out && n >= 0 && n % 4 == 0, "asis_grad_pack_bf16: null pointer or n=%ld not a multiple of 4", (long)n);
   ASIS_REQUIRE(asis_aligned16(g) && (reinterpret_cast<uintptr_t>(out) & 7) == 0, "asis_grad_pack_bf16: misaligned buffers");
   if (n == 0) return ASIS_OK;
-  hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(asis_grid(n / 4, 256, 256 * 16)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const float4*>(g), reinterpret_cast<uint2*>(out), n / 4);
   ASIS_CHECK_LAUNCH("asis_grad_pack_bf16");
   return ASIS_OK;
@@ -668,7 +659,7 @@ extern "C" int asis_grad_unpack_bf16(void* stream, const void* in, int64_t n, fl
   ASIS_REQUIRE(g && in && n >= 0 && n % 4 == 0, "asis_grad_unpack_bf16: null pointer or n=%ld not a multiple of 4", (long)n);
   ASIS_REQUIRE(asis_aligned16(g) && (reinterpret_cast<uintptr_t>(in) & 7) == 0, "asis_grad_unpack_bf16: misaligned buffers");
   if (n == 0) return ASIS_OK;
-  hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(asis_grid(n / 4, 256, 256 * 16)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const uint2*>(in), reinterpret_cast<float4*>(g), n / 4);
   ASIS_CHECK_LAUNCH("asis_grad_unpack_bf16");
   return ASIS_OK;
@@ -684,7 +675,7 @@ extern "C" int asis_zero(void* stream, void* p, int64_t bytes) {
 extern "C" int asis_scale_f32(void* stream, float* x, int64_t n, float a) {
   ASIS_REQUIRE(x && n >= 0, "asis_scale_f32: bad arguments");
   if (n == 0) return ASIS_OK;
-  hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, n, a);
+  hipLaunchKernelGGL(scale_kernel, dim3(asis_grid(n, 256, 256 * 16)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, n, a);
   ASIS_CHECK_LAUNCH("asis_scale_f32");
   return ASIS_OK;
 }

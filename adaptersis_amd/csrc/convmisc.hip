@@ -10,13 +10,6 @@
 
 namespace {
 
-inline int grid_for(int64_t total, int block = 256, int cap = 256 * 32) {
-  int64_t g = (total + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // ---- stem conv: img fp32 NCHW [B,3,H,W] -> fp32 NHWC [B,OH,OW,Cout]; w [Cout,3,3,3] ----------
 __global__ __launch_bounds__(256) void conv3x3_c3_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                          float* __restrict__ out, int B, int H, int W, int OH, int OW,
@@ -589,8 +582,6 @@ __global__ __launch_bounds__(256) void add_f32_kernel(const float4* __restrict__
 
 }  // namespace
 
-#define DT_OK(dtype, name) ASIS_REQUIRE((dtype) == ASIS_F16 || (dtype) == ASIS_BF16, name ": bad dtype %d", dtype)
-
 extern "C" int asis_conv3x3_c3(void* stream, const float* img, const float* w, float* out, int B, int H, int W, int Cout,
                                int stride, int pad) {
   ASIS_REQUIRE(img && w && out, "asis_conv3x3_c3: null pointer");
@@ -607,10 +598,7 @@ extern "C" int asis_conv3x3_c3(void* stream, const float* img, const float* w, f
 }
 
 extern "C" int asis_colstats_nparts(int64_t R) {
-  int64_t n = asis_cdiv(R, 256);
-  if (n > 2048) n = 2048;
-  if (n < 1) n = 1;
-  return (int)n;
+  return asis_grid(R, 256, 2048);
 }
 
 extern "C" int asis_colstats(void* stream, const float* x, int64_t R, int C, float* partial) {
@@ -658,15 +646,14 @@ static int bn_act_impl(void* stream, int dtype, const float* x, const float* sca
                        const float* mx_amax, int64_t R, int C) {
   ASIS_REQUIRE(x && scale && shift && out, "asis_bn_act: null pointer");
   ASIS_REQUIRE(C % 4 == 0 && C > 0, "asis_bn_act: C=%d must be a multiple of 4", C);
-  DT_OK(dtype, "asis_bn_act");
+  ASIS_DT_OK(dtype, "asis_bn_act");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = R * (C / 4);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((bn_act_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, x, scale, shift, relu,
-                       reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), R, C, mx_amax);
-  else
-    hipLaunchKernelGGL((bn_act_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, x, scale, shift, relu,
-                       reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), R, C, mx_amax);
+  if (int rc = asis_dispatch16(dtype, "asis_bn_act", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_act_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, x, scale, shift, relu,
+                           static_cast<T*>(out), static_cast<T*>(out_lo), R, C, mx_amax);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_bn_act");
   return ASIS_OK;
 }
@@ -684,16 +671,15 @@ extern "C" int asis_bn_relu_maxpool(void* stream, int dtype, const float* x, con
                                     void* out, void* out_lo, int B, int H, int W, int C) {
   ASIS_REQUIRE(x && scale && shift && out, "asis_bn_relu_maxpool: null pointer");
   ASIS_REQUIRE(C % 4 == 0 && C > 0, "asis_bn_relu_maxpool: C=%d must be a multiple of 4", C);
-  DT_OK(dtype, "asis_bn_relu_maxpool");
+  ASIS_DT_OK(dtype, "asis_bn_relu_maxpool");
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = (int64_t)B * OH * OW * (C / 4);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((bn_relu_maxpool_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, x, scale, shift,
-                       reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), B, H, W, OH, OW, C);
-  else
-    hipLaunchKernelGGL((bn_relu_maxpool_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, x, scale, shift,
-                       reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), B, H, W, OH, OW, C);
+  if (int rc = asis_dispatch16(dtype, "asis_bn_relu_maxpool", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_relu_maxpool_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, x, scale, shift,
+                           static_cast<T*>(out), static_cast<T*>(out_lo), B, H, W, OH, OW, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_bn_relu_maxpool");
   return ASIS_OK;
 }
@@ -702,29 +688,23 @@ static int bn_relu_upsample_impl(void* stream, int dtype, const float* x, const 
                                  const float* mx_amax, int B, int H, int W, int C, int factor) {
   ASIS_REQUIRE(x && scale && shift && out, "asis_bn_relu_upsample: null pointer");
   ASIS_REQUIRE(C % 4 == 0 && C > 0 && factor >= 1, "asis_bn_relu_upsample: bad C=%d / factor=%d", C, factor);
-  DT_OK(dtype, "asis_bn_relu_upsample");
+  ASIS_DT_OK(dtype, "asis_bn_relu_upsample");
   const int OH = H * factor, OW = W * factor;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = (int64_t)B * OH * OW * (C / 4);
   const long gx8 = asis_cdiv((long)OW * (C / 8), 256);
-  if (C % 8 == 0 && OH <= 65535 && B <= 65535 && gx8 * OH * B < (1L << 31) && asis_aligned16(out) &&
-      (!out_lo || asis_aligned16(out_lo)) && asis_aligned16(x)) {
-    const dim3 grid8((unsigned)gx8, (unsigned)asis_cdiv(OH, 4), (unsigned)B);  // 4 = ROWS of the kernel
-    if (dtype == ASIS_F16)
-      hipLaunchKernelGGL((bn_relu_upsample8_kernel<f16>), grid8, dim3(256), 0, s, x, scale, shift, reinterpret_cast<f16*>(out),
-                         reinterpret_cast<f16*>(out_lo), H, W, OH, OW, C, mx_amax);
-    else
-      hipLaunchKernelGGL((bn_relu_upsample8_kernel<bf16>), grid8, dim3(256), 0, s, x, scale, shift, reinterpret_cast<bf16*>(out),
-                         reinterpret_cast<bf16*>(out_lo), H, W, OH, OW, C, mx_amax);
-    ASIS_CHECK_LAUNCH("asis_bn_relu_upsample");
-    return ASIS_OK;
-  }
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((bn_relu_upsample_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, x, scale, shift,
-                       reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), mx_amax, B, H, W, OH, OW, C);
-  else
-    hipLaunchKernelGGL((bn_relu_upsample_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, x, scale, shift,
-                       reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), mx_amax, B, H, W, OH, OW, C);
+  const bool vec8 = C % 8 == 0 && OH <= 65535 && B <= 65535 && gx8 * OH * B < (1L << 31) && asis_aligned16(out) &&
+                    (!out_lo || asis_aligned16(out_lo)) && asis_aligned16(x);
+  const dim3 grid8((unsigned)gx8, (unsigned)asis_cdiv(OH, 4), (unsigned)B);  // 4 = ROWS of the kernel
+  if (int rc = asis_dispatch16(dtype, "asis_bn_relu_upsample", [&](auto t) {
+        using T = decltype(t);
+        if (vec8)
+          hipLaunchKernelGGL((bn_relu_upsample8_kernel<T>), grid8, dim3(256), 0, s, x, scale, shift, static_cast<T*>(out),
+                             static_cast<T*>(out_lo), H, W, OH, OW, C, mx_amax);
+        else
+          hipLaunchKernelGGL((bn_relu_upsample_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, x, scale, shift,
+                             static_cast<T*>(out), static_cast<T*>(out_lo), mx_amax, B, H, W, OH, OW, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_bn_relu_upsample");
   return ASIS_OK;
 }
@@ -762,7 +742,7 @@ extern "C" int asis_bn_relu_absmax(void* stream, const float* x, const float* sc
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ASIS_REQUIRE(hipMemsetAsync(amax, 0, sizeof(float), s) == hipSuccess, "asis_bn_relu_absmax: memset failed");
   if (P == 0) return ASIS_OK;
-  hipLaunchKernelGGL(bn_relu_absmax_kernel, dim3(grid_for(asis_cdiv(P * (C / 4), 4), 256, 1024)), dim3(256), 0, s, x, scale, shift, P, C, relu, amax);
+  hipLaunchKernelGGL(bn_relu_absmax_kernel, dim3(asis_grid(asis_cdiv(P * (C / 4), 4), 256, 1024)), dim3(256), 0, s, x, scale, shift, P, C, relu, amax);
   ASIS_CHECK_LAUNCH("asis_bn_relu_absmax");
   return ASIS_OK;
 }
@@ -770,7 +750,7 @@ extern "C" int asis_bn_relu_absmax(void* stream, const float* x, const float* sc
 extern "C" int asis_absmax_16(void* stream, int dtype, const void* x, int64_t rows, int cols, int64_t ld, float* amax) {
   ASIS_REQUIRE(x && amax && rows >= 0 && cols > 0 && cols % 8 == 0 && ld % 8 == 0 && ld >= cols && asis_aligned16(x),
                "asis_absmax_16: null pointer, or cols / ld not multiples of 8, or misaligned");
-  DT_OK(dtype, "asis_absmax_16");
+  ASIS_DT_OK(dtype, "asis_absmax_16");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ASIS_REQUIRE(hipMemsetAsync(amax, 0, sizeof(float), s) == hipSuccess, "asis_absmax_16: memset failed");
   if (rows == 0) return ASIS_OK;
@@ -778,10 +758,10 @@ extern "C" int asis_absmax_16(void* stream, int dtype, const void* x, int64_t ro
   if (gx > 1024) gx = 1024;
   int64_t gy = asis_cdiv(1024, gx);
   if (gy > rows) gy = rows;
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((absmax16_kernel<f16>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, reinterpret_cast<const f16*>(x), rows, cols, ld, amax);
-  else
-    hipLaunchKernelGGL((absmax16_kernel<bf16>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, reinterpret_cast<const bf16*>(x), rows, cols, ld, amax);
+  if (int rc = asis_dispatch16(dtype, "asis_absmax_16", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((absmax16_kernel<T>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, static_cast<const T*>(x), rows, cols, ld, amax);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_absmax_16");
   return ASIS_OK;
 }
@@ -791,16 +771,15 @@ extern "C" int asis_mx_from_pair(void* stream, int dtype, const void* hi, const 
   ASIS_REQUIRE(hi && lo && out_mx && amax && rows >= 0 && cols > 0 && cols % 8 == 0 && ld_in % 8 == 0 && ld_out % 8 == 0 && ld_in >= cols &&
                    ld_out >= cols && asis_aligned16(hi) && asis_aligned16(lo) && asis_aligned16(out_mx),
                "asis_mx_from_pair: null pointer, or cols / leading dimensions not multiples of 8, or misaligned");
-  DT_OK(dtype, "asis_mx_from_pair");
+  ASIS_DT_OK(dtype, "asis_mx_from_pair");
   if (rows == 0) return ASIS_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = rows * (cols / 8);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((mx_from_pair_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, reinterpret_cast<const f16*>(hi),
-                       reinterpret_cast<const f16*>(lo), ld_in, reinterpret_cast<f16*>(out_mx), ld_out, rows, cols, amax, wside);
-  else
-    hipLaunchKernelGGL((mx_from_pair_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, reinterpret_cast<const bf16*>(hi),
-                       reinterpret_cast<const bf16*>(lo), ld_in, reinterpret_cast<bf16*>(out_mx), ld_out, rows, cols, amax, wside);
+  if (int rc = asis_dispatch16(dtype, "asis_mx_from_pair", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((mx_from_pair_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, static_cast<const T*>(hi),
+                           static_cast<const T*>(lo), ld_in, static_cast<T*>(out_mx), ld_out, rows, cols, amax, wside);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_mx_from_pair");
   return ASIS_OK;
 }
@@ -810,19 +789,18 @@ static int pack_conv_weight_impl(void* stream, int dtype, const float* w, void* 
   ASIS_REQUIRE(w && out, "asis_pack_conv_weight: null pointer");
   ASIS_REQUIRE(part >= 0 && part <= 2 && (part != 2 || mx_amax), "asis_pack_conv_weight: part 2 (MX weight side) needs amax");
   ASIS_REQUIRE(mode == 0 || mode == 1, "asis_pack_conv_weight: bad mode %d", mode);
-  DT_OK(dtype, "asis_pack_conv_weight");
+  ASIS_DT_OK(dtype, "asis_pack_conv_weight");
   const int CoP = (Cout + 7) / 8 * 8;
   const int rows = mode == 0 ? Cout : Cin;
   const int K = mode == 0 ? KH * KW * Cin : KH * KW * CoP;
   ASIS_REQUIRE(ldo >= K && ldo % 8 == 0, "asis_pack_conv_weight: ldo=%ld must be a multiple of 8 and >= %d", (long)ldo, K);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = (int64_t)rows * ldo;
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((pack_conv_weight_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, w,
-                       reinterpret_cast<f16*>(out), Cout, Cin, KH, KW, mode, CoP, ldo, rows, part, mx_amax);
-  else
-    hipLaunchKernelGGL((pack_conv_weight_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, w,
-                       reinterpret_cast<bf16*>(out), Cout, Cin, KH, KW, mode, CoP, ldo, rows, part, mx_amax);
+  if (int rc = asis_dispatch16(dtype, "asis_pack_conv_weight", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pack_conv_weight_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, w,
+                           static_cast<T*>(out), Cout, Cin, KH, KW, mode, CoP, ldo, rows, part, mx_amax);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_pack_conv_weight");
   return ASIS_OK;
 }
@@ -878,7 +856,7 @@ __global__ __launch_bounds__(256) void pack_conv3x3_pair_tiled_kernel(const floa
 extern "C" int asis_pack_conv_weight_pair(void* stream, int dtype, const float* w, void* out_hi, void* out_lo, int Cout, int Cin,
                                           int KH, int KW, int mode, int64_t ldo, const float* amax) {
   ASIS_REQUIRE(w && out_hi && out_lo, "asis_pack_conv_weight_pair: null pointer");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_pack_conv_weight_pair: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_pack_conv_weight_pair");
   ASIS_REQUIRE(mode == 0 || mode == 1, "asis_pack_conv_weight_pair: mode must be 0 (forward) or 1 (dgrad)");
   const int CoP = (Cout + 7) / 8 * 8;
   const int rows = mode == 0 ? Cout : Cin;
@@ -890,24 +868,17 @@ extern "C" int asis_pack_conv_weight_pair(void* stream, int dtype, const float* 
   const bool tiled = tiled_on && KH == 3 && KW == 3 && ldo == K && ldo % 2 == 0 && asis_aligned16(w) &&
                      (reinterpret_cast<uintptr_t>(out_hi) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_lo) & 3) == 0 &&
                      (mode == 0 ? Cin % 128 == 0 : (Cout % 64 == 0 && Cin % 16 == 0));
-  if (tiled) {
-    const int64_t nblk = mode == 0 ? (int64_t)Cout * (Cin / 128) : (int64_t)(Cout / 64) * (Cin / 16);
-    ASIS_REQUIRE(nblk < (1ll << 31), "asis_pack_conv_weight_pair: too many tiles");
-    if (dtype == ASIS_F16)
-      hipLaunchKernelGGL((pack_conv3x3_pair_tiled_kernel<f16>), dim3((unsigned)nblk), dim3(256), 0, s, w, reinterpret_cast<f16*>(out_hi),
-                         reinterpret_cast<f16*>(out_lo), Cout, Cin, mode, ldo, amax);
-    else
-      hipLaunchKernelGGL((pack_conv3x3_pair_tiled_kernel<bf16>), dim3((unsigned)nblk), dim3(256), 0, s, w, reinterpret_cast<bf16*>(out_hi),
-                         reinterpret_cast<bf16*>(out_lo), Cout, Cin, mode, ldo, amax);
-    ASIS_CHECK_LAUNCH("asis_pack_conv_weight_pair");
-    return ASIS_OK;
-  }
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((pack_conv_weight_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, w, reinterpret_cast<f16*>(out_hi), Cout,
-                       Cin, KH, KW, mode, CoP, ldo, rows, 0, amax, reinterpret_cast<f16*>(out_lo));
-  else
-    hipLaunchKernelGGL((pack_conv_weight_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, w, reinterpret_cast<bf16*>(out_hi), Cout,
-                       Cin, KH, KW, mode, CoP, ldo, rows, 0, amax, reinterpret_cast<bf16*>(out_lo));
+  const int64_t nblk = mode == 0 ? (int64_t)Cout * (Cin / 128) : (int64_t)(Cout / 64) * (Cin / 16);
+  if (tiled) ASIS_REQUIRE(nblk < (1ll << 31), "asis_pack_conv_weight_pair: too many tiles");
+  if (int rc = asis_dispatch16(dtype, "asis_pack_conv_weight_pair", [&](auto t) {
+        using T = decltype(t);
+        if (tiled)
+          hipLaunchKernelGGL((pack_conv3x3_pair_tiled_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, s, w, static_cast<T*>(out_hi),
+                             static_cast<T*>(out_lo), Cout, Cin, mode, ldo, amax);
+        else
+          hipLaunchKernelGGL((pack_conv_weight_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, w, static_cast<T*>(out_hi), Cout,
+                             Cin, KH, KW, mode, CoP, ldo, rows, 0, amax, static_cast<T*>(out_lo));
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_pack_conv_weight_pair");
   return ASIS_OK;
 }
@@ -929,15 +900,14 @@ static int decoder_input_impl(void* stream, int dtype, const float* xs, int64_t 
   ASIS_REQUIRE(D % 4 == 0 && h4 <= h && w4 <= w, "asis_decoder_input: bad shape");
   ASIS_REQUIRE(c4_bstride % 4 == 0 && xs_bstride % 4 == 0 && vit_bstride % 4 == 0 && asis_aligned16(xs) &&
                    asis_aligned16(c4) && asis_aligned16(vit), "asis_decoder_input: alignment");
-  DT_OK(dtype, "asis_decoder_input");
+  ASIS_DT_OK(dtype, "asis_decoder_input");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = (int64_t)B * h * w * (3 * D / 4);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((decoder_input_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, xs, xs_bstride, c4, c4_bstride, vit,
-                       vit_bstride, reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), B, h, w, h4, w4, D, mx_amax);
-  else
-    hipLaunchKernelGGL((decoder_input_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, xs, xs_bstride, c4, c4_bstride, vit,
-                       vit_bstride, reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), B, h, w, h4, w4, D, mx_amax);
+  if (int rc = asis_dispatch16(dtype, "asis_decoder_input", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((decoder_input_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, xs, xs_bstride, c4, c4_bstride, vit,
+                           vit_bstride, static_cast<T*>(out), static_cast<T*>(out_lo), B, h, w, h4, w4, D, mx_amax);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_decoder_input");
   return ASIS_OK;
 }
@@ -957,11 +927,13 @@ extern "C" int asis_decoder_input_mx(void* stream, int dtype, const float* xs, i
 extern "C" int asis_swiglu_split(void* stream, int dtype, const float* x12, void* out, void* out_lo, int64_t R, int Hd) {
   ASIS_REQUIRE(x12 && out && Hd % 4 == 0 && Hd > 0, "asis_swiglu: bad arguments");
   ASIS_REQUIRE(asis_aligned16(x12) && (((uintptr_t)out) & 7) == 0 && (((uintptr_t)out_lo) & 7) == 0, "asis_swiglu: alignment");
-  DT_OK(dtype, "asis_swiglu");
+  ASIS_DT_OK(dtype, "asis_swiglu");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = R * (Hd / 4);
-  if (dtype == ASIS_F16) hipLaunchKernelGGL((swiglu_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, x12, reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), R, Hd);
-  else hipLaunchKernelGGL((swiglu_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, x12, reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), R, Hd);
+  if (int rc = asis_dispatch16(dtype, "asis_swiglu", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((swiglu_kernel<T>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, s, x12, static_cast<T*>(out), static_cast<T*>(out_lo), R, Hd);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_swiglu");
   return ASIS_OK;
 }
@@ -976,7 +948,7 @@ extern "C" int asis_copy_channels(void* stream, const void* src, int64_t src_ld_
   ASIS_REQUIRE(row_bytes % 16 == 0 && src_ld_bytes % 16 == 0 && dst_ld_bytes % 16 == 0 && asis_aligned16(src) && asis_aligned16(dst),
                "asis_copy_channels: everything must be 16-byte granular");
   const int64_t total = rows * (row_bytes / 16);
-  hipLaunchKernelGGL(copy_channels_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(copy_channels_kernel, dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const uint4*>(src), src_ld_bytes / 16, (const uint4*)nullptr, reinterpret_cast<uint4*>(dst),
                      dst_ld_bytes / 16, rows, (int)(row_bytes / 16));
   ASIS_CHECK_LAUNCH("asis_copy_channels");
@@ -988,7 +960,7 @@ extern "C" int asis_add_f32(void* stream, const float* a, const float* b, float*
   ASIS_REQUIRE(a && b && out, "asis_add_f32: null pointer");
   ASIS_REQUIRE(n % 4 == 0 && batch >= 1 && stride_a % 4 == 0 && stride_b % 4 == 0 && stride_out % 4 == 0 &&
                    asis_aligned16(a) && asis_aligned16(b) && asis_aligned16(out), "asis_add_f32: alignment");
-  hipLaunchKernelGGL(add_f32_kernel, dim3(grid_for(n / 4 * batch)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(add_f32_kernel, dim3(asis_grid(n / 4 * batch, 256, 256 * 32)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const float4*>(a), reinterpret_cast<const float4*>(b),
                      reinterpret_cast<float4*>(out), n / 4, batch, stride_a / 4, stride_b / 4, stride_out / 4);
   ASIS_CHECK_LAUNCH("asis_add_f32");

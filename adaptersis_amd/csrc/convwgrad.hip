@@ -184,7 +184,7 @@ extern "C" int asis_conv3x3_wgrad_halo_nblk(int B, int H, int W, int Cin, int Co
 extern "C" int asis_conv3x3_wgrad_halo(void* stream, int dtype, const void* dy, int64_t ld_dy, const void* x, float* slabs, int nblk,
                                        int B, int H, int W, int Cin, int Cout) {
   ASIS_REQUIRE(dy && x && slabs, "asis_conv3x3_wgrad_halo: null pointer");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_conv3x3_wgrad_halo: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_conv3x3_wgrad_halo");
   ASIS_REQUIRE(B > 0 && H >= TY && W >= TX && Cin % CIB == 0 && Cin > 0 && Cout % COB == 0 && Cout > 0,
                "asis_conv3x3_wgrad_halo: needs Cin %% 128 == 0, Cout %% 64 == 0 and a map of at least 8 x 16 (B=%d H=%d W=%d Cin=%d Cout=%d)",
                B, H, W, Cin, Cout);
@@ -195,10 +195,10 @@ extern "C" int asis_conv3x3_wgrad_halo(void* stream, int dtype, const void* dy, 
   ASIS_REQUIRE((int64_t)B * H * W * (Cin > ld_dy ? Cin : ld_dy) < (1LL << 40), "asis_conv3x3_wgrad_halo: tensors too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(nblk, combos), block(512);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<f16>), grid, block, 0, s, (const f16*)dy, (const f16*)x, slabs, B, H, W, Cin, Cout, (int)ld_dy, Cin / CIB);
-  else
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<bf16>), grid, block, 0, s, (const bf16*)dy, (const bf16*)x, slabs, B, H, W, Cin, Cout, (int)ld_dy, Cin / CIB);
+  if (int rc = asis_dispatch16(dtype, "asis_conv3x3_wgrad_halo", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((conv_wgrad_halo_kernel<T>), grid, block, 0, s, static_cast<const T*>(dy), static_cast<const T*>(x), slabs, B, H, W, Cin, Cout, (int)ld_dy, Cin / CIB);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_conv3x3_wgrad_halo");
   return ASIS_OK;
 }

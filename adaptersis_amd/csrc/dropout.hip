@@ -193,11 +193,6 @@ __global__ __launch_bounds__(256) void softmax_dropout_bwd_kernel(const T* __res
   }
 }
 
-int grid_for(int64_t n) {
-  int64_t g = (n + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 #define DROP_ARGS_OK(name)                                                                             \
@@ -210,7 +205,7 @@ extern "C" int asis_dropout_f32(void* stream, const float* x, const float* res, 
   DROP_ARGS_OK("asis_dropout_f32");
   ASIS_REQUIRE(asis_aligned16(x) && asis_aligned16(out) && (!res || asis_aligned16(res)), "asis_dropout_f32: 16-byte alignment");
   ASIS_REQUIRE(!bias_n || (ncols > 0 && ncols % 4 == 0 && n % ncols == 0 && asis_aligned16(bias_n)), "asis_dropout_f32: bias needs ncols % 4 == 0 dividing n");
-  hipLaunchKernelGGL(dropout_f32_kernel, dim3(grid_for(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(dropout_f32_kernel, dim3(asis_grid(n / 4, 256, 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(res), reinterpret_cast<float4*>(out), n / 4,
                      seed, (uint32_t)site, threshold(p), 1.0f / (1.0f - p), alpha, reinterpret_cast<const float4*>(bias_n), bias_n ? ncols / 4 : 1);
   ASIS_CHECK_LAUNCH("asis_dropout_f32");
@@ -220,17 +215,16 @@ extern "C" int asis_dropout_f32(void* stream, const float* x, const float* res, 
 extern "C" int asis_dropout_t16(void* stream, int dtype, void* x, void* x_lo, int64_t n, uint64_t seed, int site, float p, int rescale) {
   ASIS_REQUIRE(x, "asis_dropout_t16: null pointer");
   DROP_ARGS_OK("asis_dropout_t16");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_dropout_t16: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_dropout_t16");
   ASIS_REQUIRE((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (!x_lo || (reinterpret_cast<uintptr_t>(x_lo) & 7) == 0), "asis_dropout_t16: 8-byte alignment");
   ASIS_REQUIRE(!(x_lo && rescale), "asis_dropout_t16: a hi / lo operand pair is only zeroed (its 1 / (1 - p) belongs to the consuming GEMM)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const float scale = rescale ? 1.0f / (1.0f - p) : 1.0f;
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((dropout_t16_kernel<f16>), dim3(grid_for(n / 4)), dim3(256), 0, s, reinterpret_cast<f16*>(x), reinterpret_cast<f16*>(x_lo),
-                       n / 4, seed, (uint32_t)site, threshold(p), scale);
-  else
-    hipLaunchKernelGGL((dropout_t16_kernel<bf16>), dim3(grid_for(n / 4)), dim3(256), 0, s, reinterpret_cast<bf16*>(x), reinterpret_cast<bf16*>(x_lo),
-                       n / 4, seed, (uint32_t)site, threshold(p), scale);
+  if (int rc = asis_dispatch16(dtype, "asis_dropout_t16", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dropout_t16_kernel<T>), dim3(asis_grid(n / 4, 256, 8192)), dim3(256), 0, s, static_cast<T*>(x), static_cast<T*>(x_lo),
+                           n / 4, seed, (uint32_t)site, threshold(p), scale);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_dropout_t16");
   return ASIS_OK;
 }
@@ -239,7 +233,7 @@ extern "C" int asis_dropout_mask(void* stream, uint8_t* out, int64_t n, uint64_t
   ASIS_REQUIRE(out, "asis_dropout_mask: null pointer");
   DROP_ARGS_OK("asis_dropout_mask");
   ASIS_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "asis_dropout_mask: 4-byte alignment");
-  hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(n / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), out, n / 4, seed,
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3(asis_grid(n / 4, 256, 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), out, n / 4, seed,
                      (uint32_t)site, threshold(p));
   ASIS_CHECK_LAUNCH("asis_dropout_mask");
   return ASIS_OK;
@@ -250,18 +244,17 @@ extern "C" int asis_softmax_dropout_fwd(void* stream, int dtype, const float* S,
   ASIS_REQUIRE(S && p16 && pd16, "asis_softmax_dropout_fwd: null pointer");
   ASIS_REQUIRE(rows > 0 && N > 0 && ld >= N && ld % 4 == 0, "asis_softmax_dropout_fwd: bad shape (ld a multiple of 4, >= N)");
   ASIS_REQUIRE(p >= 0.f && p < 1.f, "asis_softmax_dropout_fwd: dropout probability must be in [0, 1)");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_softmax_dropout_fwd: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_softmax_dropout_fwd");
   ASIS_REQUIRE(asis_aligned16(S) && (reinterpret_cast<uintptr_t>(p16) & 7) == 0 && (reinterpret_cast<uintptr_t>(pd16) & 7) == 0,
                "asis_softmax_dropout_fwd: alignment");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((rows + 3) / 4));
   const float sl = scale * 1.4426950408889634f, ik = 1.0f / (1.0f - p);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((softmax_dropout_fwd_kernel<f16>), grid, dim3(256), 0, s, S, reinterpret_cast<f16*>(p16), reinterpret_cast<f16*>(pd16),
-                       rows, N, ld, sl, seed, (uint32_t)site, threshold(p), ik);
-  else
-    hipLaunchKernelGGL((softmax_dropout_fwd_kernel<bf16>), grid, dim3(256), 0, s, S, reinterpret_cast<bf16*>(p16), reinterpret_cast<bf16*>(pd16),
-                       rows, N, ld, sl, seed, (uint32_t)site, threshold(p), ik);
+  if (int rc = asis_dispatch16(dtype, "asis_softmax_dropout_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((softmax_dropout_fwd_kernel<T>), grid, dim3(256), 0, s, S, static_cast<T*>(p16), static_cast<T*>(pd16),
+                           rows, N, ld, sl, seed, (uint32_t)site, threshold(p), ik);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_softmax_dropout_fwd");
   return ASIS_OK;
 }
@@ -271,18 +264,17 @@ extern "C" int asis_softmax_dropout_bwd(void* stream, int dtype, const void* p16
   ASIS_REQUIRE(p16 && pd16 && dPd && ds16, "asis_softmax_dropout_bwd: null pointer");
   ASIS_REQUIRE(rows > 0 && N > 0 && ld >= N && ld % 4 == 0, "asis_softmax_dropout_bwd: bad shape (ld a multiple of 4, >= N)");
   ASIS_REQUIRE(p >= 0.f && p < 1.f, "asis_softmax_dropout_bwd: dropout probability must be in [0, 1)");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_softmax_dropout_bwd: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_softmax_dropout_bwd");
   ASIS_REQUIRE(asis_aligned16(dPd) && (reinterpret_cast<uintptr_t>(p16) & 7) == 0 && (reinterpret_cast<uintptr_t>(pd16) & 7) == 0 &&
                (reinterpret_cast<uintptr_t>(ds16) & 7) == 0, "asis_softmax_dropout_bwd: alignment");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((rows + 3) / 4));
   const float ik = 1.0f / (1.0f - p);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((softmax_dropout_bwd_kernel<f16>), grid, dim3(256), 0, s, reinterpret_cast<const f16*>(p16), reinterpret_cast<const f16*>(pd16),
-                       dPd, reinterpret_cast<f16*>(ds16), rows, N, ld, scale, seed, (uint32_t)site, threshold(p), ik);
-  else
-    hipLaunchKernelGGL((softmax_dropout_bwd_kernel<bf16>), grid, dim3(256), 0, s, reinterpret_cast<const bf16*>(p16), reinterpret_cast<const bf16*>(pd16),
-                       dPd, reinterpret_cast<bf16*>(ds16), rows, N, ld, scale, seed, (uint32_t)site, threshold(p), ik);
+  if (int rc = asis_dispatch16(dtype, "asis_softmax_dropout_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((softmax_dropout_bwd_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(p16), static_cast<const T*>(pd16),
+                           dPd, static_cast<T*>(ds16), rows, N, ld, scale, seed, (uint32_t)site, threshold(p), ik);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_softmax_dropout_bwd");
   return ASIS_OK;
 }

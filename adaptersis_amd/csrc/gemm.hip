@@ -424,7 +424,7 @@ extern "C" int asis_gemm(void* stream, const asis_gemm_desc* dp) {
   asis_gemm_desc d = *dp;
   ASIS_REQUIRE(d.A && d.B && d.C, "asis_gemm: null operand pointer");
   ASIS_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0, "asis_gemm: M,N,K must be positive (got %d,%d,%d)", d.M, d.N, d.K);
-  ASIS_REQUIRE(d.dtype == ASIS_F16 || d.dtype == ASIS_BF16, "asis_gemm: bad dtype %d", d.dtype);
+  ASIS_DT_OK(d.dtype, "asis_gemm");
   ASIS_REQUIRE(d.K % 8 == 0, "asis_gemm: K=%d must be a multiple of 8", d.K);
   ASIS_REQUIRE(d.ldb % 8 == 0 && d.ldb >= d.K, "asis_gemm: ldb=%ld must be a multiple of 8 and >= K", (long)d.ldb);
   ASIS_REQUIRE(asis_aligned16(d.A) && asis_aligned16(d.B), "asis_gemm: A and B must be 16-byte aligned");
@@ -458,7 +458,8 @@ extern "C" int asis_gemm(void* stream, const asis_gemm_desc* dp) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ASIS_REQUIRE(!d.conv || (d.A_lo == nullptr) == (d.B_lo == nullptr), "asis_gemm: a split convolution needs both A_lo and B_lo");
   ASIS_REQUIRE((!d.A_lo || asis_aligned16(d.A_lo)) && (!d.B_lo || asis_aligned16(d.B_lo)), "asis_gemm: split halves must be 16-byte aligned");
-  const int rc = (d.dtype == ASIS_F16) ? launch<f16>(s, d) : launch<bf16>(s, d);
+  int rc = 0;  // launch(): nonzero = no kernel form takes this descriptor
+  if (int bad = asis_dispatch16(d.dtype, "asis_gemm", [&](auto t) { rc = launch<decltype(t)>(s, d); })) return bad;
   if (rc != 0 && d.act == ASIS_ACT_SILU_MUL)
     ASIS_FAIL(ASIS_EINVAL, "asis_gemm: ASIS_ACT_SILU_MUL needs a dense 16-bit-output launch on the 8-phase form (include/asis_hip.h: K %% 64 == 0, "
                            "M >= 256, N >= 256, N %% 32 == 0, ldc %% 8 == 0, plain or MX split operands, bias only)");

@@ -489,19 +489,14 @@ extern "C" int asis_dice_bwd(void* stream, const float* logits, const int64_t* t
 
 extern "C" int asis_resize_bilinear_fwd(void* stream, const float* x, int B, int h, int w, int H, int W, int C, float* out) {
   ASIS_REQUIRE(x && out && C >= 1 && C <= MAXC, "asis_resize_bilinear_fwd: bad arguments (C <= %d)", MAXC);
-  int64_t g = ((int64_t)B * H * W + 255) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(resize_fwd_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, B, h, w, H,
-                     W, C, out);
+  hipLaunchKernelGGL(resize_fwd_kernel, dim3(asis_grid((int64_t)B * H * W, 256, 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     x, B, h, w, H, W, C, out);
   ASIS_CHECK_LAUNCH("asis_resize_bilinear_fwd");
   return ASIS_OK;
 }
 
 extern "C" int asis_ce_acc_nblk(int64_t total_pixels) {
-  int64_t n = (total_pixels + 256 * 8 - 1) / (256 * 8);
-  if (n > 2048) n = 2048;
-  if (n < 1) n = 1;
-  return (int)n;
+  return asis_grid(total_pixels, 256 * 8, 2048);
 }
 
 extern "C" int asis_ce_acc_counts(void* stream, const float* logits, const int64_t* target, const float* weight, int B,
@@ -523,29 +518,25 @@ extern "C" int asis_ce_acc(void* stream, const float* logits, const int64_t* tar
 }
 
 extern "C" int asis_resize_bwd_nblk(int64_t total_pixels) {
-  int64_t n = (total_pixels + 255) / 256;
-  if (n > 4096) n = 4096;
-  if (n < 1) n = 1;
-  return (int)n;
+  return asis_grid(total_pixels, 256, 4096);
 }
 
 extern "C" int asis_resize_bilinear_bwd(void* stream, int dtype, const float* dz, int B, int H, int W, int h, int w, int C,
                                         int CP, void* out, void* out_lo, float* partial) {
   ASIS_REQUIRE(dz && out && partial, "asis_resize_bilinear_bwd: null pointer");
   ASIS_REQUIRE(C >= 1 && C <= MAXC && CP >= C && CP <= MAXC, "asis_resize_bilinear_bwd: bad C=%d CP=%d", C, CP);
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16 || dtype == ASIS_F32, "asis_resize_bilinear_bwd: bad dtype %d", dtype);
+  if (dtype != ASIS_F32) ASIS_DT_OK(dtype, "asis_resize_bilinear_bwd");
   ASIS_REQUIRE(dtype == ASIS_F32 || CP % 8 == 0, "asis_resize_bilinear_bwd: 16-bit output needs CP %% 8 == 0");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int nblk = asis_resize_bwd_nblk((int64_t)B * h * w);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((resize_bwd_kernel<f16>), dim3(nblk), dim3(256), 0, s, dz, B, H, W, h, w, C, CP,
-                       reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), partial);
-  else if (dtype == ASIS_BF16)
-    hipLaunchKernelGGL((resize_bwd_kernel<bf16>), dim3(nblk), dim3(256), 0, s, dz, B, H, W, h, w, C, CP,
-                       reinterpret_cast<bf16*>(out), reinterpret_cast<bf16*>(out_lo), partial);
-  else
+  if (dtype == ASIS_F32)  // the float branch stays explicit (no second plane): the dispatcher knows the two 16-bit types only
     hipLaunchKernelGGL((resize_bwd_kernel<float>), dim3(nblk), dim3(256), 0, s, dz, B, H, W, h, w, C, CP,
-                       reinterpret_cast<float*>(out), (float*)nullptr, partial);
+                       static_cast<float*>(out), static_cast<float*>(nullptr), partial);
+  else if (int rc = asis_dispatch16(dtype, "asis_resize_bilinear_bwd", [&](auto t) {
+             using T = decltype(t);
+             hipLaunchKernelGGL((resize_bwd_kernel<T>), dim3(nblk), dim3(256), 0, s, dz, B, H, W, h, w, C, CP,
+                                static_cast<T*>(out), static_cast<T*>(out_lo), partial);
+           })) return rc;
   ASIS_CHECK_LAUNCH("asis_resize_bilinear_bwd");
   return ASIS_OK;
 }
@@ -553,9 +544,7 @@ extern "C" int asis_resize_bilinear_bwd(void* stream, int dtype, const float* dz
 extern "C" int asis_reduce_rows(void* stream, const float* partial, int n, int K, float scale, float* out) {
   ASIS_REQUIRE(partial && out && n > 0 && K > 0, "asis_reduce_rows: bad arguments");
   if (n <= 64 || K > 65535) {
-    int64_t g = ((int64_t)K + 255) / 256;
-    if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(reduce_rows_wide_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(reduce_rows_wide_kernel, dim3(asis_grid(K, 256, 8192)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        partial, n, (int64_t)K, scale, out);
   } else {
     hipLaunchKernelGGL(reduce_rows_kernel, dim3((K + 7) / 8), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), partial, n,

@@ -164,13 +164,6 @@ __global__ __launch_bounds__(256) void dwconv_gelu_kernel(const float* __restric
   }
 }
 
-inline int grid_for(int64_t total, int block = 256, int cap = 256 * 16) {
-  int64_t g = (total + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
 
 extern "C" int asis_msda_fwd_split(void* stream, int dtype, const void* value, const float* offaw, int64_t ld_offaw,
@@ -183,19 +176,20 @@ extern "C" int asis_msda_fwd_split(void* stream, int dtype, const void* value, c
   ASIS_REQUIRE(L * P <= MAX_LP, "asis_msda_fwd: n_levels*n_points=%d exceeds %d", L * P, MAX_LP);
   ASIS_REQUIRE(ld_offaw >= (int64_t)M * L * P * 3, "asis_msda_fwd: ld_offaw too small");
   ASIS_REQUIRE(asis_aligned16(value) && asis_aligned16(out), "asis_msda_fwd: value/out must be 16-byte aligned");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_msda_fwd: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_msda_fwd");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // ASIS_MSDA_NC (default 2): 16-byte chunks per thread when the head dim allows it
   static const int nc_env = [] { const char* e = getenv("ASIS_MSDA_NC"); return e ? atoi(e) : 2; }();
   const int nc = (nc_env >= 2 && Dh % 16 == 0) ? 2 : 1;
   const int64_t total = (int64_t)B * Lq * (M * Dh / (8 * nc));
-#define ASIS_MSDA_FWD(TT, NCC)                                                                                              \
-  hipLaunchKernelGGL((msda_fwd_kernel<TT, NCC>), dim3(grid_for(total, 256, 1 << 20)), dim3(256), 0, s,                      \
-                     reinterpret_cast<const TT*>(value), offaw, ld_offaw, ref, shapes, starts, reinterpret_cast<TT*>(out),      \
-                     reinterpret_cast<TT*>(out_lo), B, \
-                     Lq, Lin, M, L, P, Dh)
-  if (dtype == ASIS_F16) { if (nc == 2) ASIS_MSDA_FWD(f16, 2); else ASIS_MSDA_FWD(f16, 1); }
-  else { if (nc == 2) ASIS_MSDA_FWD(bf16, 2); else ASIS_MSDA_FWD(bf16, 1); }
+#define ASIS_MSDA_FWD(NCC)                                                                                        \
+  hipLaunchKernelGGL((msda_fwd_kernel<T, NCC>), dim3(asis_grid(total, 256, 1 << 20)), dim3(256), 0, s,             \
+                     static_cast<const T*>(value), offaw, ld_offaw, ref, shapes, starts, static_cast<T*>(out),     \
+                     static_cast<T*>(out_lo), B, Lq, Lin, M, L, P, Dh)
+  if (int rc = asis_dispatch16(dtype, "asis_msda_fwd", [&](auto t) {
+        using T = decltype(t);
+        if (nc == 2) ASIS_MSDA_FWD(2); else ASIS_MSDA_FWD(1);
+      })) return rc;
 #undef ASIS_MSDA_FWD
   ASIS_CHECK_LAUNCH("asis_msda_fwd");
   return ASIS_OK;
@@ -214,15 +208,14 @@ extern "C" int asis_dwconv_gelu(void* stream, int dtype, const float* x, const f
   ASIS_REQUIRE(C % 4 == 0 && B > 0 && Ntok > 0 && L > 0, "asis_dwconv_gelu: bad shape");
   ASIS_REQUIRE(asis_aligned16(x) && asis_aligned16(w9) && asis_aligned16(bias) && (((uintptr_t)out) & 7) == 0,
                "asis_dwconv_gelu: pointers must be 16-byte aligned");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_dwconv_gelu: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_dwconv_gelu");
   const int64_t total = (int64_t)B * Ntok * (C / 4);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((dwconv_gelu_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, x, w9, bias, shapes, starts,
-                       L, reinterpret_cast<f16*>(out), B, Ntok, C);
-  else
-    hipLaunchKernelGGL((dwconv_gelu_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, x, w9, bias, shapes, starts,
-                       L, reinterpret_cast<bf16*>(out), B, Ntok, C);
+  if (int rc = asis_dispatch16(dtype, "asis_dwconv_gelu", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dwconv_gelu_kernel<T>), dim3(asis_grid(total, 256, 256 * 16)), dim3(256), 0, s, x, w9, bias, shapes, starts,
+                           L, static_cast<T*>(out), B, Ntok, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_dwconv_gelu");
   return ASIS_OK;
 }

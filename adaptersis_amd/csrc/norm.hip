@@ -212,13 +212,6 @@ __global__ __launch_bounds__(256) void im2col_patch_kernel(const float* __restri
   }
 }
 
-inline int grid_for(int64_t total, int block = 256, int cap = 256 * 16) {
-  int64_t g = (total + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
 
 // ---- LayerNorm-fold chain helpers (include/asis_hip.h: asis_gemm_desc.rowstats / ln_mr) ---------------------------------------
@@ -307,14 +300,14 @@ extern "C" int asis_split_stats(void* stream, int dtype, const float* x, int64_t
   ASIS_REQUIRE(D > 0 && D % 4 == 0 && D <= 256 * LN_MAXC, "asis_split_stats: D=%d must be a multiple of 4 and <= %d", D, 256 * LN_MAXC);
   ASIS_REQUIRE(ldx % 4 == 0 && ldx >= D && ld16 % 4 == 0 && ld16 >= D, "asis_split_stats: row strides must be multiples of 4 and >= D");
   ASIS_REQUIRE(asis_aligned16(x) && (((uintptr_t)hi) & 7) == 0 && (((uintptr_t)lo) & 7) == 0, "asis_split_stats: misaligned pointers");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_split_stats: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_split_stats");
   if (rows <= 0) return ASIS_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)asis_cdiv(rows, 4)), block(256);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((split_stats_kernel<f16>), grid, block, 0, s, x, ldx, reinterpret_cast<f16*>(hi), reinterpret_cast<f16*>(lo), ld16, mr, rows, D, eps);
-  else
-    hipLaunchKernelGGL((split_stats_kernel<bf16>), grid, block, 0, s, x, ldx, reinterpret_cast<bf16*>(hi), reinterpret_cast<bf16*>(lo), ld16, mr, rows, D, eps);
+  if (int rc = asis_dispatch16(dtype, "asis_split_stats", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((split_stats_kernel<T>), grid, block, 0, s, x, ldx, static_cast<T*>(hi), static_cast<T*>(lo), ld16, mr, rows, D, eps);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_split_stats");
   return ASIS_OK;
 }
@@ -327,7 +320,7 @@ extern "C" int asis_layernorm(void* stream, int dtype, const float* x, int64_t l
   ASIS_REQUIRE(ldx % 4 == 0 && ldx >= D && ldy % 4 == 0 && ldy >= D, "asis_layernorm: row strides must be multiples of 4 and >= D");
   ASIS_REQUIRE(asis_aligned16(x) && asis_aligned16(w) && asis_aligned16(b) && (((uintptr_t)y) & 7) == 0,
                "asis_layernorm: pointers must be 16-byte aligned");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_layernorm: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_layernorm");
   if (rows <= 0) return ASIS_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)asis_cdiv(rows, 4)), block(256);
@@ -345,25 +338,21 @@ extern "C" int asis_layernorm(void* stream, int dtype, const float* x, int64_t l
       hipLaunchKernelGGL((layernorm_fixed_kernel<T, false, NCH, 2>), dim3((unsigned)asis_cdiv(rows, 8)), block, 0, s, \
                          x, ldx, w, b, eps, y, ldy, rows);                                                            \
   } while (0)
-    if (dtype == ASIS_F16) {
-      if (D == 768) ASIS_LN_FIXED(f16, 3);
-      else if (D == 1024) ASIS_LN_FIXED(f16, 4);
-      else ASIS_LN_FIXED(f16, 6);
-    } else {
-      if (D == 768) ASIS_LN_FIXED(bf16, 3);
-      else if (D == 1024) ASIS_LN_FIXED(bf16, 4);
-      else ASIS_LN_FIXED(bf16, 6);
-    }
+    if (int rc = asis_dispatch16(dtype, "asis_layernorm", [&](auto t) {
+          using T = decltype(t);
+          if (D == 768) ASIS_LN_FIXED(T, 3);
+          else if (D == 1024) ASIS_LN_FIXED(T, 4);
+          else ASIS_LN_FIXED(T, 6);
+        })) return rc;
 #undef ASIS_LN_FIXED
     ASIS_CHECK_LAUNCH("asis_layernorm");
     return ASIS_OK;
   }
-  if (out_f32)
+  if (out_f32)  // float output, whichever of the two 16-bit dtypes was passed: the kernel's T is unused, <f16, true> is its one instance
     hipLaunchKernelGGL((layernorm_kernel<f16, true>), grid, block, 0, s, x, ldx, w, b, eps, y, ldy, rows, D);
-  else if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((layernorm_kernel<f16, false>), grid, block, 0, s, x, ldx, w, b, eps, y, ldy, rows, D);
-  else
-    hipLaunchKernelGGL((layernorm_kernel<bf16, false>), grid, block, 0, s, x, ldx, w, b, eps, y, ldy, rows, D);
+  else if (int rc = asis_dispatch16(dtype, "asis_layernorm", [&](auto t) {
+             hipLaunchKernelGGL((layernorm_kernel<decltype(t), false>), grid, block, 0, s, x, ldx, w, b, eps, y, ldy, rows, D);
+           })) return rc;
   ASIS_CHECK_LAUNCH("asis_layernorm");
   return ASIS_OK;
 }
@@ -429,14 +418,14 @@ extern "C" int asis_layernorm_mx(void* stream, int dtype, const float* x, int64_
   ASIS_REQUIRE(D > 0 && D % 4 == 0 && D <= 256 * LN_MAXC && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D && asis_aligned16(x) &&
                    asis_aligned16(w) && asis_aligned16(b) && (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(y_mx) & 7) == 0,
                "asis_layernorm_mx: D=%d must be a multiple of 4 and <= %d, leading dimensions multiples of 4, pointers aligned", D, 256 * LN_MAXC);
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_layernorm_mx: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_layernorm_mx");
   if (rows == 0) return ASIS_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)asis_cdiv(rows, 4)), block(256);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((layernorm_mx_kernel<f16>), grid, block, 0, s, x, ldx, w, b, eps, reinterpret_cast<f16*>(y), reinterpret_cast<f16*>(y_mx), ldy, amax, rows, D);
-  else
-    hipLaunchKernelGGL((layernorm_mx_kernel<bf16>), grid, block, 0, s, x, ldx, w, b, eps, reinterpret_cast<bf16*>(y), reinterpret_cast<bf16*>(y_mx), ldy, amax, rows, D);
+  if (int rc = asis_dispatch16(dtype, "asis_layernorm_mx", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((layernorm_mx_kernel<T>), grid, block, 0, s, x, ldx, w, b, eps, static_cast<T*>(y), static_cast<T*>(y_mx), ldy, amax, rows, D);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_layernorm_mx");
   return ASIS_OK;
 }
@@ -448,7 +437,7 @@ extern "C" int asis_add_cls_pos(void* stream, const float* x, const float* cls, 
   ASIS_REQUIRE(asis_aligned16(x) && asis_aligned16(cls) && asis_aligned16(pos) && asis_aligned16(out),
                "asis_add_cls_pos: pointers must be 16-byte aligned");
   const int64_t total = (int64_t)B * (N + 1) * (D / 4);
-  hipLaunchKernelGGL(add_cls_pos_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(add_cls_pos_kernel, dim3(asis_grid(total, 256, 256 * 16)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(cls),
                      reinterpret_cast<const float4*>(pos), reinterpret_cast<float4*>(out), B, N, D / 4);
   ASIS_CHECK_LAUNCH("asis_add_cls_pos");
@@ -460,16 +449,15 @@ extern "C" int asis_cast_pad(void* stream, int dtype, const float* src, int64_t 
   ASIS_REQUIRE(src && dst, "asis_cast_pad: null pointer");
   ASIS_REQUIRE(ld_dst % 8 == 0 && ld_dst >= cols && ld_src >= cols, "asis_cast_pad: bad leading dims");
   ASIS_REQUIRE(asis_aligned16(dst), "asis_cast_pad: dst must be 16-byte aligned");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_cast_pad: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_cast_pad");
   if (rows <= 0) return ASIS_OK;
   const int64_t total = rows * (ld_dst / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((cast_pad_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, src, ld_src,
-                       reinterpret_cast<f16*>(dst), ld_dst, rows, cols, scale, part);
-  else
-    hipLaunchKernelGGL((cast_pad_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, src, ld_src,
-                       reinterpret_cast<bf16*>(dst), ld_dst, rows, cols, scale, part);
+  if (int rc = asis_dispatch16(dtype, "asis_cast_pad", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(asis_grid(total, 256, 256 * 16)), dim3(256), 0, s, src, ld_src,
+                           static_cast<T*>(dst), ld_dst, rows, cols, scale, part);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_cast_pad");
   return ASIS_OK;
 }
@@ -489,15 +477,14 @@ extern "C" int asis_im2col_patch_split(void* stream, int dtype, const float* img
                "Input image size %dx%d is not a multiple of patch size %d", Himg, Wimg, P);
   ASIS_REQUIRE(ldk % 8 == 0 && ldk >= 3 * P * P, "asis_im2col_patch: ldk=%ld must be a multiple of 8 and >= 3*P*P", (long)ldk);
   ASIS_REQUIRE(asis_aligned16(out), "asis_im2col_patch: out must be 16-byte aligned");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_im2col_patch: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_im2col_patch");
   const int64_t total = (int64_t)B * (Himg / P) * (Wimg / P) * (ldk / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((im2col_patch_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, img, B, Himg, Wimg, P,
-                       reinterpret_cast<f16*>(out), ldk, reinterpret_cast<f16*>(out_lo));
-  else
-    hipLaunchKernelGGL((im2col_patch_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, img, B, Himg, Wimg, P,
-                       reinterpret_cast<bf16*>(out), ldk, reinterpret_cast<bf16*>(out_lo));
+  if (int rc = asis_dispatch16(dtype, "asis_im2col_patch", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((im2col_patch_kernel<T>), dim3(asis_grid(total, 256, 256 * 16)), dim3(256), 0, s, img, B, Himg, Wimg, P,
+                           static_cast<T*>(out), ldk, static_cast<T*>(out_lo));
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_im2col_patch");
   return ASIS_OK;
 }

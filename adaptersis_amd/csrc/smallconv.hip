@@ -613,13 +613,6 @@ __global__ __launch_bounds__(256, 2) void smallcout_wgrad_mfma_kernel(const T* _
   }
 }
 
-inline int grid_for(int64_t total, int cap = 256 * 32) {
-  int64_t g = (total + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 template <typename T>
 int launch_fwd(hipStream_t s, const void* xh, const void* xl, const float* w, const float* bias, float* out, int B, int H,
                int W, int Cin, int Cout) {
@@ -635,7 +628,7 @@ int launch_fwd(hipStream_t s, const void* xh, const void* xl, const float* w, co
     return 0;
   }
 #define FWD(CO)                                                                                                    \
-  hipLaunchKernelGGL((smallcout_fwd_kernel<T, CO>), dim3(grid_for(total)), dim3(256), 9 * Cin * CO * sizeof(float), s, \
+  hipLaunchKernelGGL((smallcout_fwd_kernel<T, CO>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), 9 * Cin * CO * sizeof(float), s, \
                      a, b, w, bias, out, B, H, W, Cin, Cout)
   if (Cout <= 2) FWD(2);
   else if (Cout <= 4) FWD(4);
@@ -653,10 +646,11 @@ extern "C" int asis_conv3x3_smallcout_fwd(void* stream, int dtype, const void* x
   ASIS_REQUIRE(Cout >= 1 && Cout <= MAXCO, "asis_conv3x3_smallcout_fwd: Cout=%d must be in 1..%d", Cout, MAXCO);
   ASIS_REQUIRE(Cin >= 8 && Cin <= 64 && (Cin & (Cin - 1)) == 0, "asis_conv3x3_smallcout_fwd: Cin=%d must be 8, 16, 32 or 64", Cin);
   ASIS_REQUIRE(asis_aligned16(x_hi) && (!x_lo || asis_aligned16(x_lo)), "asis_conv3x3_smallcout_fwd: alignment");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_conv3x3_smallcout_fwd: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_conv3x3_smallcout_fwd");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16) launch_fwd<f16>(s, x_hi, x_lo, w, bias, out, B, H, W, Cin, Cout);
-  else launch_fwd<bf16>(s, x_hi, x_lo, w, bias, out, B, H, W, Cin, Cout);
+  if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_fwd", [&](auto t) {
+        launch_fwd<decltype(t)>(s, x_hi, x_lo, w, bias, out, B, H, W, Cin, Cout);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_fwd");
   return ASIS_OK;
 }
@@ -667,18 +661,17 @@ extern "C" int asis_conv3x3_smallcout_fwd_up(void* stream, int dtype, const floa
   ASIS_REQUIRE(Cin == 64 && Cout >= 1 && Cout <= 16 && B > 0 && H >= 4 && W >= 8,
                "asis_conv3x3_smallcout_fwd_up: Cin=%d must be 64, Cout=%d in 1..16, the low-resolution map at least 4 x 8", Cin, Cout);
   ASIS_REQUIRE(asis_aligned16(raw) && asis_aligned16(scale) && asis_aligned16(shift), "asis_conv3x3_smallcout_fwd_up: alignment");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_conv3x3_smallcout_fwd_up: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_conv3x3_smallcout_fwd_up");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int OH = 2 * H, OW = 2 * W;
   const int ntiles = B * ((OH + 7) / 8) * ((OW + 15) / 16);
   const UpSrc up{raw, scale, shift, H, W};
   const dim3 grid(ntiles < 512 ? ntiles : 512);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((smallcout_fwd_mfma_kernel<f16, true>), grid, dim3(256), 0, s, (const f16*)nullptr, (const f16*)nullptr, w, bias, out, B,
-                       OH, OW, Cout, up);
-  else
-    hipLaunchKernelGGL((smallcout_fwd_mfma_kernel<bf16, true>), grid, dim3(256), 0, s, (const bf16*)nullptr, (const bf16*)nullptr, w, bias, out,
-                       B, OH, OW, Cout, up);
+  if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_fwd_up", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((smallcout_fwd_mfma_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T*>(nullptr), static_cast<const T*>(nullptr), w, bias, out, B,
+                           OH, OW, Cout, up);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_fwd_up");
   return ASIS_OK;
 }
@@ -690,15 +683,14 @@ extern "C" int asis_conv3x3_smallcout_wgrad_up(void* stream, int dtype, const vo
                "asis_conv3x3_smallcout_wgrad_up: Cin=%d must be 64, CoP=%d 8, Cout=%d <= 8, the low-resolution map at least 4 x 8", Cin, CoP, Cout);
   ASIS_REQUIRE(nblk >= 1 && nblk <= 65535, "asis_conv3x3_smallcout_wgrad_up: bad slab count %d", nblk);
   ASIS_REQUIRE(asis_aligned16(dy) && asis_aligned16(raw) && asis_aligned16(scale) && asis_aligned16(shift), "asis_conv3x3_smallcout_wgrad_up: alignment");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_conv3x3_smallcout_wgrad_up: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_conv3x3_smallcout_wgrad_up");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const UpSrc up{raw, scale, shift, H, W};
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((smallcout_wgrad_mfma_kernel<f16, true>), dim3(nblk), dim3(256), 0, s, reinterpret_cast<const f16*>(dy), (const f16*)nullptr,
-                       slabs, B, 2 * H, 2 * W, Cout, up);
-  else
-    hipLaunchKernelGGL((smallcout_wgrad_mfma_kernel<bf16, true>), dim3(nblk), dim3(256), 0, s, reinterpret_cast<const bf16*>(dy),
-                       (const bf16*)nullptr, slabs, B, 2 * H, 2 * W, Cout, up);
+  if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_wgrad_up", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((smallcout_wgrad_mfma_kernel<T, true>), dim3(nblk), dim3(256), 0, s, static_cast<const T*>(dy), static_cast<const T*>(nullptr),
+                           slabs, B, 2 * H, 2 * W, Cout, up);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_wgrad_up");
   return ASIS_OK;
 }
@@ -710,7 +702,7 @@ extern "C" int asis_conv3x3_smallcout_dgrad(void* stream, int dtype, const void*
   ASIS_REQUIRE(Cin % 8 == 0 && Cin > 0 && 9 * 8 * Cin * 4 <= 64 * 1024, "asis_conv3x3_smallcout_dgrad: Cin=%d must be a multiple of 8, <= 224", Cin);
   ASIS_REQUIRE(asis_aligned16(dy_hi) && (!dy_lo || asis_aligned16(dy_lo)) && asis_aligned16(dx),
                "asis_conv3x3_smallcout_dgrad: alignment");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_conv3x3_smallcout_dgrad: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_conv3x3_smallcout_dgrad");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = (int64_t)B * H * W * (Cin / 8);
   // ASIS_SMALLCOUT_TILED (default 1): the MFMA form for Cin = 64 with the classes in one 8-channel record
@@ -718,25 +710,23 @@ extern "C" int asis_conv3x3_smallcout_dgrad(void* stream, int dtype, const void*
   if (tiled && Cin == 64 && CoP == 8 && H >= 8 && W >= 16) {
     const int ntiles = B * ((H + 7) / 8) * ((W + 15) / 16);
     const dim3 grid(ntiles < 512 ? ntiles : 512);
-    if (dtype == ASIS_F16)
-      hipLaunchKernelGGL((smallcout_dgrad_mfma_kernel<f16>), grid, dim3(256), 0, s, reinterpret_cast<const f16*>(dy_hi),
-                         reinterpret_cast<const f16*>(dy_lo), w, dx, B, H, W, Cout);
-    else
-      hipLaunchKernelGGL((smallcout_dgrad_mfma_kernel<bf16>), grid, dim3(256), 0, s, reinterpret_cast<const bf16*>(dy_hi),
-                         reinterpret_cast<const bf16*>(dy_lo), w, dx, B, H, W, Cout);
+    if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_dgrad", [&](auto t) {
+          using T = decltype(t);
+          hipLaunchKernelGGL((smallcout_dgrad_mfma_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(dy_hi),
+                             static_cast<const T*>(dy_lo), w, dx, B, H, W, Cout);
+        })) return rc;
     ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_dgrad");
     return ASIS_OK;
   }
   const int CO = Cout <= 2 ? 2 : (Cout <= 4 ? 4 : 8);
   const size_t shm = (size_t)9 * CO * Cin * sizeof(float);
-#define DG(T, C)                                                                                                  \
-  hipLaunchKernelGGL((smallcout_dgrad_kernel<T, C>), dim3(grid_for(total)), dim3(256), shm, s,                    \
-                     reinterpret_cast<const T*>(dy_hi), reinterpret_cast<const T*>(dy_lo), CoP, w, dx, B, H, W, Cin, Cout)
-  if (dtype == ASIS_F16) {
-    if (CO == 2) DG(f16, 2); else if (CO == 4) DG(f16, 4); else DG(f16, 8);
-  } else {
-    if (CO == 2) DG(bf16, 2); else if (CO == 4) DG(bf16, 4); else DG(bf16, 8);
-  }
+#define DG(C)                                                                                           \
+  hipLaunchKernelGGL((smallcout_dgrad_kernel<T, C>), dim3(asis_grid(total, 256, 256 * 32)), dim3(256), shm, s, \
+                     static_cast<const T*>(dy_hi), static_cast<const T*>(dy_lo), CoP, w, dx, B, H, W, Cin, Cout)
+  if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_dgrad", [&](auto t) {
+        using T = decltype(t);
+        if (CO == 2) DG(2); else if (CO == 4) DG(4); else DG(8);
+      })) return rc;
 #undef DG
   ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_dgrad");
   return ASIS_OK;
@@ -749,27 +739,25 @@ extern "C" int asis_conv3x3_smallcout_wgrad(void* stream, int dtype, const void*
   ASIS_REQUIRE(Cin >= 8 && Cin <= 64 && (Cin & (Cin - 1)) == 0, "asis_conv3x3_smallcout_wgrad: Cin=%d must be 8, 16, 32 or 64", Cin);
   ASIS_REQUIRE(nblk >= 1 && nblk <= 65535, "asis_conv3x3_smallcout_wgrad: bad slab count %d", nblk);
   ASIS_REQUIRE(asis_aligned16(dy) && asis_aligned16(x), "asis_conv3x3_smallcout_wgrad: alignment");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, "asis_conv3x3_smallcout_wgrad: bad dtype %d", dtype);
+  ASIS_DT_OK(dtype, "asis_conv3x3_smallcout_wgrad");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(nblk, (Cout + 1) / 2), block(256);
   // ASIS_SMALLCOUT_TILED (default 1): the MFMA form for Cin = 64 with the classes in one 8-channel record
   static const int tiled = [] { const char* e = getenv("ASIS_SMALLCOUT_TILED"); return e ? atoi(e) : 1; }();
   if (tiled && Cin == 64 && CoP == 8 && Cout <= 8 && H >= 8 && W >= 16) {
-    if (dtype == ASIS_F16)
-      hipLaunchKernelGGL((smallcout_wgrad_mfma_kernel<f16>), dim3(nblk), block, 0, s, reinterpret_cast<const f16*>(dy),
-                         reinterpret_cast<const f16*>(x), slabs, B, H, W, Cout);
-    else
-      hipLaunchKernelGGL((smallcout_wgrad_mfma_kernel<bf16>), dim3(nblk), block, 0, s, reinterpret_cast<const bf16*>(dy),
-                         reinterpret_cast<const bf16*>(x), slabs, B, H, W, Cout);
+    if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_wgrad", [&](auto t) {
+          using T = decltype(t);
+          hipLaunchKernelGGL((smallcout_wgrad_mfma_kernel<T>), dim3(nblk), block, 0, s, static_cast<const T*>(dy),
+                             static_cast<const T*>(x), slabs, B, H, W, Cout);
+        })) return rc;
     ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_wgrad");
     return ASIS_OK;
   }
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((smallcout_wgrad_kernel<f16>), grid, block, 0, s, reinterpret_cast<const f16*>(dy), CoP,
-                       reinterpret_cast<const f16*>(x), slabs, B, H, W, Cin, Cout);
-  else
-    hipLaunchKernelGGL((smallcout_wgrad_kernel<bf16>), grid, block, 0, s, reinterpret_cast<const bf16*>(dy), CoP,
-                       reinterpret_cast<const bf16*>(x), slabs, B, H, W, Cin, Cout);
+  if (int rc = asis_dispatch16(dtype, "asis_conv3x3_smallcout_wgrad", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((smallcout_wgrad_kernel<T>), grid, block, 0, s, static_cast<const T*>(dy), CoP,
+                           static_cast<const T*>(x), slabs, B, H, W, Cin, Cout);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_conv3x3_smallcout_wgrad");
   return ASIS_OK;
 }

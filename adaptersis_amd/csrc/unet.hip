@@ -13,13 +13,6 @@
 
 namespace {
 
-inline int grid_for(int64_t total) {
-  int64_t g = (total + 255) / 256;
-  if (g > 65535 * 4) g = 65535 * 4;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // ---- MaxPool2d(2) (floor mode: an odd last row / column is dropped, unet_parts.py:31) ------------------------------
 // value of a pixel = hi + lo (fp32); the first maximum in scan order (0,0),(0,1),(1,0),(1,1) wins like ATen's kernel.
 // idx[b, oh, ow, c] in 0..3 feeds the backward.
@@ -335,25 +328,21 @@ __global__ __launch_bounds__(256) void nearest_sum_kernel(const float* __restric
 
 }  // namespace
 
-#define DT_OK(dtype, name) ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, name ": bad dtype %d", dtype)
-
 extern "C" int asis_maxpool2_fwd(void* stream, int dtype, const void* x, const void* x_lo, void* out, void* out_lo,
                                  uint8_t* idx, int B, int H, int W, int C) {
   ASIS_REQUIRE(x && out, "asis_maxpool2_fwd: null pointer");
   ASIS_REQUIRE((x_lo == nullptr) == (out_lo == nullptr), "asis_maxpool2_fwd: x_lo and out_lo go together");
   ASIS_REQUIRE(C > 0 && C % 8 == 0 && H >= 2 && W >= 2, "asis_maxpool2_fwd: bad C=%d (multiple of 8) / H=%d W=%d", C, H, W);
-  DT_OK(dtype, "asis_maxpool2_fwd");
+  ASIS_DT_OK(dtype, "asis_maxpool2_fwd");
   const int OH = H / 2, OW = W / 2;
   const int64_t total = (int64_t)B * OH * OW * (C / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((maxpool2_fwd_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, reinterpret_cast<const f16*>(x),
-                       reinterpret_cast<const f16*>(x_lo), reinterpret_cast<f16*>(out), reinterpret_cast<f16*>(out_lo), idx,
-                       B, H, W, OH, OW, C);
-  else
-    hipLaunchKernelGGL((maxpool2_fwd_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s,
-                       reinterpret_cast<const bf16*>(x), reinterpret_cast<const bf16*>(x_lo), reinterpret_cast<bf16*>(out),
-                       reinterpret_cast<bf16*>(out_lo), idx, B, H, W, OH, OW, C);
+  if (int rc = asis_dispatch16(dtype, "asis_maxpool2_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((maxpool2_fwd_kernel<T>), dim3(asis_grid(total, 256, 65535 * 4)), dim3(256), 0, s, static_cast<const T*>(x),
+                           static_cast<const T*>(x_lo), static_cast<T*>(out), static_cast<T*>(out_lo), idx,
+                           B, H, W, OH, OW, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_maxpool2_fwd");
   return ASIS_OK;
 }
@@ -363,7 +352,7 @@ extern "C" int asis_maxpool2_bwd(void* stream, const float* dy, const uint8_t* i
   ASIS_REQUIRE(C > 0 && C % 8 == 0 && H >= 2 && W >= 2, "asis_maxpool2_bwd: bad C=%d / H=%d W=%d", C, H, W);
   const int OH = H / 2, OW = W / 2;
   const int64_t total = (int64_t)B * OH * OW * (C / 4);
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, idx,
+  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(asis_grid(total, 256, 65535 * 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, idx,
                      dx, B, H, W, OH, OW, C);
   ASIS_CHECK_LAUNCH("asis_maxpool2_bwd");
   return ASIS_OK;
@@ -383,18 +372,16 @@ static int convt_geom_ok(const char* name, int B, int H, int W, int Cout, int H2
 extern "C" int asis_convt2x2_scatter(void* stream, int dtype, const float* G, void* dst, void* dst_lo, int B, int H, int W,
                                      int Cout, int H2, int W2, int Ctot, int coff, int padT, int padL) {
   ASIS_REQUIRE(G && dst, "asis_convt2x2_scatter: null pointer");
-  DT_OK(dtype, "asis_convt2x2_scatter");
+  ASIS_DT_OK(dtype, "asis_convt2x2_scatter");
   int rc = convt_geom_ok("asis_convt2x2_scatter", B, H, W, Cout, H2, W2, Ctot, coff, padT, padL);
   if (rc != ASIS_OK) return rc;
   const int64_t total = (int64_t)B * H * W * (Cout / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((convt2x2_scatter_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, G, reinterpret_cast<f16*>(dst),
-                       reinterpret_cast<f16*>(dst_lo), B, H, W, Cout, H2, W2, Ctot, coff, padT, padL);
-  else
-    hipLaunchKernelGGL((convt2x2_scatter_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, G,
-                       reinterpret_cast<bf16*>(dst), reinterpret_cast<bf16*>(dst_lo), B, H, W, Cout, H2, W2, Ctot, coff, padT,
-                       padL);
+  if (int rc = asis_dispatch16(dtype, "asis_convt2x2_scatter", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((convt2x2_scatter_kernel<T>), dim3(asis_grid(total, 256, 65535 * 4)), dim3(256), 0, s, G, static_cast<T*>(dst),
+                           static_cast<T*>(dst_lo), B, H, W, Cout, H2, W2, Ctot, coff, padT, padL);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_convt2x2_scatter");
   return ASIS_OK;
 }
@@ -402,18 +389,16 @@ extern "C" int asis_convt2x2_scatter(void* stream, int dtype, const float* G, vo
 extern "C" int asis_convt2x2_gather(void* stream, int dtype, const float* dcat, void* dG, void* dG_lo, int B, int H, int W,
                                     int Cout, int H2, int W2, int Ctot, int coff, int padT, int padL) {
   ASIS_REQUIRE(dcat && dG, "asis_convt2x2_gather: null pointer");
-  DT_OK(dtype, "asis_convt2x2_gather");
+  ASIS_DT_OK(dtype, "asis_convt2x2_gather");
   int rc = convt_geom_ok("asis_convt2x2_gather", B, H, W, Cout, H2, W2, Ctot, coff, padT, padL);
   if (rc != ASIS_OK) return rc;
   const int64_t total = (int64_t)B * H * W * (Cout / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((convt2x2_gather_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, dcat, reinterpret_cast<f16*>(dG),
-                       reinterpret_cast<f16*>(dG_lo), B, H, W, Cout, H2, W2, Ctot, coff, padT, padL);
-  else
-    hipLaunchKernelGGL((convt2x2_gather_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, dcat,
-                       reinterpret_cast<bf16*>(dG), reinterpret_cast<bf16*>(dG_lo), B, H, W, Cout, H2, W2, Ctot, coff, padT,
-                       padL);
+  if (int rc = asis_dispatch16(dtype, "asis_convt2x2_gather", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((convt2x2_gather_kernel<T>), dim3(asis_grid(total, 256, 65535 * 4)), dim3(256), 0, s, dcat, static_cast<T*>(dG),
+                           static_cast<T*>(dG_lo), B, H, W, Cout, H2, W2, Ctot, coff, padT, padL);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_convt2x2_gather");
   return ASIS_OK;
 }
@@ -421,7 +406,7 @@ extern "C" int asis_convt2x2_gather(void* stream, int dtype, const float* dcat, 
 extern "C" int asis_conv1x1_dgrad_small(void* stream, int dtype, const void* d_hi, const void* d_lo, int64_t ldd, const float* w,
                                         float* dU, int64_t M, int Cq, int C) {
   ASIS_REQUIRE(d_hi && w && dU, "asis_conv1x1_dgrad_small: null pointer");
-  DT_OK(dtype, "asis_conv1x1_dgrad_small");
+  ASIS_DT_OK(dtype, "asis_conv1x1_dgrad_small");
   ASIS_REQUIRE(M > 0 && C >= 1 && C <= 8 && ldd >= C && Cq > 0 && Cq % 4 == 0 && Cq <= 1024,
                "asis_conv1x1_dgrad_small: C=%d (1..8), Cq=%d (multiple of 4, <= 1024), ldd=%ld", C, Cq, (long)ldd);
   ASIS_REQUIRE(asis_aligned16(w) && asis_aligned16(dU), "asis_conv1x1_dgrad_small: w and dU must be 16-byte aligned");
@@ -429,12 +414,11 @@ extern "C" int asis_conv1x1_dgrad_small(void* stream, int dtype, const void* d_h
   int64_t nblk = (M + rpb - 1) / rpb;
   if (nblk > 256 * 32) nblk = 256 * 32;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((conv1x1_dgrad_small_kernel<f16>), dim3((unsigned)nblk), dim3(256), 0, s, reinterpret_cast<const f16*>(d_hi),
-                       reinterpret_cast<const f16*>(d_lo), ldd, w, dU, M, Cq, C);
-  else
-    hipLaunchKernelGGL((conv1x1_dgrad_small_kernel<bf16>), dim3((unsigned)nblk), dim3(256), 0, s, reinterpret_cast<const bf16*>(d_hi),
-                       reinterpret_cast<const bf16*>(d_lo), ldd, w, dU, M, Cq, C);
+  if (int rc = asis_dispatch16(dtype, "asis_conv1x1_dgrad_small", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((conv1x1_dgrad_small_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, s, static_cast<const T*>(d_hi),
+                           static_cast<const T*>(d_lo), ldd, w, dU, M, Cq, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_conv1x1_dgrad_small");
   return ASIS_OK;
 }
@@ -464,17 +448,15 @@ extern "C" int asis_nearest_add_relu(void* stream, int dtype, void* x, void* x_l
                                      const int* ys, const int* xs, int B, int H, int W, int h, int w, int C) {
   ASIS_REQUIRE(x && r && ys && xs, "asis_nearest_add_relu: null pointer");
   ASIS_REQUIRE(C > 0 && C % 8 == 0 && B > 0 && H > 0 && W > 0 && h > 0 && w > 0, "asis_nearest_add_relu: bad shape (C=%d must be a multiple of 8)", C);
-  DT_OK(dtype, "asis_nearest_add_relu");
+  ASIS_DT_OK(dtype, "asis_nearest_add_relu");
   const int64_t total = (int64_t)B * H * W * (C / 8);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16)
-    hipLaunchKernelGGL((nearest_add_relu_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, reinterpret_cast<f16*>(x),
-                       reinterpret_cast<f16*>(x_lo), reinterpret_cast<const f16*>(r), reinterpret_cast<const f16*>(r_lo), ys, xs,
-                       B, H, W, h, w, C);
-  else
-    hipLaunchKernelGGL((nearest_add_relu_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, reinterpret_cast<bf16*>(x),
-                       reinterpret_cast<bf16*>(x_lo), reinterpret_cast<const bf16*>(r), reinterpret_cast<const bf16*>(r_lo), ys,
-                       xs, B, H, W, h, w, C);
+  if (int rc = asis_dispatch16(dtype, "asis_nearest_add_relu", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((nearest_add_relu_kernel<T>), dim3(asis_grid(total, 256, 65535 * 4)), dim3(256), 0, s, static_cast<T*>(x),
+                           static_cast<T*>(x_lo), static_cast<const T*>(r), static_cast<const T*>(r_lo), ys, xs,
+                           B, H, W, h, w, C);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_nearest_add_relu");
   return ASIS_OK;
 }
@@ -484,7 +466,7 @@ extern "C" int asis_nearest_sum(void* stream, const float* g, float* dr, const i
   ASIS_REQUIRE(g && dr && y0 && x0, "asis_nearest_sum: null pointer");
   ASIS_REQUIRE(C > 0 && C % 4 == 0 && B > 0 && H > 0 && W > 0 && h > 0 && w > 0, "asis_nearest_sum: bad shape (C=%d must be a multiple of 4)", C);
   const int64_t total = (int64_t)B * h * w * (C / 4);
-  hipLaunchKernelGGL(nearest_sum_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, dr, y0,
+  hipLaunchKernelGGL(nearest_sum_kernel, dim3(asis_grid(total, 256, 65535 * 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, dr, y0,
                      x0, B, H, W, h, w, C);
   ASIS_CHECK_LAUNCH("asis_nearest_sum");
   return ASIS_OK;

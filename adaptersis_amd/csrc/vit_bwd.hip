@@ -11,13 +11,6 @@ namespace {
 
 constexpr int LN_MAXC = 8;  // float4 chunks per lane -> D <= 2048
 
-inline int grid_for(int64_t total, int cap = 65535 * 4) {
-  int64_t g = (total + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // dx[row] = (res ? res[row] : 0) + rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * w
 // partial[blk][0][c] = sum_rows dy * xhat (d weight),  partial[blk][1][c] = sum_rows dy (d bias)
 // Each block owns ROWS_PER_BLOCK consecutive rows, 4 waves striding over them; statistics are recomputed from x.
@@ -349,13 +342,8 @@ __global__ __launch_bounds__(256) void ls_linear_finish_kernel(const float* __re
 
 }  // namespace
 
-#define DT_OK(dtype, name) ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16, name ": bad dtype %d", dtype)
-
 extern "C" int asis_rowblock_nblk(int64_t rows) {
-  int64_t n = (rows + 31) / 32;
-  if (n > 2048) n = 2048;
-  if (n < 1) n = 1;
-  return (int)n;
+  return asis_grid(rows, 32, 2048);
 }
 
 extern "C" int asis_layernorm_bwd(void* stream, const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w,
@@ -403,46 +391,48 @@ __global__ __launch_bounds__(256) void gelu_split_kernel(const float* __restrict
 
 extern "C" int asis_gelu_split(void* stream, int dtype, const float* x, void* hi, void* lo, int64_t n) {
   ASIS_REQUIRE(x && hi && n > 0 && n % 4 == 0, "asis_gelu_split: bad arguments (n %% 4 == 0)");
-  DT_OK(dtype, "asis_gelu_split");
+  ASIS_DT_OK(dtype, "asis_gelu_split");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int g = grid_for(n / 4);
-  if (dtype == ASIS_F16) hipLaunchKernelGGL((gelu_split_kernel<f16>), dim3(g), dim3(256), 0, s, x, (f16*)hi, (f16*)lo, n / 4);
-  else hipLaunchKernelGGL((gelu_split_kernel<bf16>), dim3(g), dim3(256), 0, s, x, (bf16*)hi, (bf16*)lo, n / 4);
+  const int g = asis_grid(n / 4, 256, 65535 * 4);
+  if (int rc = asis_dispatch16(dtype, "asis_gelu_split", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((gelu_split_kernel<T>), dim3(g), dim3(256), 0, s, x, static_cast<T*>(hi), static_cast<T*>(lo), n / 4);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_gelu_split");
   return ASIS_OK;
 }
 
 extern "C" int asis_gelu16(void* stream, int dtype, const void* pre, const void* dpost, void* out, int64_t n) {
   ASIS_REQUIRE(pre && out && n > 0 && n % 8 == 0, "asis_gelu16: bad arguments (n %% 8 == 0)");
-  DT_OK(dtype, "asis_gelu16");
+  ASIS_DT_OK(dtype, "asis_gelu16");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t n8 = n / 8;
-  const int g = grid_for(n8);
-  if (dtype == ASIS_F16) {
-    if (dpost) hipLaunchKernelGGL((gelu16_kernel<f16, true>), dim3(g), dim3(256), 0, s, (const f16*)pre, (const f16*)dpost, (f16*)out, n8);
-    else hipLaunchKernelGGL((gelu16_kernel<f16, false>), dim3(g), dim3(256), 0, s, (const f16*)pre, (const f16*)nullptr, (f16*)out, n8);
-  } else {
-    if (dpost) hipLaunchKernelGGL((gelu16_kernel<bf16, true>), dim3(g), dim3(256), 0, s, (const bf16*)pre, (const bf16*)dpost, (bf16*)out, n8);
-    else hipLaunchKernelGGL((gelu16_kernel<bf16, false>), dim3(g), dim3(256), 0, s, (const bf16*)pre, (const bf16*)nullptr, (bf16*)out, n8);
-  }
+  const int g = asis_grid(n8, 256, 65535 * 4);
+  if (int rc = asis_dispatch16(dtype, "asis_gelu16", [&](auto t) {
+        using T = decltype(t);
+        if (dpost) hipLaunchKernelGGL((gelu16_kernel<T, true>), dim3(g), dim3(256), 0, s, static_cast<const T*>(pre), static_cast<const T*>(dpost), static_cast<T*>(out), n8);
+        else hipLaunchKernelGGL((gelu16_kernel<T, false>), dim3(g), dim3(256), 0, s, static_cast<const T*>(pre), static_cast<const T*>(nullptr), static_cast<T*>(out), n8);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_gelu16");
   return ASIS_OK;
 }
 
 extern "C" int asis_swiglu_bwd(void* stream, int dtype, const float* x12, const void* dh, void* dx12, int64_t R, int Hd) {
   ASIS_REQUIRE(x12 && dh && dx12 && R > 0 && Hd > 0 && Hd % 4 == 0, "asis_swiglu_bwd: bad arguments (Hd %% 4 == 0)");
-  DT_OK(dtype, "asis_swiglu_bwd");
+  ASIS_DT_OK(dtype, "asis_swiglu_bwd");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int g = grid_for(R * (Hd / 4));
-  if (dtype == ASIS_F16) hipLaunchKernelGGL((swiglu_bwd_kernel<f16>), dim3(g), dim3(256), 0, s, x12, (const f16*)dh, (f16*)dx12, R, Hd);
-  else hipLaunchKernelGGL((swiglu_bwd_kernel<bf16>), dim3(g), dim3(256), 0, s, x12, (const bf16*)dh, (bf16*)dx12, R, Hd);
+  const int g = asis_grid(R * (Hd / 4), 256, 65535 * 4);
+  if (int rc = asis_dispatch16(dtype, "asis_swiglu_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((swiglu_bwd_kernel<T>), dim3(g), dim3(256), 0, s, x12, static_cast<const T*>(dh), static_cast<T*>(dx12), R, Hd);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_swiglu_bwd");
   return ASIS_OK;
 }
 
 extern "C" int asis_colsum(void* stream, int dtype, const void* x, int64_t ld, float* partial, int64_t rows, int C) {
   ASIS_REQUIRE(x && partial && rows > 0, "asis_colsum: bad arguments");
-  ASIS_REQUIRE(dtype == ASIS_F16 || dtype == ASIS_BF16 || dtype == ASIS_F32, "asis_colsum: bad dtype %d", dtype);
+  if (dtype != ASIS_F32) ASIS_DT_OK(dtype, "asis_colsum");
   ASIS_REQUIRE(C > 0 && C % 8 == 0 && ld % 8 == 0 && ld >= C, "asis_colsum: C=%d and ld must be multiples of 8", C);
   const int nblk = asis_rowblock_nblk(rows);
   const int rpb = (int)((rows + nblk - 1) / nblk);
@@ -450,12 +440,13 @@ extern "C" int asis_colsum(void* stream, int dtype, const void* x, int64_t ld, f
   // gridDim.y walks the columns (256 threads x 8 / 4 columns each), so few-rows x very-wide inputs (the batch sum of a
   // [B, tokens*D] gradient) still fill the chip
   const int per = dtype == ASIS_F32 ? 4 : 8;
-  int gy = (C / per + 255) / 256;
-  if (gy > 4096) gy = 4096;
-  if (gy < 1) gy = 1;
-  if (dtype == ASIS_F16) hipLaunchKernelGGL((colsum16_kernel<f16>), dim3(nblk, gy), dim3(256), 0, s, (const f16*)x, ld, partial, rows, C, rpb);
-  else if (dtype == ASIS_BF16) hipLaunchKernelGGL((colsum16_kernel<bf16>), dim3(nblk, gy), dim3(256), 0, s, (const bf16*)x, ld, partial, rows, C, rpb);
-  else hipLaunchKernelGGL(colsum32_kernel, dim3(nblk, gy), dim3(256), 0, s, (const float*)x, ld, partial, rows, C, rpb);
+  const int gy = asis_grid(C / per, 256, 4096);
+  if (dtype == ASIS_F32)  // the float branch stays explicit: the dispatcher knows the two 16-bit types only
+    hipLaunchKernelGGL(colsum32_kernel, dim3(nblk, gy), dim3(256), 0, s, static_cast<const float*>(x), ld, partial, rows, C, rpb);
+  else if (int rc = asis_dispatch16(dtype, "asis_colsum", [&](auto t) {
+             using T = decltype(t);
+             hipLaunchKernelGGL((colsum16_kernel<T>), dim3(nblk, gy), dim3(256), 0, s, static_cast<const T*>(x), ld, partial, rows, C, rpb);
+           })) return rc;
   ASIS_CHECK_LAUNCH("asis_colsum");
   return ASIS_OK;
 }
@@ -463,19 +454,17 @@ extern "C" int asis_colsum(void* stream, int dtype, const void* x, int64_t ld, f
 extern "C" int asis_cast_colsum(void* stream, int dtype, const float* x, int64_t ldx, void* out, int64_t ldo, float scale,
                                 float* partial, int64_t rows, int D) {
   ASIS_REQUIRE(x && out && partial && rows > 0, "asis_cast_colsum: bad arguments");
-  DT_OK(dtype, "asis_cast_colsum");
+  ASIS_DT_OK(dtype, "asis_cast_colsum");
   ASIS_REQUIRE(D > 0 && D % 4 == 0 && D <= LN_MAXC * 256 && ldx % 4 == 0 && ldo % 4 == 0 && ldo >= D,
                "asis_cast_colsum: D=%d must be a multiple of 4, <= %d; row strides multiples of 4", D, LN_MAXC * 256);
   const int nblk = asis_rowblock_nblk(rows);
   const int rpb = (int)((rows + nblk - 1) / nblk);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == ASIS_F16) {
-    if (D <= 1024) hipLaunchKernelGGL((cast_colsum_kernel<f16, 4>), dim3(nblk), dim3(256), 0, s, x, ldx, (f16*)out, ldo, scale, partial, rows, D, rpb);
-    else hipLaunchKernelGGL((cast_colsum_kernel<f16, LN_MAXC>), dim3(nblk), dim3(256), 0, s, x, ldx, (f16*)out, ldo, scale, partial, rows, D, rpb);
-  } else {
-    if (D <= 1024) hipLaunchKernelGGL((cast_colsum_kernel<bf16, 4>), dim3(nblk), dim3(256), 0, s, x, ldx, (bf16*)out, ldo, scale, partial, rows, D, rpb);
-    else hipLaunchKernelGGL((cast_colsum_kernel<bf16, LN_MAXC>), dim3(nblk), dim3(256), 0, s, x, ldx, (bf16*)out, ldo, scale, partial, rows, D, rpb);
-  }
+  if (int rc = asis_dispatch16(dtype, "asis_cast_colsum", [&](auto t) {
+        using T = decltype(t);
+        if (D <= 1024) hipLaunchKernelGGL((cast_colsum_kernel<T, 4>), dim3(nblk), dim3(256), 0, s, x, ldx, static_cast<T*>(out), ldo, scale, partial, rows, D, rpb);
+        else hipLaunchKernelGGL((cast_colsum_kernel<T, LN_MAXC>), dim3(nblk), dim3(256), 0, s, x, ldx, static_cast<T*>(out), ldo, scale, partial, rows, D, rpb);
+      })) return rc;
   ASIS_CHECK_LAUNCH("asis_cast_colsum");
   return ASIS_OK;
 }

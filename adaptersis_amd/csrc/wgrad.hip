@@ -427,7 +427,7 @@ extern "C" int asis_wgrad(void* stream, const asis_wgrad_desc* dp) {
   ASIS_REQUIRE(dp != nullptr, "asis_wgrad: null descriptor");
   asis_wgrad_desc d = *dp;
   ASIS_REQUIRE(d.dy && d.x && d.out, "asis_wgrad: null pointer");
-  ASIS_REQUIRE(d.dtype == ASIS_F16 || d.dtype == ASIS_BF16, "asis_wgrad: bad dtype %d", d.dtype);
+  ASIS_DT_OK(d.dtype, "asis_wgrad");
   ASIS_REQUIRE(d.Cin % 8 == 0 && d.Cin > 0 && d.Cout > 0, "asis_wgrad: Cin=%d must be a multiple of 8", d.Cin);
   ASIS_REQUIRE(d.CoP % 8 == 0 && d.CoP >= d.Cout && d.ld_dy >= d.CoP && d.ld_dy % 8 == 0,
                "asis_wgrad: dy channels must be padded to a multiple of 8 (CoP=%d, ld=%ld)", d.CoP, (long)d.ld_dy);
@@ -446,33 +446,23 @@ extern "C" int asis_wgrad(void* stream, const asis_wgrad_desc* dp) {
   const bool dense = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0;
   // ASIS_WGRAD_BIG (default 1): nn.Linear weight gradients with whole 256 x 128 tiles on the LDS-DMA form
   static const int big = [] { const char* e = getenv("ASIS_WGRAD_BIG"); return e ? atoi(e) : 1; }();
-  if (big && dense && d.Cout % 256 == 0 && d.Cin % 128 == 0 && d.CoP == d.Cout && d.P >= 1024 && d.k_per_split % 32 == 0) {
-    dim3 gb((unsigned)((d.Cout / 256) * (d.Cin / 128)), d.splits);
-    if (d.dtype == ASIS_F16) hipLaunchKernelGGL((wgrad_dense_big_kernel<f16>), gb, dim3(512), 0, s, d);
-    else hipLaunchKernelGGL((wgrad_dense_big_kernel<bf16>), gb, dim3(512), 0, s, d);
-    ASIS_CHECK_LAUNCH("asis_wgrad");
-    return ASIS_OK;
-  }
+  const bool big_tiles = big && d.Cout % 256 == 0 && d.Cin % 128 == 0 && d.CoP == d.Cout && d.P >= 1024 && d.k_per_split % 32 == 0;
   // the same tile form for stride-1 convolutions whose 128-column tiles lie inside one tap (decoder_1 .. 3)
-  if (big && !dense && d.stride == 1 && d.Cout % 256 == 0 && d.Cin % 128 == 0 && d.CoP == d.Cout && d.P >= 1024 &&
-      d.k_per_split % 32 == 0 && (int64_t)d.B_ * d.H * d.W * d.Cin < (1LL << 40)) {
-    dim3 gb((unsigned)((d.Cout / 256) * (Ntot / 128)), d.splits);
-    if (d.dtype == ASIS_F16) hipLaunchKernelGGL((wgrad_dense_big_kernel<f16, true>), gb, dim3(512), 0, s, d);
-    else hipLaunchKernelGGL((wgrad_dense_big_kernel<bf16, true>), gb, dim3(512), 0, s, d);
-    ASIS_CHECK_LAUNCH("asis_wgrad");
-    return ASIS_OK;
-  }
-#define ASIS_WGRAD_LAUNCH(TT, DN)                                                                         \
-  do {                                                                                                    \
-    if (bme == 32) hipLaunchKernelGGL((wgrad_kernel<TT, DN, 32>), grid, block, 0, s, d);                  \
-    else if (bme == 64) hipLaunchKernelGGL((wgrad_kernel<TT, DN, 64>), grid, block, 0, s, d);             \
-    else hipLaunchKernelGGL((wgrad_kernel<TT, DN, 128>), grid, block, 0, s, d);                           \
+  const bool big_conv = big_tiles && !dense && d.stride == 1 && (int64_t)d.B_ * d.H * d.W * d.Cin < (1LL << 40);
+  const dim3 gb((unsigned)((d.Cout / 256) * (Ntot / 128)), d.splits);  // dense: Ntot = Cin
+#define ASIS_WGRAD_LAUNCH(DN)                                                                            \
+  do {                                                                                                   \
+    if (bme == 32) hipLaunchKernelGGL((wgrad_kernel<T, DN, 32>), grid, block, 0, s, d);                  \
+    else if (bme == 64) hipLaunchKernelGGL((wgrad_kernel<T, DN, 64>), grid, block, 0, s, d);             \
+    else hipLaunchKernelGGL((wgrad_kernel<T, DN, 128>), grid, block, 0, s, d);                           \
   } while (0)
-  if (d.dtype == ASIS_F16) {
-    if (dense) ASIS_WGRAD_LAUNCH(f16, true); else ASIS_WGRAD_LAUNCH(f16, false);
-  } else {
-    if (dense) ASIS_WGRAD_LAUNCH(bf16, true); else ASIS_WGRAD_LAUNCH(bf16, false);
-  }
+  if (int rc = asis_dispatch16(d.dtype, "asis_wgrad", [&](auto t) {
+        using T = decltype(t);
+        if (big_tiles && dense) hipLaunchKernelGGL((wgrad_dense_big_kernel<T>), gb, dim3(512), 0, s, d);
+        else if (big_conv) hipLaunchKernelGGL((wgrad_dense_big_kernel<T, true>), gb, dim3(512), 0, s, d);
+        else if (dense) ASIS_WGRAD_LAUNCH(true);
+        else ASIS_WGRAD_LAUNCH(false);
+      })) return rc;
 #undef ASIS_WGRAD_LAUNCH
   ASIS_CHECK_LAUNCH("asis_wgrad");
   return ASIS_OK;
