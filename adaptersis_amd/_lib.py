@@ -66,18 +66,20 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m adaptersis_amd.build` "
             "(hipcc --offload-arch=gfx950). adaptersis_amd has no fallback path.")
     _lib = C.CDLL(LIB_PATH)
-    _lib.asis_last_error.restype = C.c_char_p
     _declare(_lib)
+    _lib.asis_last_error.restype = _lib.asis_gemm_form_name.restype = C.c_char_p
     return _lib
 
 
-# name -> argtypes ; every function returns int
+# name -> argtypes ; every function returns int (asis_gemm_form_name, like asis_last_error, a C string: set in lib())
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "asis_version": [],
     "asis_device_count": [],
     "asis_gemm": [_vp, C.POINTER(GemmDesc)],
     "asis_gemm_tiles_m": [_i],
+    "asis_gemm_plan": [C.POINTER(GemmDesc), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
+    "asis_gemm_form_name": [_i],
     "asis_absmax_f32": [_vp, _vp, _i64, _i, _i64, _vp, _i],
     "asis_bn_relu_absmax": [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp],
     "asis_absmax_16": [_vp, _i, _vp, _i64, _i, _i64, _vp],

@@ -209,219 +209,229 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const asis_gemm_desc 
 #include "gemm_big.h"
 #include "gemm_p8.h"
 
-// ASIS_GEMM_P8 / asis_gemm_set_option("p8", v): -1 = not read yet
-static int g_gemm_p8 = -1;
-static bool ph8_m16_on() { static const int v = [] { const char* e = getenv("ASIS_GEMM_8P_M16"); return e ? atoi(e) : 1; }(); return v != 0; }
+// ---- host side: options -> plan -> launch ---------------------------------------------------------------------------------
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int env_positive(const char* name, int dflt) { const int v = env_int(name, dflt); return v > 0 ? v : dflt; }
 
-template <typename T>
-int launch(hipStream_t s, const asis_gemm_desc& d) {
-  // large-tile LDS-DMA kernel (gemm_big.h); ASIS_GEMM_BIG=0 forces the 128x128 register-staged kernel
-  static const int group_m = [] { const char* e = getenv("ASIS_GEMM_GROUPM"); return e && atoi(e) > 0 ? atoi(e) : 4; }();
-  static const int big_mode = [] { const char* e = getenv("ASIS_GEMM_BIG"); return e ? atoi(e) : 1; }();
+// Every switch of the dispatcher, read from the environment once, on first use ("p8" also through asis_gemm_set_option).
+struct GemmOpts {
+  int group_m = env_positive("ASIS_GEMM_GROUPM", 4);  // raster group height of the large-tile kernels
+  // the large-tile LDS-DMA kernels (gemm_big.h); 0 forces the 128x128 register-staged kernel, 2 / 3 keep the older 256x256 /
+  // 256x128x64 dense forms selectable for A/B runs
+  int big = env_int("ASIS_GEMM_BIG", 1);
+  // 1: dense launches with at least one 256x256 tile per CU run on the PERSISTENT form of the 8-phase kernel (gemm_p8.h: one
+  // workgroup per CU walks its tiles, the next tile's first K tile is staged during the last K tile of the current one, the
+  // epilogue's stores drain under the next tile) when K <= 2048 (at K = 4096 a tile is 64 K tiles long and the per-tile savings
+  // no longer pay for the static tile lists: 347 vs 341 us); split-precision halves (A_lo / B_lo) are further K parts of the
+  // same stream; 2 = any K, from 16 tiles on (tests); 3 = any K; 0 = never
+  int p8 = env_int("ASIS_GEMM_P8", 1);
+  // 0 = never; 1 = K >= 2048 (fc2 / its input gradient: 343 vs 476 us at 42348x1024x4096) and, since the phases run on
+  // 16x16x32 MFMAs (ph8_m16: fc2 391 -> 350 us in isolation), the unbatched K >= 1024 GEMMs too (in the step: qk 222 -> 214 us,
+  // proj 160 -> 139, fc1 457 -> 441, adapter projections 242 -> 216; +3.5 % on the step) — the batched ragged V^T GEMM lost
+  // there at first (66 vs 72 us: coarser tile quantisation) and wins since the form's 16-bit outputs are converted before the
+  // LDS transposition (+0.9 % on the step); (only when there are at least 128 of its 256x256 tiles: a launch that cannot fill
+  // the chip is better off with twice as many 256x128 tiles); 3 = K >= 2048 only (the round-1 rule); 2 = wherever the shape allows
+  int ph8 = env_int("ASIS_GEMM_8P", 1);
+  int ph8_mink = env_int("ASIS_GEMM_8P_MINK", 1024);  // lab: the K >= 1024 of the rule above (not of the LayerNorm-fold launches)
+  // the phases issue 16 v_mfma_f32_16x16x32 instead of 8 32x32x16 (same FLOP, higher clock); the persistent, LayerNorm-fold and
+  // SwiGLU forms exist on these phases only
+  int ph8_m16 = env_int("ASIS_GEMM_8P_M16", 1);
+  int ph8_slab32 = env_int("ASIS_GEMM_8P_SLAB32", 0);  // lab: 16-bit outputs through the fp32 slab epilogue like the others
+  int m16 = env_int("ASIS_GEMM_M16", 1);               // 16x16x32 MFMAs in the default dense form
+  int mx_ph8 = env_int("ASIS_MX_PH8", 1);              // lab: 0 = MX convolutions on the generic large-tile forms only
+  int conv_bk32 = env_int("ASIS_CONV_BK32", 0);        // 32-wide K tiles in the 256x128 split convolution
+  // <= 64 output channels: 512x64 tile, 8 waves of 64x64 (1 KB of LDS fragment reads per MFMA; the 256x64 form's 32x64 wave
+  // tiles need 1.5 KB and are LDS-bound), one workgroup per CU: +0.6 % on the step (0: old form)
+  int conv_t512 = env_int("ASIS_CONV_T512", 1);
+  int conv_m16 = env_int("ASIS_CONV_M16", 0);          // 16x16x32 MFMAs in the split convs
+  // convolutions with whole 256-column tiles on the 8-phase 256x256x64 main loop (gemm_big.h): the long reductions of the
+  // decoder convs are where that loop is at its best (K = 9 * Cin * 3 parts)
+  int conv_8p = env_int("ASIS_CONV_8P", 1);
+};
+static GemmOpts& gemm_opts() { static GemmOpts o; return o; }
+
+// One enumerator per kernel instantiation the dispatcher can reach (what each is for: include/asis_hip.h, asis_gemm_plan).
+// Names: tile, then variant (m16 = 16x16x32 MFMAs, split = A_lo / B_lo K parts, mx = MX lo operands, ln = LayerNorm fold).
+#define ASIS_GEMM_FORMS(X)                                                                                                  \
+  X(P8, "p8") X(P8_LN, "p8_ln") X(PH8_M16, "ph8_m16") X(PH8_M32, "ph8_m32") X(PH8_LN, "ph8_ln") X(PH8_MX, "ph8_mx")         \
+  X(BIG_256x128_M16, "big_256x128_m16") X(BIG_256x128, "big_256x128") X(BIG_256x128_K64, "big_256x128_k64")                 \
+  X(BIG_256x256, "big_256x256") X(BIG_256x128_SPLIT, "big_256x128_split") X(BIG_256x64_SPLIT, "big_256x64_split")           \
+  X(CONV_PH8, "conv_ph8") X(CONV_256x128, "conv_256x128") X(CONV_256x64, "conv_256x64") X(CONV_PH8_SPLIT, "conv_ph8_split") \
+  X(CONV_512x64_SPLIT, "conv_512x64_split") X(CONV_512x64_SPLIT_M16, "conv_512x64_split_m16")                               \
+  X(CONV_256x128_SPLIT, "conv_256x128_split") X(CONV_256x128_SPLIT_M16, "conv_256x128_split_m16")                           \
+  X(CONV_256x128_SPLIT_BK32, "conv_256x128_split_bk32") X(CONV_256x64_SPLIT, "conv_256x64_split")                           \
+  X(CONV_PH8_MX, "conv_ph8_mx") X(CONV_512x64_MX, "conv_512x64_mx") X(CONV_256x128_MX, "conv_256x128_mx")                   \
+  X(CONV_256x64_MX, "conv_256x64_mx") X(GENERIC, "generic") X(GENERIC_CONV, "generic_conv")
+#define X(id, name) F_##id,
+enum GemmForm { ASIS_GEMM_FORMS(X) F_COUNT };
+#undef X
+#define X(id, name) name,
+const char* const kFormNames[F_COUNT] = {ASIS_GEMM_FORMS(X)};
+#undef X
+
+struct GemmPlan {
+  int form, grid_x, grid_y, block;
+  int group_m;   // second kernel argument of the large-tile forms: GemmOpts::group_m | 0x10000 (fp32 slab epilogue, lab)
+};
+
+// Which form a validated descriptor runs on, and its launch geometry; ASIS_EINVAL when no form takes it.  Pure: no HIP call,
+// pointers are only tested for null and alignment.  The order of the cascade is behaviour.
+int gemm_plan(const asis_gemm_desc& d, const GemmOpts& o, GemmPlan* p) {
+  auto al = [](const void* q, int a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
+  auto tiles = [&](int bm, int bn) { return (int64_t)((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn); };
+  auto take = [&](GemmForm f, int64_t gx, int gy, int block = 512, int flags = 0) {
+    *p = GemmPlan{f, (int)gx, gy, block, o.group_m | flags};
+    return (int)ASIS_OK;
+  };
   const bool vec_ok = (d.N % 4 == 0) && (d.ldc % 4 == 0);
   const bool split = d.A_lo != nullptr || d.B_lo != nullptr;
+  const bool mx_pair = d.mx_amax_a && d.mx_amax_b && d.A_lo && d.B_lo;
+  const bool ph8_m16 = o.ph8_m16 != 0;
+  const int64_t t256 = tiles(256, 256);              // 256x256 tiles: the grid of every 8-phase form
+  const int ky = d.ksplit > 1 ? d.ksplit : 1;        // grid.y of a convolution: its K parts
+  // the 8-phase K rule (GemmOpts::ph8) and the convolution shapes of the 8-phase loop: whole 256-column tiles
+  auto ph8_k = [&](int mink) { return o.ph8 == 2 || d.K >= 2048 || (o.ph8 == 1 && d.K >= mink && t256 * d.batch >= 128); };
+  const bool conv_ph8_shape = d.N >= 256 && (d.N % 256 == 0 || d.N >= 1024) && d.batch == 1;
+  // the 256-row large tile of the split / convolution forms: 128 columns, 64 for <= 64 output channels
+  const int bn = d.N > 64 ? 128 : 64;
+
   if (d.act == ASIS_ACT_GELU_GRAD) {  // only the vector epilogue of the large-tile kernels implements it
-    const bool ok = big_mode && !d.conv && !split && !d.stats && d.aux && d.K % 32 == 0 && d.M >= 256 && d.N >= 128 && vec_ok &&
-                    d.ld_aux % 4 == 0 && d.batch == 1 && (reinterpret_cast<uintptr_t>(d.aux) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(d.C) & 15) == 0 && !d.bias_m;
+    const bool ok = o.big && !d.conv && !split && !d.stats && d.aux && d.K % 32 == 0 && d.M >= 256 && d.N >= 128 && vec_ok &&
+                    d.ld_aux % 4 == 0 && d.batch == 1 && al(d.aux, 8) && al(d.C, 16) && !d.bias_m;
     if (!ok) return ASIS_EINVAL;
   }
   if (d.act == ASIS_ACT_SILU_MUL) {
     // SwiGLU epilogue: lives in the 16-bit fast path of the 8-phase 16x16-MFMA instances (gemm_big.h) — the launch goes there
     // directly or is refused (a fall-through to another epilogue would write x1 | x2 as if they were outputs)
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool mxs = d.mx_amax_a && d.mx_amax_b && d.A_lo && d.B_lo;
-    const bool ok = big_mode && ph8_m16_on() && !d.conv && (mxs || !split) && !d.out_f32 && !d.res && !d.res16 && !d.C_lo && !d.rowstats &&
+    const bool ok = o.big && ph8_m16 && !d.conv && (mx_pair || !split) && !d.out_f32 && !d.res && !d.res16 && !d.C_lo && !d.rowstats &&
                     !d.stats && !d.scale_n && !d.bias_m && !d.ln_mr && !d.aux && d.batch == 1 && d.ksplit <= 1 && d.K % 64 == 0 && d.M >= 256 &&
-                    d.N >= 256 && d.N % 32 == 0 && d.ldc % 8 == 0 && d.ldc >= d.N / 2 && al16(d.C) && (!d.bias_n || al16(d.bias_n)) &&
+                    d.N >= 256 && d.N % 32 == 0 && d.ldc % 8 == 0 && d.ldc >= d.N / 2 && al(d.C, 16) && (!d.bias_n || al(d.bias_n, 16)) &&
                     (int64_t)d.N * d.ldb < (1ll << 31);
     if (!ok) return ASIS_EINVAL;
-    dim3 g8(((d.M + 255) / 256) * ((d.N + 255) / 256), 1), block(512);
-    if (mxs) hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, true, 64, 1, true, true, 0, true>), g8, block, 0, s, d, group_m);
-    else hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true, true>), g8, block, 0, s, d, group_m);
-    return 0;
+    return take(mx_pair ? F_PH8_MX : F_PH8_M16, t256, 1);
   }
-  if (d.ksplit > 1 && !(big_mode && d.conv)) return ASIS_EINVAL;
-  // ASIS_GEMM_P8 (default 1): dense launches with at least one 256x256 tile per CU run on the PERSISTENT form of the 8-phase
-  // kernel (gemm_p8.h: one workgroup per CU walks its tiles, the next tile's first K tile is staged during the last K tile of
-  // the current one, the epilogue's stores drain under the next tile) when K <= 2048 (at K = 4096 a tile is 64 K tiles long
-  // and the per-tile savings no longer pay for the static tile lists: 347 vs 341 us); split-precision halves (A_lo / B_lo)
-  // are further K parts of the same stream; 2 = any K, from 16 tiles on (tests); 3 = any K; 0 = never
-  {
-    if (g_gemm_p8 < 0) { const char* e = getenv("ASIS_GEMM_P8"); g_gemm_p8 = e ? atoi(e) : 1; }
-    const int p8 = g_gemm_p8;
-    const int64_t p8_tiles = (int64_t)((d.M + 255) / 256) * ((d.N + 255) / 256);
+  if (d.ksplit > 1 && !(o.big && d.conv)) return ASIS_EINVAL;
+  {  // the persistent 8-phase kernel (GemmOpts::p8)
     const int kparts = 1 + (d.A_lo ? 1 : 0) + (d.B_lo ? 1 : 0);
-    auto al = [](const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
-    if (p8 && big_mode && ph8_m16_on() && !d.conv && !d.stats && d.batch == 1 && !d.bias_m && !d.ln_cols && !d.C_lo && !d.rowstats && !d.res16 &&
+    if (o.p8 && o.big && ph8_m16 && !d.conv && !d.stats && d.batch == 1 && !d.bias_m && !d.ln_cols && !d.C_lo && !d.rowstats && !d.res16 &&
         !d.mx_amax_a && !d.mx_amax_b &&
         d.ksplit <= 1 && d.K % 64 == 0 &&
-        d.M >= 256 && d.N >= 256 && p8_tiles >= (p8 == 2 ? 16 : 256) && d.K >= 128 && (p8 >= 2 || d.K * kparts <= 2048) &&
+        d.M >= 256 && d.N >= 256 && t256 >= (o.p8 == 2 ? 16 : 256) && d.K >= 128 && (o.p8 >= 2 || d.K * kparts <= 2048) &&
         (int64_t)d.M * d.lda * 2 < (1ll << 32) && (int64_t)d.N * d.ldb * 2 < (1ll << 32) && d.N % 8 == 0 && d.ldc % 8 == 0 &&
         al(d.C, 16) && (!d.res || (al(d.res, 16) && d.ldr % 4 == 0)) && (!d.bias_n || al(d.bias_n, 16)) && (!d.scale_n || al(d.scale_n, 16)) &&
-        (d.act != ASIS_ACT_GELU_GRAD || (d.aux && al(d.aux, 8) && d.ld_aux % 4 == 0))) {
-      const int nwg = p8_tiles >= 256 ? 256 : (int)(p8_tiles / 8) * 8;
-      if (d.ln_mr) hipLaunchKernelGGL((gemm_p8_kernel<T, 1>), dim3(nwg), dim3(512), 0, s, d, group_m);   // LayerNorm-fold consumer
-      else hipLaunchKernelGGL((gemm_p8_kernel<T, 0>), dim3(nwg), dim3(512), 0, s, d, group_m);
-      return 0;
-    }
+        (d.act != ASIS_ACT_GELU_GRAD || (d.aux && al(d.aux, 8) && d.ld_aux % 4 == 0)))
+      return take(d.ln_mr ? F_P8_LN : F_P8, t256 >= 256 ? 256 : (int)(t256 / 8) * 8, 1);
   }
   // LayerNorm-fold fields (C_lo / rowstats / res16 / ln_mr): implemented by the persistent kernel above and by the dense 8-phase
   // one-tile-per-workgroup form below; anything else is refused (the caller runs asis_layernorm and plain launches)
   const bool lnx = d.C_lo || d.rowstats || d.res16 || d.ln_mr;
   if (lnx) {
-    static const int ph8x = [] { const char* e = getenv("ASIS_GEMM_8P"); return e ? atoi(e) : 1; }();
-    const bool ph8_ok = ph8x && ph8_m16_on() && big_mode && !split && !d.conv && !d.stats && d.K % 64 == 0 && d.M >= 256 && d.N >= 256 &&
-                        (ph8x == 2 || d.K >= 2048 || (ph8x == 1 && d.K >= 1024 && (int64_t)((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch >= 128)) &&
-                        d.N % 8 == 0 && d.ldc % 8 == 0 && (!d.res16 || (d.res16_lo && d.ldr16 % 8 == 0 && d.ldr16 >= d.N && asis_aligned16(d.res16) && asis_aligned16(d.res16_lo))) &&
+    const bool ph8_ok = o.ph8 && ph8_m16 && o.big && !split && !d.conv && !d.stats && d.K % 64 == 0 && d.M >= 256 && d.N >= 256 &&
+                        ph8_k(1024) &&
+                        d.N % 8 == 0 && d.ldc % 8 == 0 && (!d.res16 || (d.res16_lo && d.ldr16 % 8 == 0 && d.ldr16 >= d.N && al(d.res16, 16) && al(d.res16_lo, 16))) &&
                         (!d.C_lo || !d.out_f32) && (!d.ln_mr || d.ln_cs) &&
                         // producer launches (dedicated 8-columns-per-lane epilogue of gemm_big.h): plain v = res + scale * (acc + bias)
                         (!(d.C_lo || d.rowstats || d.res16) ||
-                         ((!d.res || (d.ldr % 8 == 0 && asis_aligned16(d.res))) && (!d.C_lo || asis_aligned16(d.C_lo)) && asis_aligned16(d.C) &&
-                          (!d.bias_n || asis_aligned16(d.bias_n)) && (!d.scale_n || asis_aligned16(d.scale_n)) && d.batch == 1 && !d.bias_m &&
+                         ((!d.res || (d.ldr % 8 == 0 && al(d.res, 16))) && (!d.C_lo || al(d.C_lo, 16)) && al(d.C, 16) &&
+                          (!d.bias_n || al(d.bias_n, 16)) && (!d.scale_n || al(d.scale_n, 16)) && d.batch == 1 && !d.bias_m &&
                           d.act == ASIS_ACT_NONE && !d.ln_mr));
     if (!ph8_ok) return ASIS_EINVAL;
   }
   if (split) {  // one pass over the virtual 3K reduction; only on the large-tile kernel
-    const bool ok = big_mode && d.K % BK == 0 && d.M >= 256 && d.N >= 32 && vec_ok && (d.out_f32 || !d.conv) &&
+    const bool ok = o.big && d.K % BK == 0 && d.M >= 256 && d.N >= 32 && vec_ok && (d.out_f32 || !d.conv) &&
                     (!d.conv || (d.Cin % BK == 0 && d.A_lo && d.B_lo));
     if (!ok) return ASIS_EINVAL;
-    const int bm = 256, bn = d.N > 64 ? 128 : 64;
     if (d.ksplit > 1 && (d.batch != 1 || d.stats || (d.KH * d.KW) % d.ksplit != 0 || !d.out_f32 || d.res)) return ASIS_EINVAL;
-    dim3 grid(((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn), d.ksplit > 1 ? d.ksplit : d.batch), block(512);
+    const int64_t gx = tiles(256, bn), gx512 = tiles(512, 64);
+    const int gy = d.ksplit > 1 ? d.ksplit : d.batch;
     if (d.mx_amax_a || d.mx_amax_b) {
       // MX form of the lo operands (include/asis_hip.h): two K parts, the second on the block-scaled fp8 MFMA; 16x16 MFMA
       // instances of the three convolution tile forms
-      if (!(d.mx_amax_a && d.mx_amax_b && d.A_lo && d.B_lo)) return ASIS_EINVAL;
+      if (!mx_pair) return ASIS_EINVAL;
       if (!d.conv) {   // dense: the 8-phase one-tile-per-workgroup form, K tiles alternating 16-bit / MX
         if (!(d.K % 64 == 0 && d.N >= 256 && d.batch == 1 && d.ksplit <= 1 && !d.stats && (int64_t)d.N * d.ldb < (1ll << 31))) return ASIS_EINVAL;
-        dim3 g8(((d.M + 255) / 256) * ((d.N + 255) / 256), 1);
-        hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, true, 64, 1, true, true, 0, true>), g8, block, 0, s, d, group_m);
-        return 0;
+        return take(F_PH8_MX, t256, 1);
       }
       if ((int64_t)d.B_ * d.H * d.W * d.Cin >= (1ll << 31) || (int64_t)d.N * d.ldb >= (1ll << 31) || d.H >= 65536 || d.W >= 65536) return ASIS_EINVAL;
-      static const int mx_ph8 = [] { const char* e = getenv("ASIS_MX_PH8"); return e ? atoi(e) : 1; }();   // lab: 0 = generic forms only
-      if (mx_ph8 && d.N >= 256 && (d.N % 256 == 0 || d.N >= 1024) && d.batch == 1) {
-        dim3 g8(((d.M + 255) / 256) * ((d.N + 255) / 256), d.ksplit > 1 ? d.ksplit : 1);
-        hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, true, true, 64, 1, true, true, 0, true>), g8, block, 0, s, d, group_m);
-      } else if (bn == 64 && d.ksplit <= 1 && d.M >= 512) {
-        dim3 g512(((d.M + 511) / 512) * ((d.N + 63) / 64), 1);
-        hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 2, 2, 2, 0, true, true, 64, 1, false, true, 0, true>), g512, block, 0, s, d, group_m);
-      } else if (bn == 128) {
-        hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true, 64, 1, false, true, 0, true>), grid, block, 0, s, d, group_m);
-      } else {
-        hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, true, true, 64, 1, false, true, 0, true>), grid, block, 0, s, d, group_m);
-      }
-      return 0;
+      if (o.mx_ph8 && conv_ph8_shape) return take(F_CONV_PH8_MX, t256, ky);
+      if (bn == 64 && d.ksplit <= 1 && d.M >= 512) return take(F_CONV_512x64_MX, gx512, 1);
+      return take(bn == 128 ? F_CONV_256x128_MX : F_CONV_256x64_MX, gx, gy);
     }
-    static const int conv32 = [] { const char* e = getenv("ASIS_CONV_BK32"); return e ? atoi(e) : 0; }();
-    // <= 64 output channels: 512x64 tile, 8 waves of 64x64 (1 KB of LDS fragment reads per MFMA; the 256x64 form's 32x64
-    // wave tiles need 1.5 KB and are LDS-bound), one workgroup per CU: +0.6 % on the step (ASIS_CONV_T512=0: old form)
-    static const int t512 = [] { const char* e = getenv("ASIS_CONV_T512"); return e ? atoi(e) : 1; }();
-    static const int cm16 = [] { const char* e = getenv("ASIS_CONV_M16"); return e ? atoi(e) : 0; }();  // 16x16x32 MFMAs in the split convs
-    // ASIS_CONV_8P (default 1): convolutions with whole 256-column tiles on the 8-phase 256x256x64 main loop (gemm_big.h):
-    // the long reductions of the decoder convs are where that loop is at its best (K = 9 * Cin * 3 parts)
-    static const int conv8p = [] { const char* e = getenv("ASIS_CONV_8P"); return e ? atoi(e) : 1; }();
-    if (d.conv && conv8p && d.N >= 256 && (d.N % 256 == 0 || d.N >= 1024) && d.batch == 1) {
-      dim3 g8(((d.M + 255) / 256) * ((d.N + 255) / 256), d.ksplit > 1 ? d.ksplit : 1);
-      hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, true, true, 64, 1, true, true>), g8, block, 0, s, d, group_m);
-      return 0;
-    }
-    if (d.conv && bn == 64 && t512 && d.ksplit <= 1 && d.M >= 512) {
-      dim3 g512(((d.M + 511) / 512) * ((d.N + 63) / 64), 1);
-      if (cm16) hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 2, 2, 2, 0, true, true, 64, 1, false, true>), g512, block, 0, s, d, group_m);
-      else hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 2, 2, 2, 0, true, true, 64, 1>), g512, block, 0, s, d, group_m);
-      return 0;
-    }
+    if (d.conv && o.conv_8p && conv_ph8_shape) return take(F_CONV_PH8_SPLIT, t256, ky);
+    if (d.conv && bn == 64 && o.conv_t512 && d.ksplit <= 1 && d.M >= 512) return take(o.conv_m16 ? F_CONV_512x64_SPLIT_M16 : F_CONV_512x64_SPLIT, gx512, 1);
     if (d.conv) {
-      if (conv32 && bn == 128) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true, 32, 4>), grid, block, 0, s, d, group_m);
-      else if (bn == 128 && cm16) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true, 64, 2, false, true>), grid, block, 0, s, d, group_m);
-      else if (bn == 128) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true>), grid, block, 0, s, d, group_m);
-      else hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, true, true>), grid, block, 0, s, d, group_m);
-    } else {
-      if (bn == 128) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, false, true>), grid, block, 0, s, d, group_m);
-      else hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, false, true>), grid, block, 0, s, d, group_m);
+      if (bn == 64) return take(F_CONV_256x64_SPLIT, gx, gy);
+      return take(o.conv_bk32 ? F_CONV_256x128_SPLIT_BK32 : o.conv_m16 ? F_CONV_256x128_SPLIT_M16 : F_CONV_256x128_SPLIT, gx, gy);
     }
-    return 0;
+    return take(bn == 128 ? F_BIG_256x128_SPLIT : F_BIG_256x64_SPLIT, gx, gy);
   }
-  static const int m16 = [] { const char* e = getenv("ASIS_GEMM_M16"); return e ? atoi(e) : 1; }();  // 16x16x32 MFMAs in the default dense form
-  // ASIS_GEMM_8P: 0 = never; 1 (default) = K >= 2048 (fc2 / its input gradient: 343 vs 476 us at 42348x1024x4096) and,
-  // since the phases run on 16x16x32 MFMAs (ASIS_GEMM_8P_M16: fc2 391 -> 350 us in isolation), the unbatched K >= 1024
-  // GEMMs too (in the step: qk 222 -> 214 us, proj 160 -> 139, fc1 457 -> 441, adapter projections 242 -> 216; +3.5 % on the
-  // step) — the batched ragged V^T GEMM lost there at first (66 vs 72 us: coarser tile quantisation) and wins since the form's
-  // 16-bit outputs are converted before the LDS transposition (+0.9 % on the step);
-  // (only when there are at least 128 of its 256x256 tiles: a launch that cannot fill the chip is better off with twice as
-  // many 256x128 tiles); 3 = K >= 2048 only (the round-1 rule); 2 = wherever the shape allows
-  static const int ph8 = [] { const char* e = getenv("ASIS_GEMM_8P"); return e ? atoi(e) : 1; }();
-  static const int ph8_mink = [] { const char* e = getenv("ASIS_GEMM_8P_MINK"); return e ? atoi(e) : 1024; }();  // lab: see above
-  if (ph8 && (ph8 == 2 || d.K >= 2048 || (ph8 == 1 && d.K >= ph8_mink && (int64_t)((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch >= 128)) && big_mode && !d.conv && !d.stats && d.K % 64 == 0 && d.M >= 256 && d.N >= 256) {
+  const bool dense_big = o.big && !d.conv && !d.stats && d.M >= 256;
+  if (o.ph8 && ph8_k(o.ph8_mink) && dense_big && d.K % 64 == 0 && d.N >= 256) {
     // 256x256x64 tile, 8-phase main loop (one workgroup per CU: 128 KB of LDS)
-    dim3 grid(((d.M + 255) / 256) * ((d.N + 255) / 256), d.batch), block(512);
-    // ASIS_GEMM_8P_M16 (default 1): the phases issue 16 v_mfma_f32_16x16x32 instead of 8 32x32x16 (same FLOP, higher clock)
-    static const int ph8_m16 = [] { const char* e = getenv("ASIS_GEMM_8P_M16"); return e ? atoi(e) : 1; }();
-    // ASIS_GEMM_8P_SLAB32=1 (lab): 16-bit outputs through the fp32 slab epilogue like the others
-    static const int ph8_slab32 = [] { const char* e = getenv("ASIS_GEMM_8P_SLAB32"); return e ? atoi(e) : 0; }();
-    const int group_m_f = group_m | (ph8_slab32 ? 0x10000 : 0);
-    if (ph8_m16) {
-      if (lnx) hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true, true, 1>), grid, block, 0, s, d, group_m);
-      else hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true, true>), grid, block, 0, s, d, group_m_f);
-      return 0;
-    }
-    hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true>), grid, block, 0, s, d, group_m);
-    return 0;
+    if (!ph8_m16) return take(F_PH8_M32, t256, d.batch);
+    if (lnx) return take(F_PH8_LN, t256, d.batch);
+    return take(F_PH8_M16, t256, d.batch, 512, o.ph8_slab32 ? 0x10000 : 0);
   }
-  if (big_mode && !d.conv && !d.stats && d.K % 32 == 0 && d.M >= 256 && d.N >= 128) {
+  if (dense_big && d.K % 32 == 0 && d.N >= 128) {
     // 256x128x32 tile, 3 LDS stages (72 KB) and <= 128 VGPRs: TWO workgroups per CU, so one workgroup's epilogue
     // (HBM-write bound) overlaps the other's K loop: +12-15 % over the 1-workgroup 256x256x64 / 256x128x64 forms
-    // on the fc1 shape (scripts/gemm_lab.hip).  big_mode 2/3 keep the older forms selectable for A/B runs.
-    const int bm = 256, bn = (big_mode == 2 && d.N >= 2048) ? 256 : 128;
-    dim3 grid(((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn), d.batch), block(512);
-    if (big_mode == 2 && bn == 256) hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2>), grid, block, 0, s, d, group_m);
-    else if (big_mode >= 2) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3>), grid, block, 0, s, d, group_m);
-    else if (m16) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, false, false, 32, 4, false, true>), grid, block, 0, s, d, group_m);
-    else hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, false, false, 32, 4>), grid, block, 0, s, d, group_m);
-    return 0;
+    // on the fc1 shape (scripts/gemm_lab.hip).
+    if (o.big == 2 && d.N >= 2048) return take(F_BIG_256x256, t256, d.batch);
+    return take(o.big >= 2 ? F_BIG_256x128_K64 : o.m16 ? F_BIG_256x128_M16 : F_BIG_256x128, tiles(256, 128), d.batch);
   }
   // implicit-GEMM convolution on the same kernel: K tiles must lie inside one tap, and BatchNorm statistics
   // come from the vectorised epilogue
-  if (big_mode && d.conv && d.Cin % BK == 0 && d.M >= 256 && d.N >= 32 && vec_ok && d.out_f32) {
-    const int bm = 256, bn = d.N > 64 ? 128 : 64;
+  if (o.big && d.conv && d.Cin % BK == 0 && d.M >= 256 && d.N >= 32 && vec_ok && d.out_f32) {
     if (d.ksplit > 1 && (d.stats || (d.KH * d.KW) % d.ksplit != 0 || d.res)) return ASIS_EINVAL;
-    dim3 grid(((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn), d.ksplit > 1 ? d.ksplit : 1), block(512);
-    static const int conv8p = [] { const char* e = getenv("ASIS_CONV_8P"); return e ? atoi(e) : 1; }();
-    if (conv8p && d.N >= 256 && (d.N % 256 == 0 || d.N >= 1024) && d.batch == 1) {
-      dim3 g8(((d.M + 255) / 256) * ((d.N + 255) / 256), d.ksplit > 1 ? d.ksplit : 1);
-      hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, true, false, 64, 1, true, true>), g8, block, 0, s, d, group_m);
-      return 0;
-    }
-    if (bn == 128) hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true>), grid, block, 0, s, d, group_m);
-    else hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, true>), grid, block, 0, s, d, group_m);
-    return 0;
+    if (o.conv_8p && conv_ph8_shape) return take(F_CONV_PH8, t256, ky);
+    return take(bn == 128 ? F_CONV_256x128 : F_CONV_256x64, tiles(256, bn), ky);
   }
   if (d.ksplit > 1) return ASIS_EINVAL;  // K parts exist on the large-tile conv forms only
-  const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
-  dim3 grid(tiles_m * tiles_n, d.batch), block(NTHREADS);
-  if (d.conv)
-    hipLaunchKernelGGL((gemm_kernel<T, true>), grid, block, 0, s, d);
-  else
-    hipLaunchKernelGGL((gemm_kernel<T, false>), grid, block, 0, s, d);
-  return 0;
+  return take(d.conv ? F_GENERIC_CONV : F_GENERIC, tiles(BM, BN), d.batch, NTHREADS);
 }
 
-}  // namespace
-
-extern "C" int asis_gemm_tiles_m(int M) { return (M + BM - 1) / BM; }
-
-extern "C" int asis_gemm_set_option(const char* name, int value) {
-  ASIS_REQUIRE(name != nullptr, "asis_gemm_set_option: null name");
-  if (strcmp(name, "p8") == 0) { g_gemm_p8 = value; return ASIS_OK; }
-  ASIS_FAIL(ASIS_EINVAL, "asis_gemm_set_option: unknown option '%s'", name);
+// One launch per form: the template instantiations of this file.
+template <typename T>
+void launch(hipStream_t s, const asis_gemm_desc& d, const GemmPlan& p) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  const int gm = p.group_m;
+  switch (p.form) {
+    case F_P8: hipLaunchKernelGGL((gemm_p8_kernel<T, 0>), grid, block, 0, s, d, gm); break;
+    case F_P8_LN: hipLaunchKernelGGL((gemm_p8_kernel<T, 1>), grid, block, 0, s, d, gm); break;
+    case F_PH8_M16: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true, true>), grid, block, 0, s, d, gm); break;
+    case F_PH8_M32: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true>), grid, block, 0, s, d, gm); break;
+    case F_PH8_LN: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, false, 64, 1, true, true, 1>), grid, block, 0, s, d, gm); break;
+    case F_PH8_MX: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, false, true, 64, 1, true, true, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_BIG_256x128_M16: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, false, false, 32, 4, false, true>), grid, block, 0, s, d, gm); break;
+    case F_BIG_256x128: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, false, false, 32, 4>), grid, block, 0, s, d, gm); break;
+    case F_BIG_256x128_K64: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3>), grid, block, 0, s, d, gm); break;
+    case F_BIG_256x256: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2>), grid, block, 0, s, d, gm); break;
+    case F_BIG_256x128_SPLIT: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, false, true>), grid, block, 0, s, d, gm); break;
+    case F_BIG_256x64_SPLIT: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, false, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_PH8: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, true, false, 64, 1, true, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x128: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x64: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_PH8_SPLIT: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, true, true, 64, 1, true, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_512x64_SPLIT: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 2, 2, 2, 0, true, true, 64, 1>), grid, block, 0, s, d, gm); break;
+    case F_CONV_512x64_SPLIT_M16: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 2, 2, 2, 0, true, true, 64, 1, false, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x128_SPLIT: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x128_SPLIT_M16: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true, 64, 2, false, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x128_SPLIT_BK32: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true, 32, 4>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x64_SPLIT: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, true, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_PH8_MX: hipLaunchKernelGGL((gemm_big_kernel<T, 2, 4, 4, 2, 2, 0, true, true, 64, 1, true, true, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_512x64_MX: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 2, 2, 2, 0, true, true, 64, 1, false, true, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x128_MX: hipLaunchKernelGGL((gemm_big_kernel<T, 4, 2, 2, 2, 3, 0, true, true, 64, 1, false, true, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_CONV_256x64_MX: hipLaunchKernelGGL((gemm_big_kernel<T, 8, 1, 1, 2, 3, 0, true, true, 64, 1, false, true, 0, true>), grid, block, 0, s, d, gm); break;
+    case F_GENERIC: hipLaunchKernelGGL((gemm_kernel<T, false>), grid, block, 0, s, d); break;
+    case F_GENERIC_CONV: hipLaunchKernelGGL((gemm_kernel<T, true>), grid, block, 0, s, d); break;
+  }
 }
 
-
-extern "C" int asis_gemm(void* stream, const asis_gemm_desc* dp) {
+// The argument checks and the plan of both entry points; *out = the descriptor as the kernels take it (batch >= 1).
+int gemm_prepare(const asis_gemm_desc* dp, asis_gemm_desc* out, GemmPlan* p) {
   ASIS_REQUIRE(dp != nullptr, "asis_gemm: null descriptor");
-  asis_gemm_desc d = *dp;
+  asis_gemm_desc& d = *out;
+  d = *dp;
   ASIS_REQUIRE(d.A && d.B && d.C, "asis_gemm: null operand pointer");
   ASIS_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0, "asis_gemm: M,N,K must be positive (got %d,%d,%d)", d.M, d.N, d.K);
   ASIS_DT_OK(d.dtype, "asis_gemm");
@@ -455,17 +465,47 @@ extern "C" int asis_gemm(void* stream, const asis_gemm_desc* dp) {
   if (d.rowstats) ASIS_REQUIRE(d.N % 64 == 0, "asis_gemm: rowstats need N %% 64 == 0 (N = %d)", (int)d.N);
   const int64_t tiles = (int64_t)asis_cdiv(d.M, BM) * asis_cdiv(d.N, BN);
   ASIS_REQUIRE(tiles < (1ll << 31), "asis_gemm: too many tiles");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   ASIS_REQUIRE(!d.conv || (d.A_lo == nullptr) == (d.B_lo == nullptr), "asis_gemm: a split convolution needs both A_lo and B_lo");
   ASIS_REQUIRE((!d.A_lo || asis_aligned16(d.A_lo)) && (!d.B_lo || asis_aligned16(d.B_lo)), "asis_gemm: split halves must be 16-byte aligned");
-  int rc = 0;  // launch(): nonzero = no kernel form takes this descriptor
-  if (int bad = asis_dispatch16(d.dtype, "asis_gemm", [&](auto t) { rc = launch<decltype(t)>(s, d); })) return bad;
+  const int rc = gemm_plan(d, gemm_opts(), p);  // nonzero = no kernel form takes this descriptor
   if (rc != 0 && d.act == ASIS_ACT_SILU_MUL)
     ASIS_FAIL(ASIS_EINVAL, "asis_gemm: ASIS_ACT_SILU_MUL needs a dense 16-bit-output launch on the 8-phase form (include/asis_hip.h: K %% 64 == 0, "
                            "M >= 256, N >= 256, N %% 32 == 0, ldc %% 8 == 0, plain or MX split operands, bias only)");
   if (rc != 0) ASIS_FAIL(ASIS_EINVAL, "asis_gemm: split-precision operands / ASIS_ACT_GELU_GRAD / ksplit need the large-tile path (K %% 64 "
                                         "== 0 (GELU_GRAD: 32), M >= 256, N >= 32 (128), N and ldc multiples of 4, fp32 output for "
                                         "split; conv: Cin %% 64 == 0)");
+  return ASIS_OK;
+}
+
+}  // namespace
+
+extern "C" int asis_gemm_tiles_m(int M) { return (M + BM - 1) / BM; }
+
+extern "C" int asis_gemm_set_option(const char* name, int value) {
+  ASIS_REQUIRE(name != nullptr, "asis_gemm_set_option: null name");
+  if (strcmp(name, "p8") == 0) { gemm_opts().p8 = value; return ASIS_OK; }
+  ASIS_FAIL(ASIS_EINVAL, "asis_gemm_set_option: unknown option '%s'", name);
+}
+
+extern "C" int asis_gemm_plan(const asis_gemm_desc* dp, int* form, int* grid_x, int* grid_y, int* block) {
+  asis_gemm_desc d;
+  GemmPlan p;
+  if (int bad = gemm_prepare(dp, &d, &p)) return bad;
+  if (form) *form = p.form;
+  if (grid_x) *grid_x = p.grid_x;
+  if (grid_y) *grid_y = p.grid_y;
+  if (block) *block = p.block;
+  return ASIS_OK;
+}
+
+extern "C" const char* asis_gemm_form_name(int form) { return form >= 0 && form < F_COUNT ? kFormNames[form] : "?"; }
+
+extern "C" int asis_gemm(void* stream, const asis_gemm_desc* dp) {
+  asis_gemm_desc d;
+  GemmPlan p;
+  if (int bad = gemm_prepare(dp, &d, &p)) return bad;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int bad = asis_dispatch16(d.dtype, "asis_gemm", [&](auto t) { launch<decltype(t)>(s, d, p); })) return bad;
   ASIS_CHECK_LAUNCH("asis_gemm");
   return ASIS_OK;
 }

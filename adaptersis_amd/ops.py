@@ -7,6 +7,7 @@ tensors allocated with ``torch.empty``.  A CPU tensor, a missing library or a ba
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Optional
 
@@ -66,6 +67,12 @@ def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return t
 
 
+def _split_shape_ok(M: int, N: int, K: int) -> bool:
+    """shapes whose split-precision product runs as ONE launch over the virtual 2K / 3K reduction (large-tile kernels,
+    include/asis_hip.h: A_lo / B_lo; convolutions: K = Cin); the callers' alternative is three accumulate passes"""
+    return K % 64 == 0 and M >= 256 and N >= 32 and N % 4 == 0
+
+
 def _gemm_desc(a: torch.Tensor, b: torch.Tensor, *, out: Optional[torch.Tensor] = None, out_f32: bool = False,
                bias_n: Optional[torch.Tensor] = None, bias_m: Optional[torch.Tensor] = None,
                scale_n: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None, act: int = ACT_NONE,
@@ -117,7 +124,7 @@ def _gemm_desc(a: torch.Tensor, b: torch.Tensor, *, out: Optional[torch.Tensor] 
             raise ValueError("gemm: aux must be a 16-bit [M, N] matrix of the operand dtype")
         d.aux, d.ld_aux = aux.data_ptr(), aux.stride(-2)
     flops = 2.0 * batch * M * N * K
-    if (a_lo is None) != (b_lo is None) and not (K % 64 == 0 and M >= 256 and N >= 32 and N % 4 == 0 and out.stride(-2) % 4 == 0):
+    if (a_lo is None) != (b_lo is None) and not (_split_shape_ok(M, N, K) and out.stride(-2) % 4 == 0):
         a_lo = b_lo = None   # one-sided (weight) split is an optional refinement: shapes off the large-tile path run plain
     if a_lo is not None:
         if a_lo.stride() != a.stride():
@@ -171,9 +178,56 @@ def gemm_tiles_m(M: int) -> int:
     return lib().asis_gemm_tiles_m(int(M))
 
 
+def _plan(d: GemmDesc):
+    """``gemm_plan``, or None where ``asis_gemm`` refuses ``d``"""
+    form, gx, gy = C.c_int(), C.c_int(), C.c_int()
+    if lib().asis_gemm_plan(C.byref(d), C.byref(form), C.byref(gx), C.byref(gy), None) != 0:
+        return None
+    return lib().asis_gemm_form_name(form.value).decode(), gx.value, gy.value
+
+
+def gemm_plan(d: GemmDesc):
+    """-> (form name, grid_x, grid_y): the kernel form ``asis_gemm`` would launch for ``d`` and its grid (include/asis_hip.h:
+    asis_gemm_plan); ValueError where it refuses ``d``.  Launches nothing and needs no GPU."""
+    return _plan(d) or check(_lib.ASIS_EINVAL, "asis_gemm_plan")
+
+
+_PRESENT = 1 << 20   # a 16-byte-aligned placeholder address: the plan only tests pointers for null and alignment
+
+
+@functools.lru_cache(maxsize=None)
+def _shape_plan(M: int, N: int, K: int, batch: int = 1, act: int = ACT_NONE, out_f32: bool = False, split: bool = False,
+                mx: bool = False, ln: bool = False, producer: bool = False, conv3x3: bool = False):
+    """``gemm_plan`` (None: refused) of a contiguous launch of this shape (lda = ldb = K, ldc = N, or N / 2 for SwiGLU) with the
+    named operand fields present: what the shape predicates below ask instead of repeating the dispatcher's rules.  ``producer``:
+    C_lo, res16 and (N in whole 64-column groups) rowstats; ``conv3x3``: K = 9 Cin, stride 1, pad 1, M one-pixel images.  The
+    answers follow the dispatcher's switches, the run-time ``"p8"`` option included: ``gemm_set_option`` empties this cache.  A
+    first refused query leaves its message in ``asis_last_error`` (read only after a call that failed, so nobody sees it)."""
+    d = GemmDesc(A=_PRESENT, B=_PRESENT, C=_PRESENT, lda=K, ldb=K, ldc=N // 2 if act == ACT_SILU_MUL else N, batch=batch, M=M, N=N,
+                 K=K, act=act, out_f32=int(out_f32), dtype=_lib.ASIS_F16)
+    if split:
+        d.A_lo = d.B_lo = _PRESENT
+    if mx:
+        d.mx_amax_a = d.mx_amax_b = _PRESENT
+    if ln:
+        d.ln_mr = d.ln_cs = _PRESENT
+    if producer:
+        d.C_lo = d.res16 = d.res16_lo = _PRESENT
+        d.ldr16, d.rowstats = N, (_PRESENT if N % 64 == 0 else None)
+    if conv3x3:
+        d.conv, d.B_, d.H, d.W, d.OH, d.OW, d.Cin, d.KH, d.KW, d.stride, d.pad = 1, M, 1, 1, 1, 1, K // 9, 3, 3, 1, 1
+    return _plan(d)
+
+
+def conv3x3_plan(P: int, Cout: int, Cin: int, split: bool):
+    """``gemm_plan`` of a 3x3 convolution with P output pixels and an fp32 output (None: refused)"""
+    return _shape_plan(P, Cout, 9 * Cin, out_f32=True, split=split, conv3x3=True)
+
+
 def gemm_set_option(name: str, value: int) -> None:
     """Run-time dispatch switch of ``asis_gemm`` (``"p8"``: the persistent 8-phase form, include/asis_hip.h)."""
     check(lib().asis_gemm_set_option(name.encode(), int(value)), "asis_gemm_set_option")
+    _shape_plan.cache_clear()
 
 
 def conv_gemm(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, stride: int, pad: int, *,
@@ -227,7 +281,14 @@ def conv_gemm(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, st
     return out
 
 
-_FUSED_SPLIT = os.environ.get("ASIS_GEMM_BIG", "1") != "0" and os.environ.get("ASIS_SPLIT_FUSED", "1") != "0"
+_SPLIT_FUSED = os.environ.get("ASIS_SPLIT_FUSED", "1") != "0"   # 0: split-precision products as three accumulate passes
+
+
+def _fused_split(M: int, N: int, K: int) -> bool:
+    """``_split_shape_ok`` and the one-launch path is there: the switch above, and the large-tile kernels (a minimal split launch plans)"""
+    return _SPLIT_FUSED and _split_shape_ok(M, N, K) and _shape_plan(256, 32, 64, out_f32=True, split=True) is not None
+
+
 # narrow MX convolutions (64 / 128 output channels) on the halo-tile kernel (csrc/convhalo.hip): 256 -> 128 at 168^2 544 vs 577 us,
 # 128 -> 64 at 336^2 540 vs 692 us against the implicit-GEMM form (scripts/bench_conv_halo.py, profiles/r04_conv_halo_ab.txt);
 # ASIS_CONV_HALO=0: implicit GEMM
@@ -244,7 +305,7 @@ def conv_gemm_split(x_hi, x_lo, w_hi, w_lo, KH: int, KW: int, stride: int, pad: 
     Bn, H, W, Cin = x_hi.shape
     OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
     Cout = w_hi.shape[0]
-    if Cin % 64 == 0 and Bn * OH * OW >= 256 and Cout >= 32 and Cout % 4 == 0 and _FUSED_SPLIT:
+    if _fused_split(Bn * OH * OW, Cout, Cin):
         return conv_gemm(x_hi, w_hi, KH, KW, stride, pad, bias_n=bias_n, stats=stats, x_lo=x_lo, w_lo=w_lo, ksplit=ksplit, mx=mx)
     if mx is not None:
         raise ValueError("conv_gemm_split: MX operands need the fused large-tile path (mx_conv_ok)")
@@ -282,7 +343,7 @@ def conv3x3_halo_mx(x_hi, x_mx, w_hi, w_mx, mx, *, bias_n=None, want_stats: bool
 def gemm_split(a_hi, a_lo, b_hi, b_lo, *, out: torch.Tensor, bias_n=None):
     """Split-precision ``out = (a_hi + a_lo) @ (b_hi + b_lo).T + bias`` into an fp32 ``out``."""
     M, K, N = a_hi.shape[-2], a_hi.shape[-1], b_hi.shape[-2]
-    if K % 64 == 0 and M >= 256 and N >= 32 and N % 4 == 0 and _FUSED_SPLIT:
+    if _fused_split(M, N, K):
         return gemm(a_hi, b_hi, out=out, bias_n=bias_n, a_lo=a_lo, b_lo=b_lo)
     gemm(a_hi, b_hi, out=out, bias_n=bias_n)
     gemm(a_lo, b_hi, out=out, res=out)
@@ -291,15 +352,11 @@ def gemm_split(a_hi, a_lo, b_hi, b_lo, *, out: torch.Tensor, bias_n=None):
 
 
 def ln_fold_supported(M: int, N: int, K: int, batch: int = 1, producer: bool = False) -> bool:
-    """True when ``asis_gemm`` dispatches this dense shape to a kernel that implements the LayerNorm-fold epilogue fields:
-    consumers (``ln=``) the persistent 8-phase kernel or the one-tile-per-workgroup 8-phase form, producers (``out_lo`` /
-    ``rowstats`` / ``res16``) the latter only.  Mirrors csrc/gemm.hip:launch."""
-    if M < 256 or N < 256 or K % 64 or K < 128 or N % 8:
-        return False
-    tiles = ((M + 255) // 256) * ((N + 255) // 256)
-    if not producer and batch == 1 and tiles >= 256 and K <= 2048:
-        return True
-    return K >= 2048 or (K >= 1024 and tiles * batch >= 128)
+    """True when ``asis_gemm`` dispatches this dense shape to a kernel that implements the LayerNorm-fold epilogue fields (it
+    refuses them elsewhere): consumers (``ln=``) the persistent 8-phase kernel or the one-tile-per-workgroup 8-phase form,
+    producers (``out_lo`` / ``rowstats`` / ``res16``, unbatched) the latter only.  Follows the dispatcher's switches, the
+    run-time ``"p8"`` option included (after ``gemm_set_option("p8", 0)`` a K = 512 consumer is unsupported, as it is in ``asis_gemm``)."""
+    return _shape_plan(M, N, K, batch=1 if producer else batch, ln=not producer, producer=producer) is not None
 
 
 def ln_stats_finalize(rowstats: torch.Tensor, D: int, eps: float = 1e-6) -> torch.Tensor:
@@ -911,7 +968,7 @@ def bn_relu_maxpool(x: torch.Tensor, scale, shift, dtype: torch.dtype, split: bo
 
 def mx_conv_ok(P: int, Cin: int, Cout: int) -> bool:
     """a split 3x3 convolution with P output pixels can take MX lo operands (csrc/gemm.hip: the fused large-tile conv forms)"""
-    return Cin % 64 == 0 and P >= 256 and Cout >= 32 and Cout % 4 == 0 and _FUSED_SPLIT
+    return _fused_split(P, Cout, Cin)
 
 
 def absmax_f32(x: torch.Tensor, amax: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1090,9 +1147,9 @@ def swiglu_rows(Hd: int, device) -> torch.Tensor:
 
 
 def swiglu_fused_ok(M: int, Hd: int, K: int, split: bool, mx: bool) -> bool:
-    """shapes / operand forms the SwiGLU epilogue covers (include/asis_hip.h: ASIS_ACT_SILU_MUL); ASIS_SWIGLU_FUSED=0: never"""
-    return (_SWIGLU_FUSED and Hd % 16 == 0 and 2 * Hd >= 256 and M >= 256 and K % 64 == 0 and (mx or not split)
-            and os.environ.get("ASIS_GEMM_BIG", "1") != "0" and os.environ.get("ASIS_GEMM_8P_M16", "1") != "0")
+    """shapes / operand forms the SwiGLU epilogue covers: ``asis_gemm`` takes an ASIS_ACT_SILU_MUL launch of them (include/asis_hip.h),
+    under the dispatcher's switches as they stand; ASIS_SWIGLU_FUSED=0: never"""
+    return _SWIGLU_FUSED and _shape_plan(M, 2 * Hd, K, act=ACT_SILU_MUL, split=split, mx=mx) is not None
 
 
 _SWIGLU_FUSED = os.environ.get("ASIS_SWIGLU_FUSED", "1") not in ("0", "")

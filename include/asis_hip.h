@@ -181,8 +181,32 @@ int asis_mx_from_pair(void* stream, int dtype, const void* hi, const void* lo, i
 /* run-time dispatch switches of asis_gemm (same meaning as the environment variable read at first use):
  *   "p8" (ASIS_GEMM_P8): 1 = dense launches with at least one 256x256 tile per CU run on the persistent 8-phase kernel
  *   (csrc/gemm_p8.h) when K <= 2048, 2 = any K and from 16 tiles on, 3 = any K, 0 = never (one workgroup per tile,
- *   csrc/gemm_big.h); "noepi" (ASIS_GEMM_NOEPI, lab): 1 = main loops only, results are wrong.  Unknown name: ASIS_EINVAL. */
+ *   csrc/gemm_big.h).  Unknown name: ASIS_EINVAL. */
 int asis_gemm_set_option(const char* name, int value);
+/* The kernel form and launch geometry asis_gemm would use for *d, without launching: the same argument checks and the same plan
+ * (ASIS_EINVAL and the same message where asis_gemm refuses); needs no GPU, reads no memory behind the descriptor's pointers
+ * (null / alignment tests only).  form: an index for asis_gemm_form_name; grid_x, grid_y, block: workgroups and threads (any
+ * output pointer may be NULL).  The forms, in the order the dispatcher tries them (csrc/gemm.hip: gemm_plan; the lab switches
+ * are the fields of GemmOpts there):
+ *   ph8_m16 / ph8_mx   ASIS_ACT_SILU_MUL goes straight to the 8-phase 256x256x64 form (one tile per workgroup, 16x16x32 MFMAs),
+ *                      ph8_mx with MX split operands; no other form has that epilogue
+ *   p8, p8_ln          persistent 8-phase kernel: dense, unbatched, >= 256 tiles of 256x256, 128 <= K (x K parts) <= 2048, 16-byte
+ *                      aligned C / res / bias_n / scale_n; p8_ln with the LayerNorm-fold consumer fields (ln_mr / ln_cs per row)
+ *   ph8_ln             C_lo / rowstats / res16 / ln_mr off the persistent kernel: the 8-phase form by its K rule below (no split
+ *                      operands; producers unbatched, no activation), refused elsewhere
+ *   split operands     ph8_mx (dense MX: N >= 256, unbatched); conv_ph8_mx, conv_512x64_mx, conv_256x128_mx, conv_256x64_mx (MX
+ *                      convolutions); conv_ph8_split, conv_512x64_split(_m16), conv_256x128_split(_m16, _bk32),
+ *                      conv_256x64_split; big_256x128_split, big_256x64_split (dense).  K % 64 == 0, M >= 256, N >= 32, N and ldc
+ *                      multiples of 4 (conv: Cin % 64 == 0, fp32 output, both halves), refused elsewhere.  conv_ph8_*: N >= 256
+ *                      in whole 256-column tiles (or N >= 1024); 512x64: N <= 64, M >= 512, no K parts; else 128 columns (N > 64) or 64
+ *   ph8_m16, ph8_m32   dense, K % 64 == 0, M >= 256, N >= 256, and K >= 2048 or (K >= 1024 and >= 128 tiles x batch); m32 = 32x32x16 MFMAs (lab)
+ *   big_256x128_m16    dense, K % 32 == 0, M >= 256, N >= 128: 256x128x32 tile, two workgroups per CU (also ASIS_ACT_GELU_GRAD, which
+ *                      only these and p8 implement); big_256x128, big_256x128_k64, big_256x256: its lab variants
+ *   conv_ph8, conv_256x128, conv_256x64   plain convolutions, Cin % 64 == 0, M >= 256, N >= 32, fp32 output (tile rule as for split);
+ *                      ksplit > 1 exists on the conv_* forms only
+ *   generic, generic_conv   everything else: the 128x128x64 register-staged kernel */
+int asis_gemm_plan(const asis_gemm_desc* d, int* form, int* grid_x, int* grid_y, int* block);
+const char* asis_gemm_form_name(int form);
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm over the last dim, fp32 statistics, eps inside sqrt, biased variance
