@@ -821,6 +821,28 @@ class SegEngine(nn.Module):
             enc.update_running_stats = upd
         return ops.predict_mask(logits, tuple(inp.shape[-2:]) if size is None else size, **kw)
 
+    @torch.no_grad()
+    def predict_views(self, inps, flips, size, **kw):
+        """Test-time augmentation: masks at ``size`` = (H, W) from several views of one batch.  ``inps[k]`` is float [B,3,S_k,S_k]
+        as validation feeds it (the sizes may differ; a mirrored view is given mirrored), ``flips[k]`` tells whether view k is
+        mirrored.  ``eval_logits`` runs once per view under the guard of ``predict`` (decoder in eval mode, the encoder's running
+        statistics not updated, both restored afterwards), so the encoder's BatchNorm normalises every view with that view's own
+        batch statistics; one ``ops.predict_mask_views`` call then averages the class probabilities of the views at native size
+        (keywords as there: ``encode``, ``confidence``, ``frames`` / ``palette`` / ``alpha``, ``target`` / ``lut``)."""
+        inps, flips = list(inps), list(flips)
+        if len(inps) != len(flips):
+            raise ValueError(f"predict_views: {len(inps)} inputs and {len(flips)} flips")
+        enc = self.backbone_encoder
+        was, upd = self.seg_decoder.training, enc.update_running_stats
+        self.seg_decoder.eval()
+        enc.update_running_stats = False
+        try:
+            logits = [self.eval_logits(inp) for inp in inps]
+        finally:
+            self.seg_decoder.train(was)
+            enc.update_running_stats = upd
+        return ops.predict_mask_views(logits, size, flips=flips, **kw)
+
 
 def make_vit_bucket(model, blocks_per_bucket: int, process_group, momentum: bool = False, min_first_blocks: int = 0,
                     compress: Optional[str] = None):

@@ -1739,6 +1739,37 @@ def _u8_table(t, shape, name: str, dev, op: str = "predict_mask") -> torch.Tenso
     return t.to(dev).contiguous()
 
 
+def _predict_outputs(op: str, B: int, Cc: int, size, dev, encode, frames, palette, alpha, target, lut):
+    """The checks and tables ``predict_mask`` and ``predict_mask_views`` share -> (H, W, enc, mask, pal, alp, overlay, lut, counts)."""
+    if not 1 <= Cc <= 16:
+        raise ValueError(f"{op}: logits have C={Cc} classes, supported 1..16")
+    if isinstance(size, int):
+        size = (size, size)
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError(f"{op}: size must be a positive int or (H, W), got {size!r}")
+    H, W = int(size[0]), int(size[1])
+    from .tools import frame_resize as _fr
+    enc = _u8_table(_fr.ENCODE_INDEX[:Cc] if encode is None else encode, (Cc,), "encode", dev, op)
+    if frames is None and (palette is not None or alpha is not None):
+        raise ValueError(f"{op}: palette / alpha given without frames")
+    if (target is None) != (lut is None):
+        raise ValueError(f"{op}: target (raw masks) and lut (their label table) go together")
+    mask = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    overlay = counts = pal = alp = None
+    if frames is not None:
+        if frames.dtype != torch.uint8 or tuple(frames.shape) != (B, H, W, 3) or not frames.is_contiguous():
+            raise ValueError(f"{op}: frames must be contiguous uint8 [B,H,W,3] = {[B, H, W, 3]}, got {list(frames.shape)}")
+        pal = _u8_table(_fr.default_palette(Cc) if palette is None else palette, (Cc, 3), "palette", dev, op)
+        alp = _u8_table(_fr.default_alpha(Cc) if alpha is None else alpha, (Cc,), "alpha", dev, op)
+        overlay = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)
+    if target is not None:
+        if target.dtype != torch.uint8 or tuple(target.shape) != (B, H, W) or not target.is_contiguous():
+            raise ValueError(f"{op}: target must be contiguous uint8 [B,H,W] = {[B, H, W]}, got {list(target.shape)}")
+        lut = _u8_table(lut, (256,), "lut", dev, op)
+        counts = torch.zeros((Cc, 3), device=dev, dtype=torch.int64)
+    return H, W, enc, mask, pal, alp, overlay, lut, counts
+
+
 def predict_mask(logits: torch.Tensor, size, encode=None, *, frames: Optional[torch.Tensor] = None, palette=None, alpha=None,
                  target: Optional[torch.Tensor] = None, lut=None):
     """Native-size masks from the decoder's logits in one pass (csrc/predict.hip): fp32 NHWC [B,h,w,C] -> uint8 [B,H,W] =
@@ -1754,36 +1785,60 @@ def predict_mask(logits: torch.Tensor, size, encode=None, *, frames: Optional[to
     if logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError("predict_mask: logits must be a contiguous float32 NHWC tensor [B,h,w,C]")
     B, h, w, Cc = logits.shape
-    if not 1 <= Cc <= 16:
-        raise ValueError(f"predict_mask: logits have C={Cc} classes, supported 1..16")
-    if isinstance(size, int):
-        size = (size, size)
-    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
-        raise ValueError(f"predict_mask: size must be a positive int or (H, W), got {size!r}")
-    H, W = int(size[0]), int(size[1])
-    dev = logits.device
-    from .tools import frame_resize as _fr
-    enc = _u8_table(_fr.ENCODE_INDEX[:Cc] if encode is None else encode, (Cc,), "encode", dev)
-    if frames is None and (palette is not None or alpha is not None):
-        raise ValueError("predict_mask: palette / alpha given without frames")
-    if (target is None) != (lut is None):
-        raise ValueError("predict_mask: target (raw masks) and lut (their label table) go together")
-    mask = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
-    overlay = counts = pal = alp = None
-    if frames is not None:
-        if frames.dtype != torch.uint8 or tuple(frames.shape) != (B, H, W, 3) or not frames.is_contiguous():
-            raise ValueError(f"predict_mask: frames must be contiguous uint8 [B,H,W,3] = {[B, H, W, 3]}, got {list(frames.shape)}")
-        pal = _u8_table(_fr.default_palette(Cc) if palette is None else palette, (Cc, 3), "palette", dev)
-        alp = _u8_table(_fr.default_alpha(Cc) if alpha is None else alpha, (Cc,), "alpha", dev)
-        overlay = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)
-    if target is not None:
-        if target.dtype != torch.uint8 or tuple(target.shape) != (B, H, W) or not target.is_contiguous():
-            raise ValueError(f"predict_mask: target must be contiguous uint8 [B,H,W] = {[B, H, W]}, got {list(target.shape)}")
-        lut = _u8_table(lut, (256,), "lut", dev)
-        counts = torch.zeros((Cc, 3), device=dev, dtype=torch.int64)
+    H, W, enc, mask, pal, alp, overlay, lut, counts = _predict_outputs("predict_mask", B, Cc, size, logits.device, encode, frames,
+                                                                       palette, alpha, target, lut)
     check(lib().asis_predict_mask(_stream(), logits.data_ptr(), B, h, w, Cc, H, W, enc.data_ptr(), mask.data_ptr(), _p(frames),
                                   _p(pal), _p(alp), _p(overlay), _p(target), _p(lut), _p(counts)), "asis_predict_mask")
     out = (mask,) + ((overlay,) if overlay is not None else ()) + ((counts,) if counts is not None else ())
+    return mask if len(out) == 1 else out
+
+
+PREDICT_MAX_VIEWS = 8
+
+
+def predict_mask_views(logits, size, encode=None, *, flips=None, confidence: bool = False, frames: Optional[torch.Tensor] = None,
+                       palette=None, alpha=None, target: Optional[torch.Tensor] = None, lut=None):
+    """Test-time augmentation in one pass (csrc/predict.hip): ``logits`` = 1..8 views of one batch, each a contiguous fp32 NHWC map
+    [B,h_k,w_k,C] of its own size; ``flips[k]`` true = view k was predicted from the mirrored frame (None = no view is).  Per native
+    pixel and view, in view order: the bilinear samples of ``predict_mask`` (a mirrored view is read through mirrored columns: bit
+    for bit the result of the un-mirrored map ``v.flip(2)``), a softmax over the classes in fp32, and the sum of the
+    probabilities; -> uint8 [B,H,W] = ``encode[argmax_c sum]``, ties to the lowest class.  No [B,H,W,C] map is written however
+    many views there are.  ``confidence=True`` -> also uint8 [B,H,W] = floor(255 * mean probability of the chosen class + 0.5).
+    ``size``, ``encode``, ``frames`` / ``palette`` / ``alpha`` and ``target`` / ``lut`` as in ``predict_mask``.
+    -> mask, or (mask[, confidence][, overlay][, counts])."""
+    import ctypes
+    op = "predict_mask_views"
+    if torch.is_tensor(logits) or not isinstance(logits, (list, tuple)):
+        raise ValueError(f"{op}: logits must be a list of 1..{PREDICT_MAX_VIEWS} NHWC tensors, got {type(logits).__name__}")
+    K = len(logits)
+    if not 1 <= K <= PREDICT_MAX_VIEWS:
+        raise ValueError(f"{op}: logits holds {K} views, supported 1..{PREDICT_MAX_VIEWS}")
+    flips = [False] * K if flips is None else [bool(f) for f in flips]
+    if len(flips) != K:
+        raise ValueError(f"{op}: flips has {len(flips)} entries for {K} views in logits")
+    for k, v in enumerate(logits):
+        if not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.float32 or not v.is_contiguous():
+            raise ValueError(f"{op}: logits[{k}] must be a contiguous float32 NHWC tensor [B,h,w,C]")
+        if v.shape[0] != logits[0].shape[0] or v.shape[3] != logits[0].shape[3]:
+            raise ValueError(f"{op}: logits[{k}] is {list(v.shape)}, logits[0] {list(logits[0].shape)}: every view has the same "
+                             "B and C")
+        if v.device != logits[0].device:
+            raise ValueError(f"{op}: logits[{k}] on {v.device}, logits[0] on {logits[0].device}")
+    _dev(logits[0], frames, target)
+    B, Cc = int(logits[0].shape[0]), int(logits[0].shape[3])
+    dev = logits[0].device
+    H, W, enc, mask, pal, alp, overlay, lut, counts = _predict_outputs(op, B, Cc, size, dev, encode, frames, palette, alpha, target,
+                                                                       lut)
+    conf = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if confidence else None
+    ptrs = (ctypes.c_void_p * K)(*[v.data_ptr() for v in logits])
+    hs = (ctypes.c_int * K)(*[int(v.shape[1]) for v in logits])
+    ws = (ctypes.c_int * K)(*[int(v.shape[2]) for v in logits])
+    fl = (ctypes.c_int * K)(*[int(f) for f in flips])
+    check(lib().asis_predict_mask_views(_stream(), ptrs, hs, ws, fl, K, B, Cc, H, W, enc.data_ptr(), mask.data_ptr(), _p(conf),
+                                        _p(frames), _p(pal), _p(alp), _p(overlay), _p(target), _p(lut), _p(counts)),
+          "asis_predict_mask_views")
+    out = ((mask,) + ((conf,) if conf is not None else ()) + ((overlay,) if overlay is not None else ())
+           + ((counts,) if counts is not None else ()))
     return mask if len(out) == 1 else out
 
 

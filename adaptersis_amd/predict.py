@@ -27,6 +27,15 @@ checkpoints of ``--train_adapters --train_encoder`` runs (all three modules save
 ``train_seg`` and passes that ``--seed`` here (modules are built in the same order, ``train.build_modules``; a warning names
 what is drawn).
 
+Test-time augmentation (``--tta_flip``, ``--tta_sizes S [S ...]``): every frame is predicted at each size of ``--tta_sizes``
+(default: ``--imsize`` alone) and, with ``--tta_flip``, also mirrored at each; ``plan_views`` fixes the order.  The class
+probabilities of the views are averaged at native size and the mask is taken from the average, in one fused pass
+(``SegEngine.predict_views``, ``ops.predict_mask_views``); ``--confidence`` also writes ``<stem>_conf.png`` (mode ``L``: 255 times
+the mean probability of the chosen class, rounded).  Each view is its own forward pass: the encoder's BatchNorm normalises each
+view with that view's batch statistics, so the views of a frame differ by more than the resize and the mirror, and a frame's mask
+still depends on the batch it is predicted in.  Without any of the three flags the tool calls ``SegEngine.predict`` and writes
+exactly the files it wrote before they existed; ``metrics.json`` holds ``"views": [[size, flip], ...]`` only when views were used.
+
 Single process, single GPU: prediction is not sharded over ranks.
 """
 from __future__ import annotations
@@ -48,6 +57,7 @@ IMAGE_EXT = (".png", ".jpg", ".bmp")
 DATASETS = ("endovis2017", "endovis2018", "autolapro", "robomis")
 MAX_WRITERS = 8
 DEFAULT_TOLERANCES = (1.0, 2.0, 5.0)
+MAX_VIEWS = 8
 
 
 def get_args_parser():
@@ -75,11 +85,41 @@ def get_args_parser():
                    help="with --masks: per-frame Dice and boundary metrics (normalised surface distance at these tolerances, in "
                         "pixels at native size; Hausdorff; mean surface distance) under 'surface' in metrics.json; no value = "
                         + " ".join(f"{t:g}" for t in DEFAULT_TOLERANCES))
+    p.add_argument("--tta_flip", action="store_true", help="test-time augmentation: also predict every frame mirrored, at every size")
+    p.add_argument("--tta_sizes", nargs="+", type=int, default=None, metavar="S",
+                   help="test-time augmentation: input sizes of the views (default: --imsize alone); each as --imsize is given to train")
+    p.add_argument("--confidence", action="store_true",
+                   help="also write <stem>_conf.png (mode L): 255 x the mean probability of the chosen class over the views")
     p.add_argument("--seed", default=None, type=int,
                    help="torch seed the TRAINING process was given before it built its modules; required when the checkpoint lacks "
                         "cross_vit / cross_cnn / backbone_encoder (the training command lines do not seed, so only a caller that "
                         "seeded train_seg itself has one)")
     return p
+
+
+# ---- views ------------------------------------------------------------------------------------------------------------------
+def plan_views(imsize: int, sizes: Optional[Sequence[int]], flip: bool) -> List[Tuple[int, bool]]:
+    """The views of test-time augmentation as (input size, mirrored): ``sizes`` (None = ``imsize`` alone) ascending with duplicates
+    removed, at each size the plain view before the mirrored one.  A non-positive size or more than ``MAX_VIEWS`` views raise."""
+    chosen = [imsize] if sizes is None else list(sizes)
+    for s in chosen:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 1:
+            raise ValueError(f"--tta_sizes / --imsize: {s!r} is not a positive input size")
+    if not chosen:
+        raise ValueError("--tta_sizes: no size given")
+    views = [(int(s), f) for s in sorted(set(int(s) for s in chosen)) for f in ((False, True) if flip else (False,))]
+    if len(views) > MAX_VIEWS:
+        raise ValueError(f"--tta_sizes / --tta_flip: {len(views)} views, at most {MAX_VIEWS} are supported")
+    return views
+
+
+def views_of(args) -> Optional[List[Tuple[int, bool]]]:
+    """None when no ``--tta_*`` flag and no ``--confidence`` is given (the tool then runs ``SegEngine.predict`` as before), else
+    ``plan_views`` of the arguments."""
+    flip, sizes = getattr(args, "tta_flip", False), getattr(args, "tta_sizes", None)
+    if not flip and sizes is None and not getattr(args, "confidence", False):
+        return None
+    return plan_views(args.imsize, sizes, flip)
 
 
 # ---- file list and batches ---------------------------------------------------------------------------------------------------
@@ -269,20 +309,34 @@ def build_engine(args) -> SegEngine:
 
 
 # ---- the run -----------------------------------------------------------------------------------------------------------------
-def predict_batch(engine: SegEngine, frames_u8: torch.Tensor, masks_u8: Optional[torch.Tensor], args, lut):
-    """Native uint8 [B,H,W,3] (host) -> device outputs of ``SegEngine.predict``: mask[, overlay][, counts]."""
+def _network_input(frames: torch.Tensor, size: int, flip: bool = False) -> torch.Tensor:
+    """Native uint8 frames on the device -> the float batch validation feeds the network at ``size`` (mirrored when ``flip``)."""
     from . import ops
+    small, _ = ops.frame_resize(frames, None, size)
+    if flip:
+        small = small.flip(2).contiguous()
+    inp, _ = _t._to_device_batch(small, torch.zeros(small.shape[:3], dtype=torch.uint8, device=small.device), train=False)
+    return inp
+
+
+def predict_batch(engine: SegEngine, frames_u8: torch.Tensor, masks_u8: Optional[torch.Tensor], args, lut, views=None):
+    """Native uint8 [B,H,W,3] (host) -> device outputs of ``SegEngine.predict``: mask[, overlay][, counts]; with ``views``
+    (``plan_views``) those of ``SegEngine.predict_views``: mask[, confidence][, overlay][, counts]."""
     C = args.num_classes
     frames = frames_u8.cuda(non_blocking=True).contiguous()
     B, H, W, _ = frames.shape
-    small, _ = ops.frame_resize(frames, None, args.imsize)
-    inp, _ = _t._to_device_batch(small, torch.zeros(small.shape[:3], dtype=torch.uint8, device=small.device), train=False)
+    if views is None:
+        inp = _network_input(frames, args.imsize)
     kw = dict(encode=_fr.encode_table(args.encode, C))
     if args.overlay:
         kw.update(frames=frames, alpha=_fr.default_alpha(C, args.alpha))
     if masks_u8 is not None:
         kw.update(target=masks_u8.cuda(non_blocking=True).contiguous(), lut=lut)
-    out = engine.predict(inp, size=(H, W), **kw)
+    if views is None:
+        out = engine.predict(inp, size=(H, W), **kw)
+    else:
+        out = engine.predict_views([_network_input(frames, s, f) for s, f in views], [f for _, f in views], (H, W),
+                                   confidence=bool(args.confidence), **kw)
     return out if isinstance(out, tuple) else (out,)
 
 
@@ -341,6 +395,8 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     the writer threads), "drain_seconds" (waiting for the writers after the last batch), "frames_per_second"}."""
     _fr.encode_table(args.encode, args.num_classes)          # argument errors before any model is built
     tolerances = surface_tolerances(args)
+    views = views_of(args)
+    with_conf = views is not None and bool(args.confidence)
     meter = None
     if tolerances is not None:
         from .segloss.surface import SurfaceMeter
@@ -356,10 +412,11 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
             fr, mk = frames.load_batch(idx)
             if mk is not None and meter is not None:
                 mk = mk.cuda(non_blocking=True).contiguous()     # predict_batch's upload, made here to keep the device copy
-            out = list(predict_batch(engine, fr, mk, args, frames.lut))
+            out = list(predict_batch(engine, fr, mk, args, frames.lut, views))
             if meter is not None:
                 surface_batch(meter, out[0], mk, args, frames.lut)
             mask = out.pop(0).cpu().numpy()
+            conf = out.pop(0).cpu().numpy() if with_conf else None
             over = out.pop(0).cpu().numpy() if args.overlay else None
             if mk is not None:
                 c = out.pop(0)
@@ -368,6 +425,8 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
                 stem = os.path.splitext(frames.rel[i])[0]
                 written.append(stem + ".png")
                 jobs.append(pool.submit(_save_png, mask[k], "L", os.path.join(args.pred_dir, stem + ".png")))
+                if conf is not None:
+                    jobs.append(pool.submit(_save_png, conf[k], "L", os.path.join(args.pred_dir, stem + "_conf.png")))
                 if over is not None:
                     jobs.append(pool.submit(_save_png, over[k], "RGB", os.path.join(args.pred_dir, stem + "_overlay.png")))
         t_fed = time.perf_counter() - t0                       # read + device + download; the writers ran beside it
@@ -377,6 +436,8 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     if total is not None:
         metrics = metrics_from_counts(total.cpu().numpy())
         metrics["frames"] = len(frames.rel)
+        if views is not None:
+            metrics["views"] = [[s, f] for s, f in views]
         if meter is not None:
             metrics["surface"] = meter.result()
         os.makedirs(args.pred_dir, exist_ok=True)

@@ -732,6 +732,20 @@ int asis_predict_mask(void* stream, const float* logits, int B, int h, int w, in
                       uint8_t* mask, const uint8_t* frames, const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay,
                       const uint8_t* target, const uint8_t* lut, int64_t* counts);
 
+/* Test-time augmentation of the prediction (csrc/predict.hip): K views of one batch (1 <= K <= 8), each its own fp32 NHWC logit
+ * map [B, hs[k], ws[k], C] with a horizontal-flip flag, fused into one mask at (H, W) without any [B,H,W,C] map.
+ *   logits, hs, ws, flips: HOST arrays of K entries (device pointers of the maps, their sizes, flip != 0 = mirrored); the
+ *     kernel receives them by value in its arguments: no device table, no allocation, no copy.
+ *   Per pixel and view, in view order: the C samples of asis_predict_mask (same taps and blend; a mirrored view keeps the taps and
+ *     weights of pixel x and mirrors the two column indices, i -> ws[k] - 1 - i, which is the resize of the column-reversed map
+ *     index for index), p = exp(z - max z) / sum in fp32, acc[c] += p[c].  Fixed order: bit-identical from call to call.
+ *   mask uint8 [B,H,W] = encode[argmax_c acc[c]], ties to the lowest class; confidence (optional, NULL = off) uint8 [B,H,W] =
+ *     (uint8)(255 * acc[pred] / K + 0.5).  overlay and counts: exactly those of asis_predict_mask. */
+int asis_predict_mask_views(void* stream, const float* const* logits, const int* hs, const int* ws, const int* flips, int K, int B,
+                            int C, int H, int W, const uint8_t* encode, uint8_t* mask, uint8_t* confidence, const uint8_t* frames,
+                            const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay, const uint8_t* target,
+                            const uint8_t* lut, int64_t* counts);
+
 /* Boundary metrics (csrc/surface.hip): exact squared Euclidean distance transform of the class boundaries at native size and the
  * per (frame, class) statistics behind Dice, normalised surface distance, Hausdorff and mean surface distance.
  *   pred, target uint8 [B,H,W] raw pixel values; pred_lut, lut uint8 [256] their label tables; P = (pred_lut[pred] == c),
