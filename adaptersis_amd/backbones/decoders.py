@@ -35,7 +35,7 @@ _DGRAD_MX = __import__("os").environ.get("ASIS_DGRAD_MX", "1") not in ("0", "")
 
 class _Stage:
     """Saved tensors of one conv -> BN -> ReLU -> upsample stage."""
-    __slots__ = ("x16", "raw", "scale", "shift", "mean", "invstd", "count", "factor", "stride", "pad", "pool")
+    __slots__ = ("x16", "raw", "scale", "shift", "mean", "invstd", "count", "factor", "stride", "pad", "pool", "cls_lowres")
 
 
 def _conv_weights(owner: _Packed, key: str, conv: nn.Conv2d, split: bool):
@@ -100,7 +100,7 @@ def conv_bn_relu_up_forward(owner: _Packed, key: str, x16, x_lo, conv: nn.Conv2d
     statistics (``seg_decoder.eval()`` in validate_network, train.py:451) and nothing is saved.  ``stride`` / ``pad``:
     the 3x3 conv's geometry (the CNN encoder's stride-2 stages); ``pool``: MaxPool2d(3, 2, 1) after the ReLU (stem).
     ``defer_up``: do not write the BatchNorm + ReLU + upsampled operand pair — the consumer evaluates it on load from the raw map
-    (the classifier conv: ops.conv3x3_smallcout_fwd_up); returns ``(("deferred", raw, scale, shift), stage)``."""
+    (the classifier conv: ops.cls_lowres_fwd or ops.conv3x3_smallcout_fwd_up); returns ``(("deferred", raw, scale, shift), stage)``."""
     dt = config.operand_dtype
     split_out = x_lo is not None                   # the next stage's operand pair keeps the caller's precision mode
     if key in config.unsplit_layers:
@@ -168,6 +168,8 @@ def conv_bn_relu_up_backward(owner: _Packed, key: str, st: _Stage, dU, conv: nn.
                              inv_scale: float, grads: Dict[str, torch.Tensor], prefix: str, need_dx: bool,
                              sync_bn: bool, conv_name: Optional[str] = None, bn_name: Optional[str] = None):
     """dU fp32 [B, fH, fW, C] (scaled by the loss scale) -> grads[...] (unscaled) and dX fp32 or None.
+    ``dU`` may also be the pair ``(g, partial)`` that ops.upsample_bn_relu_bwd would return, already computed by the consumer
+    (the commuted classifier, ops.cls_lowres_bwd): the transposed upsampling is then skipped.
     Parameter names default to ``prefix.0`` (conv) / ``prefix.1`` (BatchNorm)."""
     conv_name = conv_name or prefix + ".0"
     bn_name = bn_name or prefix + ".1"
@@ -175,7 +177,9 @@ def conv_bn_relu_up_backward(owner: _Packed, key: str, st: _Stage, dU, conv: nn.
     dt = config.operand_dtype
     C = conv.out_channels
     stride, pad = getattr(st, "stride", 1) or 1, getattr(st, "pad", 1)
-    if getattr(st, "pool", False):
+    if isinstance(dU, tuple):
+        g, partial = dU
+    elif getattr(st, "pool", False):
         g, partial = ops.maxpool_bn_relu_bwd(dU, st.raw, st.scale, st.shift, st.mean, st.invstd)
     else:
         g, partial = ops.upsample_bn_relu_bwd(dU, st.raw, st.scale, st.shift, st.mean, st.invstd, st.factor)
@@ -299,15 +303,27 @@ class FeatureDecoder(_Packed):
                           ops.mx_conv_ok(Bq * 4 * Hq * Wq, nxt.in_channels, nxt.out_channels))
             # stage 4 -> classifier: with 64 channels, <= 8 classes and split operands the upsampled pair (4x the bytes of the raw map)
             # is never written: the classifier conv and its weight gradient evaluate BatchNorm + ReLU + upsampling on load
+            # (ops.FUSE_CLS_UP, opt-in)
             fo = self.final_out
-            defer = bool(i == 4 and a[1] is not None and ops.FUSE_CLS_UP and seq[0].out_channels == 64 and fo.in_channels == 64 and
-                         fo.out_channels <= 8 and Hq >= 4 and Wq >= 8)
+            fuse = bool(i == 4 and a[1] is not None and ops.FUSE_CLS_UP and seq[0].out_channels == 64 and fo.in_channels == 64 and
+                        fo.out_channels <= 8 and Hq >= 4 and Wq >= 8)
+            # the default for 64 channels and 2..4 classes (ops.CLS_LOWRES): the classifier conv is commuted with the upsampling, so
+            # the stage's output is not written either, and the backward gets stage 4's (g, partial) from the classifier's kernel
+            lowres = bool(i == 4 and not fuse and ops.CLS_LOWRES and seq[0].out_channels == 64 and fo.in_channels == 64 and
+                          2 <= fo.out_channels <= 4 and Hq >= 2 and Wq >= 2)
+            defer = fuse or lowres
             a, st = conv_bn_relu_up_forward(self, f"d{i}", a[0], a[1], seq[0], seq[1], 2, self.sync_bn, save, training, mx_out=mx_out,
                                             defer_up=defer)
+            if lowres and st is not None:
+                st.cls_lowres = True
             saved.append(st)
         if isinstance(a[0], str):                     # ("deferred", raw, scale, shift)
-            logits = ops.conv3x3_smallcout_fwd_up(a[1], a[2], a[3], self._f32("final.wf", self.final_out.weight),
-                                                  self._f32("final.b", self.final_out.bias), config.operand_dtype)
+            if lowres:
+                logits = ops.cls_lowres_fwd(a[1], a[2], a[3], self._f32("final.wf", self.final_out.weight),
+                                            self._f32("final.b", self.final_out.bias))
+            else:
+                logits = ops.conv3x3_smallcout_fwd_up(a[1], a[2], a[3], self._f32("final.wf", self.final_out.weight),
+                                                      self._f32("final.b", self.final_out.bias), config.operand_dtype)
             saved.append(None)                        # no classifier input tensor: _final_backward recomputes it from saved[3]
             return logits, saved
         logits = self._final_forward(a)
@@ -326,13 +342,20 @@ class FeatureDecoder(_Packed):
         return ops.conv_gemm(a[0], w_hi, 3, 3, 1, 1, bias_n=bias)
 
     def _final_backward(self, x5, d16, d_lo, bias_partial, inv_scale, grads, dlogits_f32, st4=None):
-        """Gradients of the classifier conv; returns loss_scale * dL/d(its input), fp32 NHWC."""
+        """Gradients of the classifier conv; returns loss_scale * dL/d(its input), fp32 NHWC — or, where the forward took the
+        commuted classifier (``st4.cls_lowres``), the pair (g, partial) of stage 4 that conv_bn_relu_up_backward accepts."""
         C = self.num_classes
         if bias_partial is not None:
             ops.reduce_rows(bias_partial, inv_scale, grads["final_out.bias"])
         else:  # compatibility path: column sums of the fp32 dlogits [P, C]
             ops.reduce_rows(dlogits_f32, 1.0, grads["final_out.bias"])
         wout = grads["final_out.weight"]
+        if x5 is None and getattr(st4, "cls_lowres", False):
+            # one kernel: g of stage 4, its BatchNorm partial sums and the weight-gradient slabs; the slab sum on the side stream
+            g, partial, slabs = ops.cls_lowres_bwd(d16, d_lo, st4.raw, st4.scale, st4.shift, st4.mean, st4.invstd,
+                                                   self._f32("final.wf", self.final_out.weight), reduce=False)
+            parallel.wgrad_on_side_stream(lambda: ops.reduce_rows(slabs, inv_scale, wout.view(-1)), slabs)
+            return g, partial
         if x5 is None:      # the classifier's input was never written (upsample on load): st4 = the stage that would have produced it
             parallel.wgrad_on_side_stream(lambda: ops.conv3x3_smallcout_wgrad_up(d16, st4.raw, st4.scale, st4.shift, C, inv_scale, out=wout),
                                           d16, st4.raw)

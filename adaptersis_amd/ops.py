@@ -847,6 +847,58 @@ def conv3x3_smallcout_wgrad_up(dy: torch.Tensor, raw: torch.Tensor, scale: torch
     return out
 
 
+# stage-4 tail + classifier with the conv commuted with the x2 upsampling (csrc/clslowres.hip): ON by default — the 64-channel map
+# is never written at the classifier's resolution, forward (the 16-bit operand pair) or backward (the fp32 dU);
+# ASIS_CLS_LOWRES=0 keeps bn_relu_upsample -> smallcout_fwd / smallcout_dgrad -> upsample_bn_relu_bwd + wgrad
+CLS_LOWRES = os.environ.get("ASIS_CLS_LOWRES", "1") not in ("0", "")
+
+
+def cls_lowres_ok(raw: torch.Tensor, C: int) -> bool:
+    """shapes the commuted classifier kernels cover: fp32 NHWC raw map with 64 channels, at least 2 x 2, and 2..4 classes"""
+    return bool(raw.dtype == torch.float32 and raw.dim() == 4 and raw.shape[3] == 64 and raw.is_contiguous()
+                and 2 <= C <= 4 and raw.shape[1] >= 2 and raw.shape[2] >= 2)
+
+
+def cls_lowres_fwd(raw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, w: torch.Tensor,
+                   bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """conv3x3(upsample2(relu(raw * scale + shift))) + bias, the conv's 1x1 parts evaluated before the upsampling
+    (include/asis_hip.h: asis_cls_lowres_fwd): raw fp32 NHWC [B, H, W, 64], w fp32 [C, 64, 3, 3] -> fp32 [B, 2H, 2W, C]."""
+    _dev(raw, scale, shift, w, bias)
+    B, H, W, Cin = raw.shape
+    Cout = w.shape[0]
+    z = torch.empty((B, H, 9, W, Cout), device=raw.device, dtype=torch.float32)
+    out = torch.empty((B, 2 * H, 2 * W, Cout), device=raw.device, dtype=torch.float32)
+    check(lib().asis_cls_lowres_fwd(_stream(), raw.data_ptr(), _f32c(scale).data_ptr(), _f32c(shift).data_ptr(), _f32c(w).data_ptr(),
+                                    _p(_f32c(bias)), z.data_ptr(), out.data_ptr(), B, H, W, Cin, Cout), "asis_cls_lowres_fwd")
+    return out
+
+
+def cls_lowres_bwd(d16: torch.Tensor, d_lo: Optional[torch.Tensor], raw: torch.Tensor, scale, shift, mean, invstd, w: torch.Tensor,
+                   inv_scale: float = 1.0, out: Optional[torch.Tensor] = None, reduce: bool = True):
+    """backward of the same: d16 (+ d_lo) 16-bit [B, 2H, 2W, CP] (loss-scaled) -> (g fp32 [B, H, W, 64], partial [nblk, 2, 64],
+    dW fp32 [C, 64, 3, 3] = inv_scale * the reduced slabs).  ``reduce=False``: the third item is the slab tensor [nblk, C*64*9] and
+    the caller runs ``reduce_rows(slabs, inv_scale, out)`` itself (on the weight-gradient stream)."""
+    _dev(d16, d_lo, raw, w, out)
+    B, H, W, Cin = raw.shape
+    Cout = w.shape[0]
+    if not d16.is_contiguous() or tuple(d16.shape[:3]) != (B, 2 * H, 2 * W) or (d_lo is not None and d_lo.shape != d16.shape):
+        raise ValueError("cls_lowres_bwd: d16 / d_lo must be contiguous [B, 2H, 2W, CP]")
+    nblk = lib().asis_cls_lowres_nblk(B, H, W)
+    g = torch.empty_like(raw)
+    partial = torch.empty((nblk, 2, Cin), device=raw.device, dtype=torch.float32)
+    slabs = torch.empty((nblk, Cout * Cin * 9), device=raw.device, dtype=torch.float32)
+    check(lib().asis_cls_lowres_bwd(_stream(), _dt(d16.dtype), d16.data_ptr(), _p(d_lo), d16.shape[3], raw.data_ptr(),
+                                    _f32c(scale).data_ptr(), _f32c(shift).data_ptr(), _f32c(mean).data_ptr(), _f32c(invstd).data_ptr(),
+                                    _f32c(w).data_ptr(), g.data_ptr(), partial.data_ptr(), slabs.data_ptr(), nblk, B, H, W, Cin, Cout),
+          "asis_cls_lowres_bwd")
+    if not reduce:
+        return g, partial, slabs
+    if out is None:
+        out = torch.empty((Cout, Cin, 3, 3), device=raw.device, dtype=torch.float32)
+    reduce_rows(slabs, inv_scale, out.view(-1))
+    return g, partial, out
+
+
 def conv3x3_smallcout_dgrad(dy_hi: torch.Tensor, dy_lo: Optional[torch.Tensor], w: torch.Tensor) -> torch.Tensor:
     """Input gradient of the small-Cout conv: dy 16-bit [B,H,W,CoP] (hi [+lo]) -> dx fp32 [B,H,W,Cin]."""
     _dev(dy_hi, dy_lo, w)

@@ -429,6 +429,24 @@ int asis_conv3x3_smallcout_fwd_up(void* stream, int dtype, const float* raw, con
 int asis_conv3x3_smallcout_wgrad_up(void* stream, int dtype, const void* dy, int CoP, const float* raw, const float* scale,
                                     const float* shift, float* slabs, int nblk, int B, int H, int W, int Cin, int Cout);
 
+/* The same stage-4 tail and classifier with the conv COMMUTED with the upsampling (csrc/clslowres.hip).  The x2 upsampling acts per
+ * channel and is linear, so the 1x1 part of each of the nine taps runs first, at [H, W]:  a = relu(raw * scale + shift),
+ * z[b,i,j,(ky*3+kx)*Cout + c] = sum_k a[k] * w[c,k,ky,kx]  (fp32 [B, H, W, 9 Cout], a work buffer the caller provides), and
+ * out[b,y,x,c] = bias[c] + sum over the taps whose position (y+ky-1, x+kx-1) lies inside [2H, 2W] of up(z[tap,c]) there (the conv's
+ * zero padding as a bounds mask; the bilinear taps are the tap_ac_true expressions of asis_upsample_bn_relu_bwd).  The 64-channel
+ * map never exists at [2H, 2W], forward or backward.  Cin = 64, Cout in 2..4, H, W >= 2; products and sums in fp32.
+ * Backward, one kernel: e[tap,c] = up^T(shift_tap(d)) with d = d16 (+ d_lo), 16-bit [B, 2H, 2W, CoP] (CoP % 4 == 0, still carrying
+ * the loss scale); g = relu'(.) * (Wz^T e) fp32 [B, H, W, 64] and partial[nblk][2][64] = sum g | sum g*xhat — what
+ * asis_upsample_bn_relu_bwd hands to asis_bn_bwd_apply; slabs[nblk][Cout*64*9] = per-workgroup sums of a[k] * e[tap,c] in the
+ * parameter's [Cout][64][3][3] order (asis_reduce_rows finishes both).  nblk = asis_cls_lowres_nblk(B, H, W).  No atomics: every sum
+ * runs in a fixed order. */
+int asis_cls_lowres_nblk(int B, int H, int W);
+int asis_cls_lowres_fwd(void* stream, const float* raw, const float* scale, const float* shift, const float* w, const float* bias,
+                        float* z, float* out, int B, int H, int W, int Cin, int Cout);
+int asis_cls_lowres_bwd(void* stream, int dtype, const void* d16, const void* d_lo, int CoP, const float* raw, const float* scale,
+                        const float* shift, const float* mean, const float* invstd, const float* w, float* g, float* partial,
+                        float* slabs, int nblk, int B, int H, int W, int Cin, int Cout);
+
 /* Weight gradient of the same 3x3 / stride 1 / pad 1 classifier conv (`backbones/decoders.py:135` under
  * `loss.backward()`, `train.py:432`): dy 16-bit [B,H,W,CoP], x 16-bit [B,H,W,Cin] -> `nblk` fp32 slab rows of
  * [Cout,Cin,3,3] partial sums (one per workgroup; sum them with asis_reduce_rows).  Cin in {8,16,32,64}. */
