@@ -204,6 +204,10 @@ SIGNATURES = {
     "asis_softmax_dropout_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, C.c_uint64, _i, _f],
     "asis_grad_guard": [_vp, _vp, _i64, _vp, _i],
     "asis_sgd_momentum_guarded": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i, _vp, _i],
+    "asis_grad_sumsq_blocks": [_i64],
+    "asis_grad_sumsq": [_vp, _vp, _i64, _vp],
+    "asis_adamw_prepare": [_vp, _vp, _i, _vp, _vp, _f, _f, _d, _d],
+    "asis_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _d, _d, _d, _d, _f, _vp, _vp],
     "asis_scale_f32": [_vp, _vp, _i64, _f],
     "asis_zero": [_vp, _vp, _i64],
     "asis_grad_pack_bf16": [_vp, _vp, _i64, _vp],

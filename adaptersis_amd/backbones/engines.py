@@ -26,7 +26,7 @@ from torch import nn
 
 from .. import config, ops
 from ..dinov2.layers.blocks import _Packed, _pack, run_blocks
-from ..optim import SGD, FlatBucket
+from ..optim import SGD, AdamW, FlatBucket
 from ..parallel import StageReducer, world_size
 from .adapter_blocks import CACNN, CAViT, deform_inputs
 
@@ -85,7 +85,9 @@ class SegEngine(nn.Module):
                  n_last_blocks: int = 4, num_classes: int = 2, lr: float = 0.01, momentum: float = 0.99,
                  weight_decay: float = 3e-5, mode: str = "reference_exact", process_group=None, loss: str = "dice",
                  train_encoder: bool = False, train_backbone: bool = False, optimize_backbone: bool = False,
-                 blocks_per_bucket: int = 4, grad_compress: Optional[str] = None):
+                 blocks_per_bucket: int = 4, grad_compress: Optional[str] = None, optimizer: str = "sgd",
+                 betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
+                 layer_decay: Optional[float] = None):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -100,7 +102,12 @@ class SegEngine(nn.Module):
         computed and exchanged but not applied unless ``optimize_backbone`` is set.  ``grad_compress`` ("bf16" | "none"; default: the ``ASIS_GRAD_COMPRESS``
         environment variable, else "bf16"): the backbone bucket travels as bfloat16 (parallel.StageReducer) — half the bytes of the
         one exchange that is large enough for an xGMI ring to notice (0.6 instead of 1.2 GB); the decoder / adapter / encoder buckets
-        (63 + 31 MB) always travel as fp32 like the reference's DDP."""
+        (63 + 31 MB) always travel as fp32 like the reference's DDP.
+
+        ``optimizer``: "sgd" (default: ``optim.SGD`` with ``momentum`` / ``weight_decay``, the reference scripts) or "adamw"
+        (``optim.AdamW`` with ``betas``, ``eps``, ``weight_decay``, global-norm clipping at ``clip_grad``, ``no_decay`` for 1-D and
+        token parameters; ``layer_decay`` scales the learning rate of the ViT bucket per block, so it needs
+        ``optimize_backbone``).  ``clip_grad`` with "sgd" raises: the SGD kernels do not clip."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -188,7 +195,11 @@ class SegEngine(nn.Module):
                                                                                compress=grad_compress)
             if optimize_backbone:
                 buckets.append(self.vit_bucket)
-        self.optimizer = SGD(buckets, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        if layer_decay is not None and not (train_backbone and optimize_backbone):
+            raise ValueError("layer_decay scales the learning rates of the ViT blocks: it needs train_backbone and optimize_backbone")
+        self.optimizer = make_optimizer(optimizer, buckets, lr=lr, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps,
+                                        clip_grad=clip_grad, no_decay=no_decay, depth=len(model.blocks),
+                                        layer_decay=[layer_decay if b is self.vit_bucket else None for b in buckets])
         self.reducer = StageReducer(self.bucket.grad, self.stage_ranges, process_group)
         self._geom = {}
 
@@ -844,6 +855,21 @@ class SegEngine(nn.Module):
         return ops.predict_mask_views(logits, size, flips=flips, **kw)
 
 
+def make_optimizer(kind: str, buckets, *, lr, momentum, weight_decay, betas=(0.9, 0.999), eps=1e-8, clip_grad=None, no_decay=True,
+                   layer_decay=None, depth=None):
+    """The engines' ``optimizer=`` switch: "sgd" builds exactly the ``optim.SGD`` they always built, "adamw" an ``optim.AdamW``."""
+    if kind == "sgd":
+        if clip_grad is not None:
+            raise ValueError("clip_grad needs optimizer='adamw': the SGD kernels do not clip")
+        if layer_decay is not None and any(d is not None for d in layer_decay):
+            raise ValueError("layer_decay needs optimizer='adamw'")
+        return SGD(buckets, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    if kind == "adamw":
+        return AdamW(buckets, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_grad=clip_grad, no_decay=no_decay,
+                     layer_decay=layer_decay, depth=depth)
+    raise ValueError("optimizer must be 'sgd' or 'adamw'")
+
+
 def make_vit_bucket(model, blocks_per_bucket: int, process_group, momentum: bool = False, min_first_blocks: int = 0,
                     compress: Optional[str] = None):
     """Flat gradient bucket of the whole backbone in gradient-ready order (final norm, blocks last..first, then the token
@@ -885,7 +911,8 @@ class EndToEndEngine(nn.Module):
     """
 
     def __init__(self, model, seg_decoder, *, lr: float = 0.01, momentum: float = 0.9, weight_decay: float = 0.0,
-                 loss: str = "ce_dc", process_group=None, blocks_per_bucket: int = 4):
+                 loss: str = "ce_dc", process_group=None, blocks_per_bucket: int = 4, optimizer: str = "sgd",
+                 betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True):
         super().__init__()
         if loss not in SegEngine.LOSSES:
             raise ValueError(f"loss must be one of {sorted(SegEngine.LOSSES)}")
@@ -899,7 +926,8 @@ class EndToEndEngine(nn.Module):
         assert len(ordered) == len(named)
         self.bucket = FlatBucket(ordered)
         self.stage_ranges = [self.bucket.range_of([n for n in named if n.startswith(pre + ".")]) for pre in order]
-        self.optimizer = SGD([self.bucket], lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.optimizer = make_optimizer(optimizer, [self.bucket], lr=lr, momentum=momentum, weight_decay=weight_decay, betas=betas,
+                                        eps=eps, clip_grad=clip_grad, no_decay=no_decay)
         self.reducer = StageReducer(self.bucket.grad, self.stage_ranges, process_group)
         # backbone: gradient-ready order = final norm, blocks last..first, then the token embedding parameters; reduced
         # after every `blocks_per_bucket` blocks

@@ -1691,6 +1691,55 @@ def sgd_momentum(p: torch.Tensor, g: torch.Tensor, buf: torch.Tensor, lr: float,
           "asis_sgd_momentum")
 
 
+def grad_sumsq_blocks(n: int) -> int:
+    """partials ``grad_sumsq`` writes for a bucket of ``n`` elements (host arithmetic)"""
+    return int(lib().asis_grad_sumsq_blocks(int(n)))
+
+
+def grad_sumsq(g: torch.Tensor, partials: torch.Tensor) -> None:
+    """partials fp32 [grad_sumsq_blocks(g.numel())] = per-workgroup sums of g^2 (fixed order: bit-identical between calls);
+    a non-finite element makes its partial non-finite.  ``partials``: a bucket's slice of the step's partials buffer."""
+    _dev(g, partials)
+    if _f32c(partials).numel() != grad_sumsq_blocks(g.numel()):
+        raise ValueError(f"grad_sumsq: partials must hold {grad_sumsq_blocks(g.numel())} elements, got {partials.numel()}")
+    check(lib().asis_grad_sumsq(_stream(), _f32c(g).data_ptr(), g.numel(), partials.data_ptr()), "asis_grad_sumsq")
+
+
+def _adamw_state(guard: torch.Tensor, rec: torch.Tensor) -> None:
+    if guard.dtype != torch.int32 or guard.numel() != 3 or not guard.is_contiguous():
+        raise ValueError("guard must be a contiguous int32 tensor of 3 elements (skip flag, skipped steps, step count)")
+    if _f32c(rec).numel() != 4:
+        raise ValueError("rec must be a float32 tensor of 4 elements (clip coefficient, two bias corrections, norm)")
+
+
+def adamw_prepare(partials: torch.Tensor, guard: torch.Tensor, rec: torch.Tensor, inv_scale: float, max_norm: Optional[float],
+                  beta1: float, beta2: float) -> None:
+    """Once per step, behind the ``grad_sumsq`` of every bucket: overflow decision, step count, clip coefficient (``max_norm``
+    None or <= 0: no clipping) and bias corrections, all on the device (include/asis_hip.h)."""
+    _dev(partials, guard, rec)
+    _adamw_state(guard, rec)
+    check(lib().asis_adamw_prepare(_stream(), _f32c(partials).data_ptr(), partials.numel(), guard.data_ptr(), rec.data_ptr(),
+                                   float(inv_scale), float(max_norm or 0.0), float(beta1), float(beta2)), "asis_adamw_prepare")
+
+
+def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, codes: torch.Tensor, lr_scale: torch.Tensor,
+               weight_decay: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, inv_scale: float,
+               guard: torch.Tensor, rec: torch.Tensor) -> None:
+    """torch.optim.AdamW on one flat bucket; ``codes`` uint8 [numel / 4] picks (lr_scale, weight_decay) per 4 elements."""
+    _dev(p, g, m, v, codes, lr_scale, weight_decay, guard, rec)
+    _adamw_state(guard, rec)
+    n = _f32c(p).numel()
+    if _f32c(g).numel() != n or _f32c(m).numel() != n or _f32c(v).numel() != n:
+        raise ValueError("adamw_step: p, g, m and v must have the same length")
+    if codes.dtype != torch.uint8 or not codes.is_contiguous() or codes.numel() * 4 != n:
+        raise ValueError(f"adamw_step: codes must be a contiguous uint8 tensor of numel / 4 = {n // 4} elements")
+    if _f32c(lr_scale).numel() != _f32c(weight_decay).numel():
+        raise ValueError("adamw_step: the lr_scale and weight_decay tables must have the same length")
+    check(lib().asis_adamw_step(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, codes.data_ptr(),
+                                lr_scale.data_ptr(), weight_decay.data_ptr(), lr_scale.numel(), float(lr), float(beta1),
+                                float(beta2), float(eps), float(inv_scale), guard.data_ptr(), rec.data_ptr()), "asis_adamw_step")
+
+
 # --------------------------------------------------------------------------------------------
 # input pipeline
 # --------------------------------------------------------------------------------------------

@@ -144,13 +144,22 @@ def broadcast_module_states(modules, src: int = 0, group=None) -> None:
 
 
 def _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=0.01, momentum=0.99, weight_decay=3e-5,
-                mode="reference_exact", train_encoder=False, num_classes=2, loss="dice"):
+                mode="reference_exact", train_encoder=False, num_classes=2, loss="dice", **optimizer_args):
     key = id(seg_decoder)
     if key not in _ENGINES:
         _ENGINES[key] = SegEngine(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=momentum,
                                   weight_decay=weight_decay, mode=mode, train_encoder=train_encoder, num_classes=num_classes,
-                                  loss=loss)
+                                  loss=loss, **optimizer_args)
     return _ENGINES[key]
+
+
+def _optimizer_args(args) -> dict:
+    """The optimizer flags of ``get_args_parser`` as ``SegEngine`` arguments (a namespace built without them: the SGD defaults)."""
+    kind = getattr(args, "optimizer", "sgd")
+    if kind == "sgd":   # clip_grad / layer_decay are passed on so that the engine rejects them
+        return {"optimizer": "sgd", "clip_grad": getattr(args, "clip_grad", None), "layer_decay": getattr(args, "layer_decay", None)}
+    return {"optimizer": kind, "betas": (args.adam_beta1, args.adam_beta2), "eps": args.adam_eps, "clip_grad": args.clip_grad,
+            "layer_decay": args.layer_decay}
 
 
 def build_modules(args, head: str, num_classes: int, dev):
@@ -194,14 +203,17 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = 
     # the reference wraps these four modules in DistributedDataParallel (`train.py:84-116`), whose constructor broadcasts
     # rank 0's parameters and buffers: without it every rank would train its own randomly initialised copy
     broadcast_module_states([backbone_encoder, cross_vit, cross_cnn, seg_decoder])
+    wd = getattr(args, "weight_decay", None)   # --weight_decay; default: the script's own value
     if head == "mla":
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
-        engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9, weight_decay=0.0,
-                             num_classes=num_classes, loss=loss)
+        engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
+                             weight_decay=0.0 if wd is None else wd, num_classes=num_classes, loss=loss, **_optimizer_args(args))
     else:
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=args.lr,
+                             weight_decay=3e-5 if wd is None else wd,
                              mode="train_adapters" if getattr(args, "train_adapters", False) else "reference_exact",
-                             train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss)
+                             train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss,
+                             **_optimizer_args(args))
     optimizer = engine.optimizer
 
     dataset_train, dataset_val, collate = open_datasets(args)
@@ -289,9 +301,11 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
     seg_decoder.train()
     engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder)
     if optimizer is not engine.optimizer:
-        raise ValueError("train(): pass the engine's optimizer (adaptersis_amd.optim.SGD over the flat bucket)")
+        raise ValueError("train(): pass the engine's optimizer (engine.optimizer: adaptersis_amd.optim.SGD or AdamW over the "
+                         "flat buckets)")
     metric_logger = utils.MetricLogger(delimiter="  ")
     metric_logger.add_meter("lr", utils.SmoothedValue(window_size=1, fmt="{value:.6f}"))
+    with_norm = hasattr(optimizer, "last_grad_norm")   # optim.AdamW: one more scalar read behind the step's synchronize
     # SyncBatchNorm element counts: with the reference's DistributedSampler every rank holds the same number of images in every
     # iteration (also in the short last batch); any other loader may not, so the ranks' batch sizes are exchanged per step
     ragged = parallel.collectives_on() and not isinstance(getattr(loader, "sampler", None),
@@ -303,11 +317,13 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
         torch.cuda.synchronize()  # the reference syncs and reads the loss every step (train.py:439-440)
         metric_logger.update(loss=loss.item())
         metric_logger.update(lr=optimizer.param_groups[0]["lr"])
+        if with_norm:
+            metric_logger.update(grad_norm=optimizer.last_grad_norm)
     if ragged:
         parallel.set_batch_ratio(None)
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
-    # overflow guard of the static 16-bit loss scale (optim.SGD): a step whose gradients hold an inf / NaN is skipped on the
+    # overflow guard of the static 16-bit loss scale (optim.SGD / optim.AdamW): a step whose gradients hold an inf / NaN is skipped on the
     # device.  One host read per epoch; an epoch in which EVERY step was skipped means the scale is too large for this data —
     # the reference's torch.optim.SGD has no skip, so a silent stall would be a behaviour change.
     skipped = optimizer.skipped_steps
@@ -388,6 +404,16 @@ def get_args_parser():
     p.add_argument("--shard_val", action="store_true",
                    help="validation sharded over the ranks (every world-th batch per rank, metric sums all-reduced) instead of the "
                         "reference's whole val set on every rank (train.py:125-130,236-238); same batches, same per-batch results")
+    # extension: the optimizer (default: the reference's SGD).  adamw = optim.AdamW, the fused HIP AdamW with global-norm clipping
+    p.add_argument("--optimizer", default="sgd", choices=("sgd", "adamw"))
+    p.add_argument("--weight_decay", default=None, type=float,
+                   help="default: the script's own value (train.py 3e-5, train_mla.py / train_multi_class.py 0)")
+    p.add_argument("--adam_beta1", default=0.9, type=float)
+    p.add_argument("--adam_beta2", default=0.999, type=float)
+    p.add_argument("--adam_eps", default=1e-8, type=float)
+    p.add_argument("--clip_grad", default=None, type=float, help="adamw: clip the global gradient norm at this value")
+    p.add_argument("--layer_decay", default=None, type=float,
+                   help="adamw: layer-wise learning-rate decay of the ViT blocks (engines that optimise the backbone)")
     return p
 
 

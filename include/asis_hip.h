@@ -817,6 +817,34 @@ int asis_softmax_dropout_bwd(void* stream, int dtype, const void* p16, const voi
 int asis_grad_guard(void* stream, const float* g, int64_t n, int32_t* guard, int reset);
 int asis_sgd_momentum_guarded(void* stream, float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
                               float weight_decay, float inv_scale, int first_step, int32_t* guard, int count_skip);
+/* Fused AdamW with global-norm gradient clipping on the flat fp32 buckets (csrc/adamw.hip; torch.optim.AdamW with decoupled
+ * decay and amsgrad=False behind torch.nn.utils.clip_grad_norm_, the optimiser of the reference's DINOv2 half,
+ * dinov2/train/train.py:62,250-259).  Three launches per step and no host synchronisation; buckets are 16-byte aligned and a
+ * multiple of 4 elements long (there is no scalar path: anything else is ASIS_EINVAL).
+ *   asis_grad_sumsq: partials[0 .. asis_grad_sumsq_blocks(n)) = per-workgroup fp32 sums of g^2, added in a fixed order (no
+ *     atomics, the grid depends on n alone: bit-identical between calls).  An inf / NaN element makes its partial non-finite:
+ *     this pass is the overflow check too and replaces asis_grad_guard.  The buckets of a step write side by side into one
+ *     partials buffer, each at its own offset.
+ *   asis_grad_sumsq_blocks(n): that count (host arithmetic, no GPU).
+ *   asis_adamw_prepare (one workgroup, once per step, after every asis_grad_sumsq): sum = the n_partials partials in double, in
+ *     a fixed order.  guard = int32[3] {skip flag, skipped steps, step count t}, rec = fp32[4].
+ *       sum not finite: guard[0] = 1, guard[1] += 1, nothing else changes;
+ *       else guard[0] = 0, t = ++guard[2], norm = inv_scale * sqrt(sum),
+ *         rec = {max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1, 1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t), norm}
+ *         (the three factors computed in double).  The step count lives on the device because the host never learns whether a
+ *         step was skipped.
+ *   asis_adamw_step (per bucket): nothing when guard[0] != 0; else per element, in fp32, with c = codes[i / 4] (one uint8 per
+ *     group of 4 elements, n / 4 of them; n_groups <= 256 table entries), lr_e = lr * lr_scale[c], wd_e = weight_decay[c]:
+ *       g' = g * inv_scale * rec[0];  p *= 1 - lr_e * wd_e;  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;
+ *       p -= lr_e * rec[1] * m / (sqrt(v) * rec[2] + eps).
+ *     A code >= n_groups reads the last table entry.  Only asis_adamw_prepare writes guard and rec. */
+int asis_grad_sumsq_blocks(int64_t n);
+int asis_grad_sumsq(void* stream, const float* g, int64_t n, float* partials);
+int asis_adamw_prepare(void* stream, const float* partials, int n_partials, int32_t* guard, float* rec, float inv_scale,
+                       float max_norm, double beta1, double beta2);
+int asis_adamw_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* codes,
+                    const float* lr_scale, const float* weight_decay, int n_groups, double lr, double beta1, double beta2,
+                    double eps, float inv_scale, const int32_t* guard, const float* rec);
 int asis_scale_f32(void* stream, float* x, int64_t n, float a);
 /* zero `bytes` bytes at p on `stream` (hipMemsetAsync: the DMA fill, ~6 TB/s; the step's few accumulate-into buffers) */
 int asis_zero(void* stream, void* p, int64_t bytes);
