@@ -196,6 +196,7 @@ SIGNATURES = {
     "asis_frame_resize": [_vp] * 5 + [_i, _vp, _vp, _i] + [_vp] * 6 + [_i] * 5,
     "asis_predict_mask": [_vp, _vp] + [_i] * 6 + [_vp] * 9,
     "asis_predict_mask_views": [_vp] * 5 + [_i] * 5 + [_vp] * 10,
+    "asis_predict_mask_tiles": [_vp] * 6 + [_i] * 4 + [_f] + [_i] * 4 + [_vp] * 10,
     "asis_surface_stats": [_vp] * 5 + [_i] * 6 + [_vp, _i] + [_vp] * 6 + [_i],
     "asis_dropout_f32": [_vp, _vp, _vp, _vp, _i64, C.c_uint64, _i, _f, _f, _vp, _i],
     "asis_dropout_t16": [_vp, _i, _vp, _vp, _i64, C.c_uint64, _i, _f, _i],

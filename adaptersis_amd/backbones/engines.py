@@ -854,6 +854,31 @@ class SegEngine(nn.Module):
             enc.update_running_stats = upd
         return ops.predict_mask_views(logits, size, flips=flips, **kw)
 
+    @torch.no_grad()
+    def predict_tiles(self, inps, tiles, work, size, **kw):
+        """Sliding-window prediction: masks at ``size`` = (H, W) from several tiles of one batch.  ``inps[k]`` is float [B,3,S,S]
+        as validation feeds it: the crop (or, for a context tile, the resized whole) of the working frame ``work`` = (Lh, Lw)
+        that ``tiles[k]`` = (oy, ox, sy, sx, flip) names, given mirrored when ``flip``.  ``eval_logits`` runs once per tile under
+        the guard of ``predict`` (decoder in eval mode, the encoder's running statistics not updated, both restored afterwards).
+        Each tile is its own forward of batch B, so the encoder's BatchNorm normalises every tile with that tile's own batch
+        statistics: the tiles of a frame differ by more than their place, and a frame's mask still depends on the batch it is
+        predicted in.  One ``ops.predict_mask_tiles`` call then blends the class probabilities of the tiles at native size
+        (keywords as there: ``encode``, ``blend``, ``ramp``, ``confidence``, ``frames`` / ``palette`` / ``alpha``, ``target`` /
+        ``lut``)."""
+        inps, tiles = list(inps), list(tiles)
+        if len(inps) != len(tiles):
+            raise ValueError(f"predict_tiles: {len(inps)} inputs and {len(tiles)} tiles")
+        enc = self.backbone_encoder
+        was, upd = self.seg_decoder.training, enc.update_running_stats
+        self.seg_decoder.eval()
+        enc.update_running_stats = False
+        try:
+            logits = [self.eval_logits(inp) for inp in inps]
+        finally:
+            self.seg_decoder.train(was)
+            enc.update_running_stats = upd
+        return ops.predict_mask_tiles(logits, tiles, work, size, **kw)
+
 
 def make_optimizer(kind: str, buckets, *, lr, momentum, weight_decay, betas=(0.9, 0.999), eps=1e-8, clip_grad=None, no_decay=True,
                    layer_decay=None, depth=None):

@@ -26,6 +26,23 @@
 //                         them is a runtime loop around the four pixels of the thread, so the vertical tap of a view is computed
 //                         once per thread and only acc[4][CB] and one pixel's samples are live (CB = C rounded up to 4 / 8 / 16:
 //                         no scratch).  Same quad store, overlay and counts as predict_mask_kernel (PredictTables).
+//   predict_tiles_kernel  sliding-window prediction: K <= 32 logit maps (tiles) of one batch, tile k an fp32 NHWC map of its own size
+//                         [B, h, w, C] that holds the integer rectangle (oy, ox, sy, sx) of a working grid Lh x Lw, some mirrored.
+//                         Per native pixel (y, x) of H x W, all in fp32, in this order:
+//                             uy = ((float)y + 0.5f) * ((float)Lh / (float)H)          (ux likewise with x, Lw, W)
+//                             tile k covers the pixel iff (float)oy <= uy < (float)(oy + sy) and the same in x
+//                             s  = (uy - (float)oy) * ((float)h / (float)sy) - 0.5f, s < 0 -> 0
+//                             i0 = min((int)s, h - 1), i1 = min(i0 + 1, h - 1), l1 = s - (float)i0, l0 = 1 - l1   (columns likewise; a
+//                             mirrored tile keeps the weights and reads columns w - 1 - i0, w - 1 - i1)
+//                         which is align_corners=False sampling of the tile's map, clamped inside the tile.  Then blend_taps per
+//                         class, the softmax of predict_views_kernel, acc[c] += g * p[c] (the product rounded on its own: no fma,
+//                         so a tile given twice doubles its term exactly) and wsum += g, tiles in list order.  g = 1 (uniform), or
+//                         g = gy * gx with gy = min(uy - oy, (oy + sy) - uy, R) / R, where an edge on the border of the working
+//                         grid (oy == 0, oy + sy == Lh) counts as infinitely far (ramp).  mask = encode[argmax acc] (strict >),
+//                         confidence = (uint8)(255 * acc[pred] / wsum + 0.5).  The loop over the tiles is a runtime loop that
+//                         skips a tile whose rows do not hold uy (one y per thread; uniform over a wave unless a row is shorter
+//                         than 256 pixels) or whose columns hold none of the thread's four ux before any address is formed; the
+//                         vertical tap is made once per tile and thread.  acc[4][CB], wsum[4] and one pixel's samples are live.
 #include "asis_common.h"
 #include "bilinear_tap.h"
 
@@ -285,6 +302,155 @@ __global__ __launch_bounds__(256) void predict_views_kernel(const ViewSet vs, in
   if (counts) flush_counts(s, tid, C, counts);
 }
 
+// K tiles of one batch in the kernel arguments (1.2 KB of the 4 KB a launch may carry): map k is fp32 NHWC [B, h[k], w[k], C] and
+// holds the rectangle rows [oy, oy + sy), columns [ox, ox + sx) of the working grid; flip[k] != 0 mirrors its columns
+constexpr int MAXTILES = 32;
+struct TileSet {
+  const float* p[MAXTILES];
+  int h[MAXTILES], w[MAXTILES], oy[MAXTILES], ox[MAXTILES], sy[MAXTILES], sx[MAXTILES], flip[MAXTILES];
+  int K, Lh, Lw, ramp_mode;
+  float R;
+};
+
+// distance weight of one axis: u in [o, o + s), an edge on the border of the working grid [0, L) does not ramp
+__device__ __forceinline__ float ramp_weight(float u, int o, int s, int L, float R) {
+  const float d0 = o == 0 ? INFINITY : u - (float)o;
+  const float d1 = o + s == L ? INFINITY : (float)(o + s) - u;
+  return fminf(fminf(d0, d1), R) / R;
+}
+
+// source coordinate d (in tile pixels, before the half-pixel shift) -> the tap of tap_ac_false
+__device__ __forceinline__ Tap tap_tile(float d, float scale, int in) {
+  float s = d * scale - 0.5f;
+  if (s < 0.f) s = 0.f;
+  Tap t;
+  t.i0 = (int)s;
+  if (t.i0 > in - 1) t.i0 = in - 1;
+  t.i1 = t.i0 + ((t.i0 < in - 1) ? 1 : 0);
+  t.l1 = s - (float)t.i0;
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+
+// tiles -> mask [B, H, W] (+ confidence [B, H, W]); grid as predict_mask_kernel; V, CB as predict_views_kernel
+template <int V, int CB>
+__global__ __launch_bounds__(256) void predict_tiles_kernel(const TileSet ts, int C, int H, int W, const uint8_t* __restrict__ encode,
+                                                            uint8_t* __restrict__ mask, uint8_t* __restrict__ confidence,
+                                                            const uint8_t* __restrict__ frames, const uint8_t* __restrict__ palette,
+                                                            const uint8_t* __restrict__ alpha, uint8_t* __restrict__ overlay,
+                                                            const uint8_t* __restrict__ target, const uint8_t* __restrict__ lut,
+                                                            unsigned long long* __restrict__ counts) {
+  __shared__ PredictTables s;
+  const int tid = threadIdx.x;
+  load_tables(s, tid, C, encode, palette, alpha, overlay != nullptr, lut, counts != nullptr);
+
+  const int b = blockIdx.y;
+  const int quads = (W + PX - 1) / PX;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + tid;
+  if (t < (int64_t)H * quads) {
+    const int y = (int)(t / quads), x0 = (int)(t - (int64_t)y * quads) * PX;
+    const int np = min(PX, W - x0);
+    const float rh = (float)ts.Lh / (float)H, rw = (float)ts.Lw / (float)W;
+    const float uy = ((float)y + 0.5f) * rh;
+    float ux[PX];
+#pragma unroll
+    for (int u = 0; u < PX; ++u) ux[u] = ((float)min(x0 + u, W - 1) + 0.5f) * rw;
+    const bool ramp = ts.ramp_mode != 0;
+    float acc[PX][CB], wsum[PX];
+#pragma unroll
+    for (int u = 0; u < PX; ++u) {
+      wsum[u] = 0.f;
+#pragma unroll
+      for (int c = 0; c < CB; ++c) acc[u][c] = 0.f;
+    }
+    for (int k = 0; k < ts.K; ++k) {
+      const int oy = ts.oy[k], sy = ts.sy[k];
+      if (!(uy >= (float)oy && uy < (float)(oy + sy))) continue;
+      const int ox = ts.ox[k], sx = ts.sx[k];
+      const float fx0 = (float)ox, fx1 = (float)(ox + sx);
+      if (!(ux[PX - 1] >= fx0 && ux[0] < fx1)) continue;          // ux ascends: none of the four is inside
+      const int h = ts.h[k], w = ts.w[k];
+      const bool flip = ts.flip[k] != 0;
+      const float sh = (float)h / (float)sy, sw = (float)w / (float)sx;
+      const Tap ty = tap_tile(uy - (float)oy, sh, h);
+      const float gy = ramp ? ramp_weight(uy, oy, sy, ts.Lh, ts.R) : 1.f;
+      const float* lg = ts.p[k] + (int64_t)b * h * w * C;
+      const float* r0 = lg + (int64_t)ty.i0 * w * C;
+      const float* r1 = lg + (int64_t)ty.i1 * w * C;
+#pragma unroll
+      for (int u = 0; u < PX; ++u) {
+        if (ux[u] >= fx0 && ux[u] < fx1) {
+          const Tap tx = tap_tile(ux[u] - fx0, sw, w);
+          const float g = ramp ? gy * ramp_weight(ux[u], ox, sx, ts.Lw, ts.R) : 1.f;
+          const int j0 = flip ? w - 1 - tx.i0 : tx.i0, j1 = flip ? w - 1 - tx.i1 : tx.i1;
+          const float* p00 = r0 + (int64_t)j0 * C;
+          const float* p01 = r0 + (int64_t)j1 * C;
+          const float* p10 = r1 + (int64_t)j0 * C;
+          const float* p11 = r1 + (int64_t)j1 * C;
+          float z[CB];
+          float m = -INFINITY;
+#pragma unroll
+          for (int c0 = 0; c0 < CB; c0 += V)
+            if (c0 < C) {
+              float v00[V], v01[V], v10[V], v11[V];
+              load_channels<V>(p00 + c0, v00);
+              load_channels<V>(p01 + c0, v01);
+              load_channels<V>(p10 + c0, v10);
+              load_channels<V>(p11 + c0, v11);
+#pragma unroll
+              for (int i = 0; i < V; ++i) {
+                z[c0 + i] = blend_taps(ty, tx, v00[i], v01[i], v10[i], v11[i]);
+                if (z[c0 + i] > m) m = z[c0 + i];
+              }
+            }
+          float sum = 0.f;
+#pragma unroll
+          for (int c = 0; c < CB; ++c)
+            if (c < C) {
+              z[c] = expf(z[c] - m);
+              sum += z[c];
+            }
+#pragma unroll
+          for (int c = 0; c < CB; ++c)
+            if (c < C) acc[u][c] += __fmul_rn(g, z[c] / sum);      // in tile order: bit-identical from call to call
+          wsum[u] += g;
+        }
+      }
+    }
+    int cls[PX];
+    uint32_t conf[PX];
+#pragma unroll
+    for (int u = 0; u < PX; ++u) {
+      float m = acc[u][0];
+      int am = 0;
+#pragma unroll
+      for (int c = 1; c < CB; ++c)
+        if (c < C && acc[u][c] > m) { m = acc[u][c]; am = c; }   // strict, in class order: the lowest class wins a tie
+      cls[u] = am;
+      conf[u] = wsum[u] > 0.f ? (uint32_t)(255.f * m / wsum[u] + 0.5f) : 0u;   // no weight: a pixel the host check lets through
+    }
+    const int64_t pix = ((int64_t)b * H + y) * W + x0;
+    emit_quad(s, tid, C, cls, np, pix, mask, frames, overlay, target, counts != nullptr);
+    if (confidence) store_quad(confidence + pix, np, conf[0], conf[1], conf[2], conf[3]);
+  }
+  if (counts) flush_counts(s, tid, C, counts);
+}
+
+// do the intervals [o[k], o[k] + s[k]) cover [0, L)?
+bool intervals_cover(const int* rects, int K, int at, int L) {
+  int reach = 0;
+  while (reach < L) {
+    int best = reach;
+    for (int k = 0; k < K; ++k) {
+      const int o = rects[k * 4 + at], e = o + rects[k * 4 + at + 2];
+      if (o <= reach && e > best) best = e;
+    }
+    if (best == reach) return false;
+    reach = best;
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" int asis_predict_mask(void* stream, const float* logits, int B, int h, int w, int C, int H, int W, const uint8_t* encode,
@@ -370,5 +536,81 @@ extern "C" int asis_predict_mask_views(void* stream, const float* const* logits,
 #undef ASIS_VIEWS_BUCKET
 #undef ASIS_VIEWS_LAUNCH
   ASIS_CHECK_LAUNCH("asis_predict_mask_views");
+  return ASIS_OK;
+}
+
+extern "C" int asis_predict_mask_tiles(void* stream, const float* const* logits, const int* hs, const int* ws, const int* rects,
+                                       const int* flips, int K, int Lh, int Lw, int blend, float ramp, int B, int C, int H, int W,
+                                       const uint8_t* encode, uint8_t* mask, uint8_t* confidence, const uint8_t* frames,
+                                       const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay, const uint8_t* target,
+                                       const uint8_t* lut, int64_t* counts) {
+  ASIS_REQUIRE(K >= 1 && K <= MAXTILES, "asis_predict_mask_tiles: K=%d tiles, supported 1..%d", K, MAXTILES);
+  ASIS_REQUIRE(logits && hs && ws && rects && flips && encode && mask,
+               "asis_predict_mask_tiles: null pointer (logits, hs, ws, rects, flips, encode and mask are required)");
+  ASIS_REQUIRE(C >= 1 && C <= MAXC, "asis_predict_mask_tiles: C=%d must be in 1..%d", C, MAXC);
+  ASIS_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Lh >= 1 && Lw >= 1,
+               "asis_predict_mask_tiles: non-positive size B=%d H=%d W=%d Lh=%d Lw=%d", B, H, W, Lh, Lw);
+  ASIS_REQUIRE(B <= 65535 && H <= 16384 && W <= 16384 && Lh <= 16384 && Lw <= 16384,
+               "asis_predict_mask_tiles: sizes above 16384 (batch above 65535)");
+  ASIS_REQUIRE(blend == 0 || blend == 1, "asis_predict_mask_tiles: blend=%d must be 0 (uniform) or 1 (ramp)", blend);
+  ASIS_REQUIRE(ramp >= 1.f && ramp <= 16384.f, "asis_predict_mask_tiles: ramp=%g must be in 1..16384 working pixels", (double)ramp);
+  TileSet ts = {};
+  ts.K = K;
+  ts.Lh = Lh;
+  ts.Lw = Lw;
+  ts.ramp_mode = blend;
+  ts.R = ramp;
+  uintptr_t la = 0;
+  for (int k = 0; k < K; ++k) {
+    const int oy = rects[k * 4], ox = rects[k * 4 + 1], sy = rects[k * 4 + 2], sx = rects[k * 4 + 3];
+    ASIS_REQUIRE(logits[k], "asis_predict_mask_tiles: logits[%d] is a null pointer", k);
+    ASIS_REQUIRE(hs[k] >= 1 && ws[k] >= 1, "asis_predict_mask_tiles: non-positive size of tile %d: hs=%d ws=%d", k, hs[k], ws[k]);
+    ASIS_REQUIRE(hs[k] <= 16384 && ws[k] <= 16384, "asis_predict_mask_tiles: tile %d: hs=%d ws=%d above 16384", k, hs[k], ws[k]);
+    ASIS_REQUIRE(sy >= 1 && sx >= 1 && sy <= Lh && sx <= Lw && oy >= 0 && ox >= 0 && oy <= Lh - sy && ox <= Lw - sx,
+                 "asis_predict_mask_tiles: rectangle of tile %d (oy=%d ox=%d sy=%d sx=%d) is empty or outside the working grid %dx%d",
+                 k, oy, ox, sy, sx, Lh, Lw);
+    ts.p[k] = logits[k];
+    ts.h[k] = hs[k];
+    ts.w[k] = ws[k];
+    ts.oy[k] = oy;
+    ts.ox[k] = ox;
+    ts.sy[k] = sy;
+    ts.sx[k] = sx;
+    ts.flip[k] = flips[k] != 0;
+    la |= reinterpret_cast<uintptr_t>(logits[k]);
+  }
+  // the rule: the row intervals of the rectangles cover [0, Lh) and their column intervals cover [0, Lw).  Necessary for every
+  // pixel to lie in a tile, and sufficient for a set that holds a full grid of windows (every row origin with every column origin)
+  ASIS_REQUIRE(intervals_cover(rects, K, 0, Lh), "asis_predict_mask_tiles: the tiles' rows do not cover the working grid's %d rows", Lh);
+  ASIS_REQUIRE(intervals_cover(rects, K, 1, Lw), "asis_predict_mask_tiles: the tiles' columns do not cover the working grid's %d columns",
+               Lw);
+  ASIS_REQUIRE(!overlay || (frames && palette && alpha),
+               "asis_predict_mask_tiles: overlay requested without frames, palette [C][3] and alpha [C]");
+  ASIS_REQUIRE(!counts || (target && lut),
+               "asis_predict_mask_tiles: counts requested without a raw mask and its 256-entry label table");
+  ASIS_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 7) == 0, "asis_predict_mask_tiles: counts must be 8-byte aligned");
+  const int quads = (W + PX - 1) / PX;
+  const int64_t n = (int64_t)H * quads;
+  // as asis_predict_mask_views: the wide loads need all K addresses aligned
+  const int V = (C % 4 == 0 && la % 16 == 0) ? 4 : ((C % 2 == 0 && la % 8 == 0) ? 2 : 1);
+  const int CB = C <= 4 ? 4 : (C <= 8 ? 8 : 16);
+  const dim3 grid((unsigned)((n + 255) / 256), (unsigned)B);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+#define ASIS_TILES_LAUNCH(VV, CC)                                                                                                \
+  hipLaunchKernelGGL((predict_tiles_kernel<VV, CC>), grid, dim3(256), 0, s, ts, C, H, W, encode, mask, confidence, frames, palette, \
+                     alpha, overlay, target, lut, cnt)
+#define ASIS_TILES_BUCKET(VV)          \
+  do {                                 \
+    if (CB == 4) ASIS_TILES_LAUNCH(VV, 4);       \
+    else if (CB == 8) ASIS_TILES_LAUNCH(VV, 8);  \
+    else ASIS_TILES_LAUNCH(VV, 16);    \
+  } while (0)
+  if (V == 4) ASIS_TILES_BUCKET(4);
+  else if (V == 2) ASIS_TILES_BUCKET(2);
+  else ASIS_TILES_BUCKET(1);
+#undef ASIS_TILES_BUCKET
+#undef ASIS_TILES_LAUNCH
+  ASIS_CHECK_LAUNCH("asis_predict_mask_tiles");
   return ASIS_OK;
 }

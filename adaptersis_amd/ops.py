@@ -1943,6 +1943,92 @@ def predict_mask_views(logits, size, encode=None, *, flips=None, confidence: boo
     return mask if len(out) == 1 else out
 
 
+PREDICT_MAX_TILES = 32
+PREDICT_BLENDS = ("uniform", "ramp")       # the ABI's blend = the index
+
+
+def predict_mask_tiles(logits, tiles, work, size, encode=None, *, blend: str = "ramp", ramp=None, confidence: bool = False,
+                       frames: Optional[torch.Tensor] = None, palette=None, alpha=None, target: Optional[torch.Tensor] = None,
+                       lut=None):
+    """Sliding-window prediction in one pass (csrc/predict.hip): ``logits`` = 1..32 tiles of one batch, each a contiguous fp32 NHWC
+    map [B,h_k,w_k,C] of its own size; ``tiles[k]`` = (oy, ox, sy, sx, flip): the integer rectangle of the working grid ``work`` =
+    (Lh, Lw) (or an int) that map k holds, and whether it was predicted from the mirrored crop.  Per native pixel (y, x) of
+    ``size`` = (H, W): u = (y + 0.5) * Lh / H, (x + 0.5) * Lw / W on the working grid; every tile whose rectangle holds u is
+    sampled there (``align_corners=False`` sampling of its map, clamped inside the tile; mirrored columns for a mirrored tile: bit
+    for bit the un-mirrored map ``v.flip(2)``), a softmax over the classes in fp32, and the probabilities are summed with the
+    weight g, tiles in list order; -> uint8 [B,H,W] = ``encode[argmax_c sum]``, ties to the lowest class.  ``blend="uniform"``:
+    g = 1.  ``blend="ramp"``: g = gy * gx, gy = min(distance to the tile's two row edges, ramp) / ramp, an edge on the border of
+    the working grid not counting; ``ramp`` >= 1 in working pixels (None: a third of the smallest rectangle side, at least 1).
+    The rectangles' row intervals must cover [0, Lh) and their column intervals [0, Lw) (enough for a full grid of windows: every
+    pixel then lies in a tile).  ``confidence=True`` -> also uint8 [B,H,W] = floor(255 * weighted mean probability of the chosen
+    class + 0.5).  ``size``, ``encode``, ``frames`` / ``palette`` / ``alpha`` and ``target`` / ``lut`` as in ``predict_mask``.
+    -> mask, or (mask[, confidence][, overlay][, counts])."""
+    import ctypes
+    op = "predict_mask_tiles"
+    if torch.is_tensor(logits) or not isinstance(logits, (list, tuple)):
+        raise ValueError(f"{op}: logits must be a list of 1..{PREDICT_MAX_TILES} NHWC tensors, got {type(logits).__name__}")
+    K = len(logits)
+    if not 1 <= K <= PREDICT_MAX_TILES:
+        raise ValueError(f"{op}: logits holds {K} tiles, supported 1..{PREDICT_MAX_TILES}")
+    tiles = list(tiles)
+    if len(tiles) != K:
+        raise ValueError(f"{op}: tiles has {len(tiles)} entries for {K} maps in logits")
+    if isinstance(work, int):
+        work = (work, work)
+    if len(work) != 2 or int(work[0]) < 1 or int(work[1]) < 1:
+        raise ValueError(f"{op}: work must be a positive int or (Lh, Lw), got {work!r}")
+    Lh, Lw = int(work[0]), int(work[1])
+    rects, flips = [], []
+    for k, t in enumerate(tiles):
+        if len(t) != 5:
+            raise ValueError(f"{op}: tiles[{k}] must be (oy, ox, sy, sx, flip), got {t!r}")
+        oy, ox, sy, sx = (int(v) for v in t[:4])
+        if sy < 1 or sx < 1 or oy < 0 or ox < 0 or oy + sy > Lh or ox + sx > Lw:
+            raise ValueError(f"{op}: tiles[{k}] = {tuple(t)!r} is empty or outside the working grid work = {(Lh, Lw)}")
+        rects += [oy, ox, sy, sx]
+        flips.append(bool(t[4]))
+    for axis, L, name in ((0, Lh, "rows"), (1, Lw, "columns")):
+        reach = 0
+        for o, e in sorted((rects[4 * k + axis], rects[4 * k + axis] + rects[4 * k + axis + 2]) for k in range(K)):
+            if o > reach:
+                break
+            reach = max(reach, e)
+        if reach < L:
+            raise ValueError(f"{op}: tiles leave the working grid's {name} from {reach} on uncovered (work = {(Lh, Lw)})")
+    if blend not in PREDICT_BLENDS:
+        raise ValueError(f"{op}: blend must be one of {PREDICT_BLENDS}, got {blend!r}")
+    if ramp is None:
+        ramp = max(min(min(rects[4 * k + 2], rects[4 * k + 3]) for k in range(K)) // 3, 1)
+    ramp = float(ramp)
+    if not ramp >= 1.0:
+        raise ValueError(f"{op}: ramp must be at least 1 working pixel, got {ramp!r}")
+    for k, v in enumerate(logits):
+        if not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.float32 or not v.is_contiguous():
+            raise ValueError(f"{op}: logits[{k}] must be a contiguous float32 NHWC tensor [B,h,w,C]")
+        if v.shape[0] != logits[0].shape[0] or v.shape[3] != logits[0].shape[3]:
+            raise ValueError(f"{op}: logits[{k}] is {list(v.shape)}, logits[0] {list(logits[0].shape)}: every tile has the same "
+                             "B and C")
+        if v.device != logits[0].device:
+            raise ValueError(f"{op}: logits[{k}] on {v.device}, logits[0] on {logits[0].device}")
+    _dev(logits[0], frames, target)
+    B, Cc = int(logits[0].shape[0]), int(logits[0].shape[3])
+    dev = logits[0].device
+    H, W, enc, mask, pal, alp, overlay, lut, counts = _predict_outputs(op, B, Cc, size, dev, encode, frames, palette, alpha, target,
+                                                                       lut)
+    conf = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if confidence else None
+    ptrs = (ctypes.c_void_p * K)(*[v.data_ptr() for v in logits])
+    hs = (ctypes.c_int * K)(*[int(v.shape[1]) for v in logits])
+    ws = (ctypes.c_int * K)(*[int(v.shape[2]) for v in logits])
+    rc = (ctypes.c_int * (4 * K))(*rects)
+    fl = (ctypes.c_int * K)(*[int(f) for f in flips])
+    check(lib().asis_predict_mask_tiles(_stream(), ptrs, hs, ws, rc, fl, K, Lh, Lw, PREDICT_BLENDS.index(blend), ramp, B, Cc, H, W,
+                                        enc.data_ptr(), mask.data_ptr(), _p(conf), _p(frames), _p(pal), _p(alp), _p(overlay),
+                                        _p(target), _p(lut), _p(counts)), "asis_predict_mask_tiles")
+    out = ((mask,) + ((conf,) if conf is not None else ()) + ((overlay,) if overlay is not None else ())
+           + ((counts,) if counts is not None else ()))
+    return mask if len(out) == 1 else out
+
+
 SURFACE_MAX_TOLERANCES = 8
 SURFACE_WORKSPACE_BYTES = 512 << 20    # bound on the vertical-distance maps of one asis_surface_stats call (csrc/surface.hip)
 

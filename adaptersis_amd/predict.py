@@ -36,6 +36,17 @@ view with that view's batch statistics, so the views of a frame differ by more t
 still depends on the batch it is predicted in.  Without any of the three flags the tool calls ``SegEngine.predict`` and writes
 exactly the files it wrote before they existed; ``metrics.json`` holds ``"views": [[size, flip], ...]`` only when views were used.
 
+Sliding-window prediction (``--slide_size L`` [``--slide_stride T``] [``--slide_blend ramp|uniform``] [``--slide_context``]): the
+frame is resized to L x L (``ops.frame_resize``), the network runs at its own input size S = ``--imsize`` on the S x S windows of
+that working frame whose origins ``plan_tiles`` lists (stride T, default 2 S // 3; the last window of a row or column is pulled
+back to end at L), and the class probabilities of the windows are blended at native size in one fused pass
+(``SegEngine.predict_tiles``, ``ops.predict_mask_tiles``): each window is sampled once, at the native pixel's place in it, and
+weighs 1 (``uniform``) or ramps down over S - T working pixels towards its inner edges (``ramp``, the default).
+``--slide_context`` adds the whole frame at S x S (the very input of the plain path) as one more tile, ``--tta_flip`` follows every
+tile with its mirrored twin, ``--confidence`` works as above; ``--tta_sizes`` cannot be combined with it.  Every tile is its own
+forward pass with its own BatchNorm batch statistics, as every view is.  ``metrics.json`` holds ``"tiles": {"size", "stride",
+"blend", "context", "flip", "count"}`` only in this mode.
+
 Single process, single GPU: prediction is not sharded over ranks.
 """
 from __future__ import annotations
@@ -58,6 +69,8 @@ DATASETS = ("endovis2017", "endovis2018", "autolapro", "robomis")
 MAX_WRITERS = 8
 DEFAULT_TOLERANCES = (1.0, 2.0, 5.0)
 MAX_VIEWS = 8
+MAX_TILES = 32
+BLENDS = ("ramp", "uniform")
 
 
 def get_args_parser():
@@ -90,6 +103,16 @@ def get_args_parser():
                    help="test-time augmentation: input sizes of the views (default: --imsize alone); each as --imsize is given to train")
     p.add_argument("--confidence", action="store_true",
                    help="also write <stem>_conf.png (mode L): 255 x the mean probability of the chosen class over the views")
+    p.add_argument("--slide_size", default=None, type=int, metavar="L",
+                   help="sliding-window prediction: resize every frame to L x L and predict --imsize windows of it, blended at native "
+                        "size (L >= --imsize)")
+    p.add_argument("--slide_stride", default=None, type=int, metavar="T",
+                   help="with --slide_size: distance of the window origins in pixels of the L x L frame (default 2 * imsize // 3)")
+    p.add_argument("--slide_blend", default=None, choices=BLENDS,
+                   help="with --slide_size: weight of a window at a pixel: ramp (default; falls off over imsize - T pixels towards the "
+                        "window's inner edges) or uniform")
+    p.add_argument("--slide_context", action="store_true",
+                   help="with --slide_size: one more tile, the whole frame at --imsize (the input of the plain prediction)")
     p.add_argument("--seed", default=None, type=int,
                    help="torch seed the TRAINING process was given before it built its modules; required when the checkpoint lacks "
                         "cross_vit / cross_cnn / backbone_encoder (the training command lines do not seed, so only a caller that "
@@ -120,6 +143,60 @@ def views_of(args) -> Optional[List[Tuple[int, bool]]]:
     if not flip and sizes is None and not getattr(args, "confidence", False):
         return None
     return plan_views(args.imsize, sizes, flip)
+
+
+# ---- tiles ------------------------------------------------------------------------------------------------------------------
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def slide_origins(L: int, S: int, stride: int) -> List[int]:
+    """Window origins along one axis: n = max(L - S + stride - 1, 0) // stride + 1 windows at min(i * stride, L - S)."""
+    return [min(i * stride, L - S) for i in range(max(L - S + stride - 1, 0) // stride + 1)]
+
+
+def plan_tiles(L: int, S: int, stride: int, context: bool, flip: bool) -> List[Tuple[int, int, int, int, bool]]:
+    """The tiles of sliding-window prediction as (oy, ox, sy, sx, mirrored) on the L x L working frame: the S x S windows at
+    ``slide_origins`` in row-major order, then with ``context`` the whole frame (0, 0, L, L); with ``flip`` every tile is followed
+    by its mirrored twin.  ``S`` < 1, ``L`` < ``S``, a ``stride`` outside 1..S or more than ``MAX_TILES`` tiles raise."""
+    for name, v in (("--imsize", S), ("--slide_size", L), ("--slide_stride", stride)):
+        if not _is_int(v):
+            raise ValueError(f"{name}: {v!r} is not an integer")
+    L, S, stride = int(L), int(S), int(stride)
+    if S < 1:
+        raise ValueError(f"--imsize: {S} is not a positive input size")
+    if L < S:
+        raise ValueError(f"--slide_size: {L} is smaller than the network input size --imsize {S}")
+    if not 1 <= stride <= S:
+        raise ValueError(f"--slide_stride: {stride} must be in 1..{S} (--imsize): a larger stride leaves pixels between the windows")
+    org = slide_origins(L, S, stride)
+    count = (len(org) ** 2 + bool(context)) * (2 if flip else 1)
+    if count > MAX_TILES:
+        raise ValueError(f"--slide_size / --slide_stride / --slide_context / --tta_flip: {count} tiles, at most {MAX_TILES} are "
+                         "supported")
+    rects = [(oy, ox, S, S) for oy in org for ox in org] + ([(0, 0, L, L)] if context else [])
+    return [r + (f,) for r in rects for f in ((False, True) if flip else (False,))]
+
+
+def tiles_of(args) -> Optional[dict]:
+    """None without ``--slide_size``, else the checked plan: {"size", "stride", "blend", "context", "flip", "ramp", "tiles"}.
+    ``--tta_sizes`` with ``--slide_size``, and the other ``--slide_*`` flags without it, raise."""
+    L = getattr(args, "slide_size", None)
+    stride, blend, context = (getattr(args, n, None) for n in ("slide_stride", "slide_blend", "slide_context"))
+    if L is None:
+        for name, given in (("--slide_stride", stride is not None), ("--slide_blend", blend is not None),
+                            ("--slide_context", bool(context))):
+            if given:
+                raise ValueError(f"{name} needs --slide_size")
+        return None
+    if getattr(args, "tta_sizes", None) is not None:
+        raise ValueError("--tta_sizes cannot be combined with --slide_size: the windows are predicted at --imsize")
+    S = args.imsize
+    stride = 2 * S // 3 if stride is None else stride
+    flip = bool(getattr(args, "tta_flip", False))
+    tiles = plan_tiles(L, S, stride, bool(context), flip)
+    return {"size": int(L), "stride": int(stride), "blend": blend or BLENDS[0], "context": bool(context), "flip": flip,
+            "ramp": max(int(S) - int(stride), 1), "tiles": tiles}
 
 
 # ---- file list and batches ---------------------------------------------------------------------------------------------------
@@ -313,26 +390,54 @@ def _network_input(frames: torch.Tensor, size: int, flip: bool = False) -> torch
     """Native uint8 frames on the device -> the float batch validation feeds the network at ``size`` (mirrored when ``flip``)."""
     from . import ops
     small, _ = ops.frame_resize(frames, None, size)
+    return _normalised(small, flip)
+
+
+def _normalised(small: torch.Tensor, flip: bool = False) -> torch.Tensor:
+    """uint8 [B,S,S,3] on the device -> validation's float batch (mirrored when ``flip``)."""
     if flip:
-        small = small.flip(2).contiguous()
+        small = small.flip(2)
+    small = small.contiguous()
     inp, _ = _t._to_device_batch(small, torch.zeros(small.shape[:3], dtype=torch.uint8, device=small.device), train=False)
     return inp
 
 
-def predict_batch(engine: SegEngine, frames_u8: torch.Tensor, masks_u8: Optional[torch.Tensor], args, lut, views=None):
+def tile_inputs(frames: torch.Tensor, S: int, plan: dict) -> List[torch.Tensor]:
+    """Native uint8 frames on the device -> the network input of every tile of ``plan`` (``tiles_of``): S x S windows of the frame
+    resized to the working size, and for the context tile the frame resized to S x S (the input of the plain path)."""
+    from . import ops
+    L = plan["size"]
+    work, _ = ops.frame_resize(frames, None, L)
+    whole = None
+    out = []
+    for oy, ox, sy, sx, flip in plan["tiles"]:
+        if (sy, sx) == (S, S):
+            out.append(_normalised(work[:, oy:oy + S, ox:ox + S], flip))
+        else:
+            if whole is None:
+                whole, _ = ops.frame_resize(frames, None, S)
+            out.append(_normalised(whole, flip))
+    return out
+
+
+def predict_batch(engine: SegEngine, frames_u8: torch.Tensor, masks_u8: Optional[torch.Tensor], args, lut, views=None, tiles=None):
     """Native uint8 [B,H,W,3] (host) -> device outputs of ``SegEngine.predict``: mask[, overlay][, counts]; with ``views``
-    (``plan_views``) those of ``SegEngine.predict_views``: mask[, confidence][, overlay][, counts]."""
+    (``plan_views``) those of ``SegEngine.predict_views``, with ``tiles`` (``tiles_of``) those of ``SegEngine.predict_tiles``:
+    mask[, confidence][, overlay][, counts]."""
     C = args.num_classes
     frames = frames_u8.cuda(non_blocking=True).contiguous()
     B, H, W, _ = frames.shape
-    if views is None:
+    if views is None and tiles is None:
         inp = _network_input(frames, args.imsize)
     kw = dict(encode=_fr.encode_table(args.encode, C))
     if args.overlay:
         kw.update(frames=frames, alpha=_fr.default_alpha(C, args.alpha))
     if masks_u8 is not None:
         kw.update(target=masks_u8.cuda(non_blocking=True).contiguous(), lut=lut)
-    if views is None:
+    if tiles is not None:
+        out = engine.predict_tiles(tile_inputs(frames, args.imsize, tiles), tiles["tiles"], tiles["size"], (H, W),
+                                   blend=tiles["blend"], ramp=tiles["ramp"], confidence=bool(args.confidence), **kw)
+    elif views is None:
         out = engine.predict(inp, size=(H, W), **kw)
     else:
         out = engine.predict_views([_network_input(frames, s, f) for s, f in views], [f for _, f in views], (H, W),
@@ -395,8 +500,9 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     the writer threads), "drain_seconds" (waiting for the writers after the last batch), "frames_per_second"}."""
     _fr.encode_table(args.encode, args.num_classes)          # argument errors before any model is built
     tolerances = surface_tolerances(args)
-    views = views_of(args)
-    with_conf = views is not None and bool(args.confidence)
+    tiles = tiles_of(args)
+    views = None if tiles is not None else views_of(args)
+    with_conf = (views is not None or tiles is not None) and bool(args.confidence)
     meter = None
     if tolerances is not None:
         from .segloss.surface import SurfaceMeter
@@ -412,7 +518,7 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
             fr, mk = frames.load_batch(idx)
             if mk is not None and meter is not None:
                 mk = mk.cuda(non_blocking=True).contiguous()     # predict_batch's upload, made here to keep the device copy
-            out = list(predict_batch(engine, fr, mk, args, frames.lut, views))
+            out = list(predict_batch(engine, fr, mk, args, frames.lut, views, tiles))
             if meter is not None:
                 surface_batch(meter, out[0], mk, args, frames.lut)
             mask = out.pop(0).cpu().numpy()
@@ -438,6 +544,8 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
         metrics["frames"] = len(frames.rel)
         if views is not None:
             metrics["views"] = [[s, f] for s, f in views]
+        if tiles is not None:
+            metrics["tiles"] = {**{k: tiles[k] for k in ("size", "stride", "blend", "context", "flip")}, "count": len(tiles["tiles"])}
         if meter is not None:
             metrics["surface"] = meter.result()
         os.makedirs(args.pred_dir, exist_ok=True)

@@ -764,6 +764,27 @@ int asis_predict_mask_views(void* stream, const float* const* logits, const int*
                             const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay, const uint8_t* target,
                             const uint8_t* lut, int64_t* counts);
 
+/* Sliding-window prediction (csrc/predict.hip): K = 1..32 tiles of one batch, tile k an fp32 NHWC map [B, hs[k], ws[k], C] that
+ * holds the integer rectangle rects[4k..4k+3] = (oy, ox, sy, sx) of a working grid Lh x Lw (0 <= oy, oy + sy <= Lh, sy >= 1;
+ * likewise in x), fused into one mask at (H, W) without any [B,H,W,C] map.
+ *   logits, hs, ws, rects, flips: HOST arrays (K, K, K, 4 K, K entries); the kernel receives them by value in its arguments.
+ *   Per native pixel (y, x), in fp32: uy = (y + 0.5) * (Lh / H), ux = (x + 0.5) * (Lw / W); tile k covers the pixel iff
+ *     oy <= uy < oy + sy and ox <= ux < ox + sx; its source row is max(0, (uy - oy) * (hs[k] / sy) - 0.5) with the taps floor,
+ *     min(floor + 1, hs[k] - 1) and the fraction (columns likewise; flips[k] != 0 reads columns ws[k] - 1 - i), i.e.
+ *     align_corners=False sampling clamped inside the tile; the four-tap blend of asis_predict_mask, p = softmax over C in fp32,
+ *     acc[c] += g * p[c], wsum += g, tiles in list order (bit-identical from call to call).
+ *   blend 0 (uniform): g = 1.  blend 1 (ramp): g = gy * gx, gy = min(uy - oy, oy + sy - uy, ramp) / ramp, where an edge that
+ *     lies on the border of the working grid (oy == 0, oy + sy == Lh) counts as infinitely far; ramp >= 1 working pixels.
+ *   mask uint8 [B,H,W] = encode[argmax_c acc[c]], ties to the lowest class; confidence (optional, NULL = off) uint8 [B,H,W] =
+ *     (uint8)(255 * acc[pred] / wsum + 0.5).  overlay and counts: exactly those of asis_predict_mask.
+ *   Refused: a tile set whose row intervals [oy, oy + sy) do not cover [0, Lh) or whose column intervals do not cover [0, Lw)
+ *     (necessary for every pixel to lie in a tile; sufficient when the set holds a full grid of windows). */
+int asis_predict_mask_tiles(void* stream, const float* const* logits, const int* hs, const int* ws, const int* rects,
+                            const int* flips, int K, int Lh, int Lw, int blend, float ramp, int B, int C, int H, int W,
+                            const uint8_t* encode, uint8_t* mask, uint8_t* confidence, const uint8_t* frames,
+                            const uint8_t* palette, const uint8_t* alpha, uint8_t* overlay, const uint8_t* target,
+                            const uint8_t* lut, int64_t* counts);
+
 /* Boundary metrics (csrc/surface.hip): exact squared Euclidean distance transform of the class boundaries at native size and the
  * per (frame, class) statistics behind Dice, normalised surface distance, Hausdorff and mean surface distance.
  *   pred, target uint8 [B,H,W] raw pixel values; pred_lut, lut uint8 [256] their label tables; P = (pred_lut[pred] == c),

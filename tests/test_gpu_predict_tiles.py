@@ -1,0 +1,540 @@
+"""GPU: sliding-window prediction — ``ops.predict_mask_tiles`` (csrc/predict.hip) against the formulas of its header restated in
+torch float64 on the CPU (gather the four taps, softmax, weighted mean), its coverage bookkeeping, stitching against
+``ops.predict_mask`` on the map the tiles were cut from, exact properties (mirrored tiles, repeated tiles, repeated calls, ties),
+tails and unaligned addresses, overlay and counts against numpy, argument errors; ``SegEngine.predict_tiles`` against ``predict``
+and ``eval_logits``; the ``adaptersis_amd.predict`` entry point with ``--slide_size`` on a two-size EndoVis2017-style PNG tree."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+from adaptersis_amd import ops
+from adaptersis_amd.tools import frame_resize as FR
+
+pytestmark = pytest.mark.gpu
+
+TAU = 2e-4            # float64 top-2 margin of the blended probability below which a pixel is left out (test_gpu_predict_views.py:
+                      # same taps, same softmax, so the same 20 x torch's own fp32 error of 1e-5)
+EDGE = 1e-3           # no native pixel of a case may lie this close (in working pixels) to a tile edge: `u < o + s` is discontinuous
+BLENDS = ("uniform", "ramp")
+
+
+# ---- the float64 restatement ------------------------------------------------------------------------------------------------
+def origins(L, S, T):
+    return [min(i * T, L - S) for i in range(max(L - S + T - 1, 0) // T + 1)]
+
+
+def window_tiles(work, S, T, context=False, flip=False):
+    """(oy, ox, S, S) windows in row-major order, then the whole working grid; with ``flip`` each followed by its mirrored twin."""
+    Lh, Lw = work
+    rects = [(oy, ox, S, S) for oy in origins(Lh, S, T) for ox in origins(Lw, S, T)] + ([(0, 0, Lh, Lw)] if context else [])
+    return [r + (f,) for r in rects for f in ((False, True) if flip else (False,))]
+
+
+def _axis64(n, L, o, s, size, R):
+    """One axis in float64 -> (covered [n], i0, i1 [n] long, l1 [n], ramp weight [n], distance to the nearest of the two edges [n])."""
+    u = (torch.arange(n, dtype=torch.float64) + 0.5) * L / n
+    cov = (u >= o) & (u < o + s)
+    src = ((u - o) * size / s - 0.5).clamp(min=0)
+    i0 = src.floor().clamp(max=size - 1)
+    i1 = (i0 + 1).clamp(max=size - 1)
+    inf = torch.full_like(u, float("inf"))
+    d0 = inf if o == 0 else u - o
+    d1 = inf if o + s == L else (o + s) - u
+    g = torch.minimum(torch.minimum(d0, d1), torch.full_like(u, float(R))) / R
+    return cov, i0.long().clamp(min=0), i1.long().clamp(min=0), src - i0, g, torch.minimum((u - o).abs(), (u - (o + s)).abs())
+
+
+def blend64(maps, tiles, work, H, W, blend, R):
+    """-> (prob float64 [B,C,H,W] = sum_k g_k softmax(sample_k) / sum_k g_k, weights float64 [K,H,W] (0 where tile k does not cover),
+    the smallest distance of a pixel centre to a tile edge in working pixels)."""
+    Lh, Lw = work
+    B, C = maps[0].shape[0], maps[0].shape[3]
+    acc = torch.zeros((B, H, W, C), dtype=torch.float64)
+    weights, edge = [], float("inf")
+    for v, (oy, ox, sy, sx, f) in zip(maps, tiles):
+        x = v.double().flip(2) if f else v.double()                              # what the mirrored crop's map says about the crop
+        h, w = x.shape[1:3]
+        cy, y0, y1, ly, gy, ey = _axis64(H, Lh, oy, sy, h, R)
+        cx, x0, x1, lx, gx, ex = _axis64(W, Lw, ox, sx, w, R)
+        edge = min(edge, float(ey.min()), float(ex.min()))
+        r0, r1 = x[:, y0], x[:, y1]                                              # [B,H,w,C]
+        lx_, ly_ = lx[None, None, :, None], ly[None, :, None, None]
+        z = (1 - ly_) * ((1 - lx_) * r0[:, :, x0] + lx_ * r0[:, :, x1]) + ly_ * ((1 - lx_) * r1[:, :, x0] + lx_ * r1[:, :, x1])
+        g = (cy[:, None] & cx[None, :]).double() * (gy[:, None] * gx[None, :] if blend == "ramp" else 1.0)
+        acc += g[None, :, :, None] * z.softmax(-1)
+        weights.append(g)
+    weights = torch.stack(weights)
+    wsum = weights.sum(0)
+    assert float(wsum.min()) > 0, "a pixel without weight"
+    return (acc / wsum[None, :, :, None]).permute(0, 3, 1, 2), weights, edge
+
+
+def margin_rule(prob):
+    """-> (argmax [B,H,W], sure [B,H,W] = top-2 margin >= TAU, max [B,H,W])."""
+    top = prob.topk(2, dim=1).values
+    return prob.argmax(1), (top[:, 0] - top[:, 1]) >= TAU, top[:, 0]
+
+
+def _maps(C, B, shapes, seed, scale=3.0):
+    g = torch.Generator().manual_seed(seed)
+    return [(scale * torch.randn((B, h, w, C), generator=g)).contiguous() for h, w in shapes]
+
+
+# name -> (work, S, T, context, flip, map size of a window, map size of the context tile, native size)
+CASES = {
+    "A": ((96, 96), 48, 32, False, False, (24, 24), None, (134, 206)),
+    "B": ((80, 80), 48, 32, True, True, (17, 17), (21, 19), (301, 517)),
+    "C": ((112, 112), 48, 16, True, False, (24, 24), (24, 24), (97, 61)),
+    "D": ((48, 48), 48, 48, False, False, (37, 53), None, (131, 203)),
+    "E": ((64, 96), 48, 24, False, True, (24, 24), None, (256, 320)),
+}
+COUNTS = {"A": 9, "B": 10, "C": 26, "D": 1, "E": 12}
+
+
+@functools.lru_cache(maxsize=None)
+def _case_maps(name, C):
+    work, S, T, context, flip, hw, hw_ctx, _ = CASES[name]
+    tiles = window_tiles(work, S, T, context, flip)
+    assert len(tiles) == COUNTS[name]
+    n_ctx = (2 if flip else 1) if context else 0                                 # the context tile (and its twin) comes last
+    shapes = [hw] * (len(tiles) - n_ctx) + [hw_ctx] * n_ctx
+    return _maps(C, 1, shapes, seed=8765 + C), tiles
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name, C, blend):
+    work, S, T, _, _, _, _, (H, W) = CASES[name]
+    maps, tiles = _case_maps(name, C)
+    R = max(S - T, 1)
+    prob, _, edge = blend64(maps, tiles, work, H, W, blend, R)
+    return maps, tiles, work, H, W, R, margin_rule(prob), edge
+
+
+# ---- 1. against float64 on the CPU ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend", BLENDS)
+@pytest.mark.parametrize("name", sorted(CASES))
+@pytest.mark.parametrize("C", [2, 3, 8, 11, 16])
+def test_mask_and_confidence_vs_float64(dev, C, name, blend):
+    """Pixels whose float64 top-2 margin of the blended probability is below TAU are left out; every other pixel must agree and
+    the confidence is within one level of round(255 * max) everywhere.  At most 1 % may be left out; the float64 reference alone
+    must stay at or below 0.5 % for these seeds (the worst here: case C, 16 classes, uniform, where 26 averaged tiles flatten the
+    distribution).  No pixel centre may lie within EDGE of a tile edge, where coverage itself would hang on rounding."""
+    maps, tiles, work, H, W, R, (want, sure, pmax), edge = _case(name, C, blend)
+    assert edge >= EDGE, f"a pixel centre {edge:.2e} working pixels from a tile edge"
+    left_out = 1.0 - float(sure.double().mean())
+    assert left_out <= 0.005, f"the float64 reference leaves out {100 * left_out:.3f} %: reseed"
+    mask, conf = ops.predict_mask_tiles([v.to(dev) for v in maps], tiles, work, (H, W), blend=blend, ramp=R, confidence=True)
+    assert mask.dtype == torch.uint8 and conf.dtype == torch.uint8 and tuple(mask.shape) == tuple(conf.shape) == (1, H, W)
+    wrong = int(((mask.cpu().long() != want) & sure).sum())
+    conf_err = int((conf.cpu().long() - torch.round(255.0 * pmax).long()).abs().max())
+    print(f"case {name} C={C} K={len(tiles)} {blend} -> {H}x{W}: nearest edge {edge:.4f}, left out {100 * left_out:.4f} %, "
+          f"disagreements outside the margin {wrong}, largest confidence difference {conf_err} levels")
+    assert left_out <= 0.01
+    assert wrong == 0
+    assert conf_err <= 1
+    assert torch.equal(mask, ops.predict_mask_tiles([v.to(dev) for v in maps], tiles, work, (H, W), blend=blend, ramp=R))
+
+
+# ---- 2. coverage bookkeeping ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", [(97, 131), (203, 64)])
+def test_coverage_bookkeeping(dev, size):
+    """A 2 x 2 grid of windows, tile k says class k with +40: under ``uniform`` a pixel of one tile gets that tile's class and a
+    pixel of an overlap the lowest class among its tiles (their sums are equal: 1 + e^-40 rounds to 1 in any order); under ``ramp``
+    the class of the heaviest tile wherever the two largest float64 weights differ by more than 1e-3."""
+    work, S, T = (80, 80), 48, 32
+    tiles = window_tiles(work, S, T)
+    assert [t[:2] for t in tiles] == [(0, 0), (0, 32), (32, 0), (32, 32)]
+    maps = []
+    for k in range(4):
+        m = torch.zeros((2, 12, 13, 4))
+        m[..., k] = 40.0
+        maps.append(m.to(dev))
+    H, W = size
+    _, weights, edge = blend64([m.cpu() for m in maps], tiles, work, H, W, "uniform", 16)
+    assert edge >= EDGE
+    cover = weights > 0                                                          # [4,H,W]
+    assert set(cover.sum(0).unique().tolist()) == {1, 2, 4}
+    lowest = cover.long().argmax(0)                                              # the first covering tile = the lowest class
+    got = ops.predict_mask_tiles(maps, tiles, work, size, blend="uniform")
+    assert torch.equal(got.cpu().long(), lowest[None].expand(2, -1, -1))
+    _, weights, _ = blend64([m.cpu() for m in maps], tiles, work, H, W, "ramp", 16)
+    top = weights.topk(2, dim=0).values
+    clear = (top[0] - top[1]) > 1e-3
+    assert float(clear.double().mean()) > 0.5
+    got = ops.predict_mask_tiles(maps, tiles, work, size, blend="ramp", ramp=16).cpu().long()
+    assert torch.equal(got[:, clear], weights.argmax(0)[clear][None].expand(2, -1))
+
+
+# ---- 3. stitching -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend", BLENDS)
+@pytest.mark.parametrize("size", [(131, 203), (301, 517)])
+def test_stitching_reproduces_the_whole_map(dev, blend, size):
+    """Nine 48 x 48 tiles cut from one 96 x 96 map, one map pixel per working pixel: further than one working pixel from every
+    tile edge each covering tile reads the four taps ``ops.predict_mask`` reads from the whole map, so every tile says what the
+    whole map says and so does their blend — away from that op's own near-ties (top-2 logit margin 1e-5)."""
+    work, S, T = (96, 96), 48, 24
+    G = _maps(8, 2, [(96, 96)], seed=31)[0].to(dev)
+    tiles = window_tiles(work, S, T)
+    assert len(tiles) == 9
+    maps = [G[:, oy:oy + S, ox:ox + S].contiguous() for oy, ox, _, _, _ in tiles]
+    H, W = size
+    edges = torch.tensor(sorted({e for oy, ox, sy, sx, _ in tiles for e in (oy, oy + sy)}), dtype=torch.float64)
+    uy = (torch.arange(H, dtype=torch.float64) + 0.5) * 96 / H
+    ux = (torch.arange(W, dtype=torch.float64) + 0.5) * 96 / W
+    far = (((uy[:, None] - edges).abs().min(1).values > 1.0)[:, None] & ((ux[:, None] - edges).abs().min(1).values > 1.0)[None, :])
+    assert 0.8 < float(far.double().mean()) < 1.0
+    top = ops.resize_bilinear_fwd(G, H, W).topk(2, dim=-1).values
+    sure = ((top[..., 0] - top[..., 1]) >= 1e-5) & far.to(dev)[None]
+    got, ref = ops.predict_mask_tiles(maps, tiles, work, size, blend=blend, ramp=S - T), ops.predict_mask(G, size)
+    wrong = int(((got != ref) & sure).sum())
+    print(f"{blend} {H}x{W}: compared {100 * float(sure.double().mean()):.2f} % of the pixels, disagreements {wrong}")
+    assert wrong == 0
+
+
+# ---- 4. exact properties ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend", BLENDS)
+@pytest.mark.parametrize("C,W", [(3, 203), (8, 517)])
+def test_exact_properties(dev, C, W, blend):
+    H, work, S, T = 131, (80, 80), 48, 32
+    tiles = window_tiles(work, S, T, context=True)
+    maps = [t.to(dev) for t in _maps(C, 2, [(17, 19)] * 4 + [(23, 21)], seed=C * 10 + W)]
+    enc = torch.arange(C, dtype=torch.uint8) * 7 + 3
+    run = lambda m, t, wk=work, size=(H, W): ops.predict_mask_tiles(m, t, wk, size, enc, blend=blend, ramp=S - T, confidence=True)
+    same = lambda a, b: torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    # (a) a mirrored tile is the un-mirrored tile with its columns reversed, bit for bit
+    mirrored = [t[:4] + (k % 2 == 0,) for k, t in enumerate(tiles)]
+    assert same(run(maps, mirrored), run([m.flip(2).contiguous() if t[4] else m for m, t in zip(maps, mirrored)], tiles))
+    assert not torch.equal(run(maps, mirrored)[0], run(maps, tiles)[0])          # and the flag does something
+    # (b) a tile list given twice.  Where one tile covers a pixel, g p + g p and g + g are exact, so mask and confidence are the
+    # same bit for bit: a single tile, and a grid of windows that do not overlap
+    one = [(0, 0, 80, 80, True)]
+    assert same(run(maps[4:], one), run(maps[4:] * 2, one * 2))
+    apart, even = window_tiles((96, 96), 48, 48), (H - 1, W - 1)                  # an even size: no pixel centre on the seam at 48
+    assert len(apart) == 4 and blend64([m.cpu() for m in maps[:4]], apart, (96, 96), *even, blend, S - T)[2] >= EDGE
+    assert same(run(maps[:4], apart, (96, 96), even), run(maps[:4] * 2, apart * 2, (96, 96), even))
+    assert same(run(maps[:4], apart, (96, 96), even),
+                run([m for m in maps[:4] for _ in (0, 1)], [t for t in apart for _ in (0, 1)], (96, 96), even))
+    # where tiles overlap the sums are made in another order and may round differently: the same mask outside the float64 margin
+    prob, _, edge = blend64([m.cpu() for m in maps], tiles, work, H, W, blend, S - T)
+    assert edge >= EDGE
+    want, sure, _ = margin_rule(prob)
+    twice = run(maps * 2, tiles * 2)[0].cpu().long()
+    assert int(((twice != enc.long()[want]) & sure).sum()) == 0 and float(sure.double().mean()) >= 0.99
+    # (c) two calls on the same inputs
+    assert same(run(maps, mirrored), run(maps, mirrored))
+
+
+@pytest.mark.parametrize("blend", BLENDS)
+def test_ties_go_to_the_lowest_class(dev, blend):
+    # (d) equal logits: class 0 everywhere, confidence 255 / C rounded (1 / C and every g / C are exact for C = 16 and 8)
+    tiles = window_tiles((80, 80), 48, 32, context=True, flip=True)
+    for C, level in ((16, 16), (8, 32)):                                         # 255 / 16 + 0.5 = 16.4, 255 / 8 + 0.5 = 32.4
+        maps = [torch.full((1, 7 + k, 9, C), -2.5 + k).to(dev) for k in range(len(tiles))]
+        mask, conf = ops.predict_mask_tiles(maps, tiles, 80, (33, 35), blend=blend, ramp=16, confidence=True)
+        assert bool((mask == 0).all()) and bool((conf == level).all())
+    const = torch.zeros((2, 9, 11, 8))
+    const[..., 2] = 1.0
+    const[..., 5] = 1.0                                                          # classes 2 and 5 hold the same maximal value
+    enc = torch.arange(8, dtype=torch.uint8) * 10
+    got = ops.predict_mask_tiles([const.to(dev)] * len(tiles), tiles, 80, (64, 83), enc, blend=blend, ramp=16)
+    assert bool((got == 20).all())
+
+
+# ---- 5. tails and alignment -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W", [1, 2, 3, 5, 6, 7, 517])
+def test_tails_and_unaligned_rows(dev, W):
+    """Widths that are not multiples of the 4-byte store, two frames: the second frame's mask and confidence start at 9 * W bytes
+    (every alignment), the last quad of a row is short.  Against float64 with the margin rule of test 1."""
+    H, C, work, S, T = 9, 3, (80, 80), 48, 32
+    tiles = window_tiles(work, S, T, flip=True)
+    maps = _maps(C, 2, [(23, 31), (17, 29)] * 4, seed=77)
+    for blend in BLENDS:
+        prob, _, edge = blend64(maps, tiles, work, H, W, blend, S - T)
+        assert edge >= EDGE
+        want, sure, pmax = margin_rule(prob)
+        mask, conf = ops.predict_mask_tiles([v.to(dev) for v in maps], tiles, work, (H, W), blend=blend, ramp=S - T, confidence=True)
+        left_out = 1.0 - float(sure.double().mean())
+        wrong = int(((mask.cpu().long() != want) & sure).sum())
+        print(f"W={W} {blend}: left out {100 * left_out:.4f} %, disagreements outside the margin {wrong}")
+        assert left_out <= 0.01 and wrong == 0                                   # test 1's cap; a frame of 9 x W pixels is small
+        assert int((conf.cpu().long() - torch.round(255.0 * pmax).long()).abs().max()) <= 1
+    # logit maps whose address is only 4- or 8-byte aligned: the wide channel loads must not be taken, the values are the same
+    two = [(0, 0, 80, 48, True), (0, 32, 80, 48, False)]
+    for Cc, off in ((8, 1), (8, 2), (4, 3), (2, 1)):
+        src = _maps(Cc, 2, [(23, 31), (17, 29)], seed=W + Cc + off)
+        aligned = [s.to(dev) for s in src]
+        flat = torch.zeros(2 * 23 * 31 * Cc + 4, device=dev)
+        odd = flat[off:off + 2 * 23 * 31 * Cc].view(2, 23, 31, Cc)
+        odd.copy_(src[0])
+        assert odd.is_contiguous() and odd.data_ptr() % 16 != 0
+        for order in ((0, 1), (1, 0)):                                           # the misaligned map first and last
+            a = ops.predict_mask_tiles([aligned[k] for k in order], two, work, (40, W), confidence=True)
+            b = ops.predict_mask_tiles([(odd, aligned[1])[k] for k in order], two, work, (40, W), confidence=True)
+            assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+# ---- 6. overlay and counts --------------------------------------------------------------------------------------------------
+def _np_counts(mask_idx, label, C):
+    return np.array([[int(((mask_idx == c) & (label == c)).sum()), int((mask_idx == c).sum()), int((label == c).sum())]
+                     for c in range(C)], dtype=np.int64)
+
+
+@pytest.mark.parametrize("C,H,W", [(8, 256, 320), (3, 131, 203)])
+def test_overlay_and_counts(dev, C, H, W):
+    g = torch.Generator().manual_seed(C + H)
+    work = (64, 96)
+    tiles = window_tiles(work, 48, 24, context=True)
+    maps = _maps(C, 2, [(24, 30), (31, 27)] * 3 + [(19, 23)], seed=C)
+    for m in maps:
+        m[..., C - 1] -= 100.0                                                   # a class that is never predicted
+    maps = [m.to(dev) for m in maps]
+    frames = torch.randint(0, 256, (2, H, W, 3), generator=g, dtype=torch.uint8)
+    palette = torch.randint(0, 256, (C, 3), generator=g, dtype=torch.uint8)
+    alpha = torch.randint(0, 256, (C,), generator=g, dtype=torch.uint8)
+    alpha[0] = 0
+    raw = torch.randint(0, 8, (2, H, W), generator=g, dtype=torch.uint8) * 32    # LUT_MULTI labels 0..7: some >= C when C < 8
+    lut = FR.LUT_MULTI
+    enc = torch.from_numpy(FR.ENCODE_ENDOVIS2017[:C].copy())
+    run = functools.partial(ops.predict_mask_tiles, maps, tiles, work, (H, W), enc, ramp=24)
+    plain = run()
+    mask, conf, over, counts = run(confidence=True, frames=frames.to(dev), palette=palette, alpha=alpha, target=raw.to(dev), lut=lut)
+    assert torch.equal(mask, plain)
+    assert torch.equal(conf, run(confidence=True)[1])
+    m = mask.cpu().numpy().astype(np.int64) >> 5
+    f, p, a = frames.numpy().astype(np.int64), palette.numpy().astype(np.int64), alpha.numpy().astype(np.int64)
+    want = (f * (255 - a[m])[..., None] + p[m] * a[m][..., None] + 127) // 255
+    assert np.array_equal(over.cpu().numpy(), want.astype(np.uint8))
+    assert np.array_equal(over.cpu().numpy()[m == 0], frames.numpy()[m == 0])    # alpha 0 leaves the frame untouched
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (C, 3)
+    cw = _np_counts(m, lut[raw.numpy()], C)
+    assert np.array_equal(counts.cpu().numpy(), cw)
+    assert cw[C - 1, 1] == 0 and int(cw[:, 1].sum()) == 2 * H * W
+    m2, o2 = run(frames=frames.to(dev), palette=palette, alpha=alpha)
+    m3, c3 = run(target=raw.to(dev), lut=lut)
+    assert torch.equal(m2, mask) and torch.equal(o2, over) and torch.equal(m3, mask) and torch.equal(c3, counts)
+
+
+# ---- 7. argument errors -----------------------------------------------------------------------------------------------------
+def test_argument_errors(dev):
+    v = _maps(3, 2, [(8, 8)], seed=0)[0].to(dev)
+    whole, halves = [(0, 0, 16, 16, False)], [(0, 0, 16, 9, False), (0, 7, 16, 9, True)]
+    for logits, tiles, kw, name in (
+            ([], [], {}, "logits"), ([v] * 33, whole * 33, {}, "logits"), (v, whole, {}, "logits"),
+            ([v, v], whole, {}, "tiles"), ([v], halves, {}, "tiles"), ([v], [(0, 0, 16, 16)], {}, r"tiles\[0\]"),
+            ([v, v], [(0, 0, 16, 9, False), (0, 8, 16, 9, False)], {}, r"tiles\[1\]"),          # sticks out on the right
+            ([v, v], [(-1, 0, 16, 16, False), (0, 0, 16, 16, False)], {}, r"tiles\[0\]"),
+            ([v], [(0, 0, 17, 16, False)], {}, r"tiles\[0\]"), ([v, v], [(0, 0, 16, 16, False), (3, 3, 0, 4, False)], {}, r"tiles\[1\]"),
+            ([v, v], [(0, 0, 16, 7, False), (0, 8, 16, 8, False)], {}, "columns from 7"),       # an uncovered strip
+            ([v, v], [(0, 0, 7, 16, False), (9, 0, 7, 16, False)], {}, "rows from 7"),
+            ([v], [(0, 0, 15, 16, False)], {}, "rows from 15"), ([v], [(1, 0, 15, 16, False)], {}, "rows from 0"),
+            ([v], whole, dict(ramp=0), "ramp"), ([v], whole, dict(ramp=0.5), "ramp"), ([v], whole, dict(ramp=float("nan")), "ramp"),
+            ([v], whole, dict(blend="gauss"), "blend"), ([v], whole, dict(blend=None), "blend"),
+            ([v, torch.zeros((2, 8, 8, 4), device=dev)], halves, {}, r"logits\[1\]"),
+            ([v, torch.zeros((1, 8, 8, 3), device=dev)], halves, {}, r"logits\[1\]"),
+            ([v, v.half()], halves, {}, r"logits\[1\]"), ([v.double()], whole, {}, r"logits\[0\]"),
+            ([v, v.permute(0, 2, 1, 3)], halves, {}, r"logits\[1\]"), ([v[:, :, ::2]], whole, {}, r"logits\[0\]"),
+            ([v], whole, dict(encode=[1, 2]), "encode"), ([v], whole, dict(palette=[[0, 0, 0]] * 3), "frames"),
+            ([v], whole, dict(target=torch.zeros((2, 16, 16), dtype=torch.uint8, device=dev)), "lut"),
+            ([v], whole, dict(frames=torch.zeros((2, 16, 15, 3), dtype=torch.uint8, device=dev)), "frames")):
+        with pytest.raises(ValueError, match=name):
+            ops.predict_mask_tiles(logits, tiles, 16, 16, **kw)
+    for work in (0, (16,), (16, 0)):
+        with pytest.raises(ValueError, match="work"):
+            ops.predict_mask_tiles([v], whole, work, 16)
+    with pytest.raises(ValueError, match="size"):
+        ops.predict_mask_tiles([v], whole, 16, (0, 4))
+    with pytest.raises(ValueError, match="C=17"):
+        ops.predict_mask_tiles([torch.zeros((1, 4, 4, 17), device=dev)], whole, 16, 16)
+    with pytest.raises(Exception, match="CPU tensor"):
+        ops.predict_mask_tiles([v.cpu()], whole, 16, 16)
+    with pytest.raises(ValueError, match=r"logits\[1\]"):
+        ops.predict_mask_tiles([v, v.cpu()], halves, 16, 16)
+    thirty_two = window_tiles((84, 84), 48, 12, flip=True)
+    assert len(thirty_two) == 32
+    assert tuple(ops.predict_mask_tiles([v] * 32, thirty_two, 84, (16, 21)).shape) == (2, 16, 21)        # 32 tiles are allowed
+
+
+# ---- 8. engine --------------------------------------------------------------------------------------------------------------
+def _engine(head, dev, num_classes):
+    from adaptersis_amd.backbones.adapter_blocks import CACNN, CAViT
+    from adaptersis_amd.backbones.decoders import DecoderMLA, FeatureDecoder
+    from adaptersis_amd.backbones.encoders import FeatureEncoder
+    from adaptersis_amd.backbones.engines import SegEngine
+    from adaptersis_amd.dinov2.models import vision_transformer as vits
+    from adaptersis_amd.utils import weights as W
+    arch, D = "vit_tiny_test", 128
+    model = vits.vit_tiny_test(patch_size=14, img_size=518, init_values=1e-5, block_chunks=0)
+    model.load_state_dict(W.make_vit_state_dict(arch))
+    enc = FeatureEncoder(embed_dim=D)
+    enc.load_state_dict(W.make_encoder_state_dict(D))
+    cv = CAViT(dim=D, n_levels=3, num_heads=8, init_values=0.0, n_points=4)
+    cv.load_state_dict(W.make_cavit_state_dict(D))
+    cn = CACNN(dim=D, n_levels=1, num_heads=8, n_points=4, with_cffn=True, cffn_ratio=0.25)
+    cn.load_state_dict(W.make_cacnn_state_dict(D))
+    if head == "mla":
+        dec = DecoderMLA(img_size=224, mla_channels=D, mlahead_channels=128, num_classes=num_classes)
+        dec.load_state_dict(W.make_decoder_mla_state_dict(D, 128, num_classes))
+        kw = dict(lr=0.01, momentum=0.9, weight_decay=0.0, loss="iou")
+    else:
+        feats = (128, 32, 16, 16, 8)
+        dec = FeatureDecoder(embed_dim=D, num_classes=num_classes, features=list(feats))
+        dec.load_state_dict(W.make_feature_decoder_state_dict(D, num_classes, features=feats))
+        kw = dict(lr=0.05)
+    return SegEngine(model.to(dev).eval(), enc.to(dev), cv.to(dev), cn.to(dev), dec.to(dev), num_classes=num_classes, **kw)
+
+
+def _bn_buffers(eng):
+    return {n: b.clone() for n, b in eng.named_buffers() if "running_" in n or "num_batches_tracked" in n}
+
+
+@pytest.mark.parametrize("head,C", [("feature", 2), ("mla", 8)])
+def test_engine_predict_tiles(dev, head, C):
+    from adaptersis_amd.utils import weights as W
+    S, L, T = 224, 336, 112
+    img, tgt = W.synthetic_batch(2, S, C)
+    img, tgt = img.to(dev), tgt.to(dev)
+    big = W.synthetic_batch(2, L, C)[0].to(dev)
+    size = (301, 517)
+    tiles = window_tiles((L, L), S, T, context=True)
+    assert tiles == [(0, 0, S, S, False), (0, T, S, S, False), (T, 0, S, S, False), (T, T, S, S, False), (0, 0, L, L, False)]
+    inps = [big[:, :, oy:oy + S, ox:ox + S].contiguous() for oy, ox, _, _, _ in tiles[:4]] + [img]
+    kw = dict(blend="ramp", ramp=S - T, confidence=True)
+    losses = {}
+    for with_tiles in (False, True):
+        eng = _engine(head, dev, C)
+        eng.seg_decoder.train()
+        if with_tiles:
+            before = _bn_buffers(eng)
+            assert before
+            got = eng.predict_tiles(inps, tiles, L, size, **kw)
+            assert eng.seg_decoder.training and eng.backbone_encoder.update_running_stats
+            after = _bn_buffers(eng)
+            assert all(torch.equal(before[n], after[n]) for n in before), "predict_tiles moved a BatchNorm running buffer"
+            assert all(t.dtype == torch.uint8 and tuple(t.shape) == (2,) + size for t in got)
+            # one ops.predict_mask_tiles call on the logits validation sees, tile by tile
+            eng.seg_decoder.eval()
+            upd, eng.backbone_encoder.update_running_stats = eng.backbone_encoder.update_running_stats, False
+            logits = [eng.eval_logits(x) for x in inps]
+            eng.backbone_encoder.update_running_stats = upd
+            eng.seg_decoder.train()
+            want = ops.predict_mask_tiles(logits, tiles, L, size, **kw)
+            assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+            with pytest.raises(ValueError, match="5 inputs and 4 tiles"):
+                eng.predict_tiles(inps, tiles[:4], L, size)
+            # the context tile alone against predict: exp is monotone, so only near-ties can differ
+            for blend in BLENDS:
+                one, ref = eng.predict_tiles([img], tiles[4:], L, size, blend=blend), eng.predict(img, size)
+                top = ops.resize_bilinear_fwd(logits[4], *size).topk(2, dim=-1).values
+                sure = (top[..., 0] - top[..., 1]) >= 1e-5
+                left_out = 1.0 - float(sure.double().mean())
+                wrong = int(((one != ref) & sure).sum())
+                print(f"{head} C={C} {blend}: left out {100 * left_out:.4f} %, disagreements with predict outside the margin {wrong}")
+                assert left_out <= 0.001 and wrong == 0
+            eng.seg_decoder.eval()
+            eng.predict_tiles([img], [(0, 0, L, L, True)], L, size)
+            assert not eng.seg_decoder.training                                  # restored to what it was, whichever that is
+            eng = _engine(head, dev, C)                                          # a fresh engine for the comparison of the losses
+            eng.seg_decoder.train()
+            eng.predict_tiles(inps, tiles, L, size)
+        losses[with_tiles] = eng.train_step(img, tgt).clone()
+    assert torch.equal(losses[False], losses[True]), "a predict_tiles call changed the following train_step"
+
+
+# ---- 9. entry point ---------------------------------------------------------------------------------------------------------
+def _write_tree(root, split, seq_sizes, n, seed):
+    """EndoVis2017 layout: per sequence n frames and instruments masks (blocky labels 0..7, the colour follows the label)."""
+    rng = np.random.default_rng(seed)
+    pal = (np.arange(8)[:, None] * np.array([[29, 71, 113]])) % 256
+    for s, hw in seq_sizes.items():
+        d = os.path.join(root, split, f"instrument_dataset_{s}")
+        os.makedirs(os.path.join(d, "images"))
+        os.makedirs(os.path.join(d, "instruments_masks"))
+        for k in range(n):
+            lab = rng.integers(0, 8, (hw[0] // 32, hw[1] // 32)).repeat(32, 0).repeat(32, 1)
+            img = np.clip(pal[lab] + rng.integers(-12, 13, hw + (3,)), 0, 255).astype(np.uint8)
+            Image.fromarray(img).save(os.path.join(d, "images", f"frame{k:03d}.png"))
+            Image.fromarray((lab * 32).astype(np.uint8)).save(os.path.join(d, "instruments_masks", f"frame{k:03d}.png"))
+
+
+def _read_tree(d):
+    return {os.path.relpath(os.path.join(r, f), d): open(os.path.join(r, f), "rb").read() for r, _, fs in os.walk(d) for f in fs}
+
+
+def test_predict_entry_point_with_tiles(dev, tmp_path):
+    from adaptersis_amd import predict as P
+    from adaptersis_amd import train as T
+    from adaptersis_amd import train_multi_class as TMC
+    root, out = str(tmp_path / "ev17"), str(tmp_path / "out")
+    native = {1: (256, 320), 2: (192, 288)}
+    _write_tree(root, "Train", {1: (256, 320)}, 8, seed=0)
+    _write_tree(root, "Test", native, 5, seed=1)                                  # two native sizes, short last batches
+    model_args = ["--arch", "vit_tiny_test", "--imsize", "224", "--batch_size_per_gpu", "4", "--num_workers", "0", "--output_dir", out]
+    T._ENGINES.clear(); T._AUGMENTERS.clear()
+    torch.manual_seed(0)
+    TMC.train_seg(TMC.get_args_parser().parse_args(model_args + ["--lr", "0.08", "--data_path", root, "--epochs", "1",
+                                                                 "--num_classes", "8"]))
+    T._ENGINES.clear()
+
+    def pargs(pred, *extra):
+        return P.get_args_parser().parse_args(model_args + ["--head", "mla", "--num_classes", "8", "--input", root, "--dataset",
+                                                            "endovis2017", "--split", "Test", "--encode", "endovis2017", "--masks",
+                                                            "--seed", "0", "--pred_dir", str(tmp_path / pred), *extra])
+    S, L, St = 224, 336, 112
+    args = pargs("slide", "--slide_size", str(L), "--slide_stride", str(St), "--slide_context", "--tta_flip", "--confidence")
+    eng = P.build_engine(args)
+    res = P.predict_seg(args, engine=eng)
+    rels = [f"instrument_dataset_{s}/images/frame{k:03d}.png" for s in (1, 2) for k in range(5)]
+    assert sorted(res["files"]) == rels
+    got = _read_tree(args.pred_dir)
+    assert sorted(got) == sorted(rels + [r[:-4] + "_conf.png" for r in rels] + ["metrics.json"])
+    met = json.load(open(os.path.join(args.pred_dir, "metrics.json")))
+    assert met["tiles"] == {"size": L, "stride": St, "blend": "ramp", "context": True, "flip": True, "count": 10}
+    assert met["frames"] == 10 and "views" not in met
+    masks, confs = {}, {}
+    for r in rels:
+        hw = native[int(r.split("/")[0].rsplit("_", 1)[1])]
+        for store, path in ((masks, r), (confs, r[:-4] + "_conf.png")):
+            im = Image.open(os.path.join(args.pred_dir, path))
+            assert im.mode == "L" and im.size == (hw[1], hw[0])
+            store[r] = np.array(im)
+        assert set(np.unique(masks[r]).tolist()) <= set(range(0, 256, 32))
+    # the same batches through engine.predict_tiles and engine.predict: sizes ascending, sorted paths inside a size, 4 per batch
+    tiles = window_tiles((L, L), S, St, context=True, flip=True)
+    assert len(tiles) == 10 and tiles == P.plan_tiles(L, S, St, True, True)
+    enc = FR.encode_table("endovis2017", 8)
+    norm = lambda u8: T._to_device_batch(u8.contiguous(), torch.zeros(u8.shape[:3], dtype=torch.uint8, device=dev), train=False)[0]
+    plain = {}
+    for batch in ([f"instrument_dataset_2/images/frame{k:03d}.png" for k in range(4)], ["instrument_dataset_2/images/frame004.png"],
+                  [f"instrument_dataset_1/images/frame{k:03d}.png" for k in range(4)], ["instrument_dataset_1/images/frame004.png"]):
+        frames = torch.from_numpy(np.stack([np.array(Image.open(os.path.join(root, "Test", r)).convert("RGB")) for r in batch])).to(dev)
+        work, _ = ops.frame_resize(frames, None, L)
+        whole, _ = ops.frame_resize(frames, None, S)
+        inps = []
+        for oy, ox, sy, sx, f in tiles:
+            crop = work[:, oy:oy + S, ox:ox + S] if (sy, sx) == (S, S) else whole
+            inps.append(norm(crop.flip(2) if f else crop))
+        m, c = eng.predict_tiles(inps, tiles, L, tuple(frames.shape[1:3]), encode=enc, blend="ramp", ramp=S - St, confidence=True)
+        p = eng.predict(norm(whole), size=tuple(frames.shape[1:3]), encode=enc)
+        for k, r in enumerate(batch):
+            assert np.array_equal(m[k].cpu().numpy(), masks[r]), r
+            assert np.array_equal(c[k].cpu().numpy(), confs[r]), r
+            plain[r] = p[k].cpu().numpy()
+    counts = _np_counts(np.concatenate([masks[r].reshape(-1) >> 5 for r in rels]),
+                        np.concatenate([np.array(Image.open(os.path.join(root, "Test", r.replace("/images/", "/instruments_masks/"))))
+                                        .reshape(-1) >> 5 for r in rels]), 8)
+    assert met["counts"] == counts.tolist()
+
+    # without the slide flags: the files of predict_seg as it was (engine.predict on the same batches), byte for byte, no "tiles"
+    a2 = pargs("plain")
+    P.predict_seg(a2, engine=eng)
+    got2 = _read_tree(a2.pred_dir)
+    assert sorted(got2) == sorted(rels + ["metrics.json"])
+    met2 = json.load(open(os.path.join(a2.pred_dir, "metrics.json")))
+    assert "tiles" not in met2 and "views" not in met2
+    for r in rels:
+        assert np.array_equal(np.array(Image.open(os.path.join(a2.pred_dir, r))), plain[r]), r
