@@ -133,6 +133,10 @@ SIGNATURES = {
     "asis_cls_lowres_nblk": [_i, _i, _i],
     "asis_cls_lowres_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "asis_cls_lowres_bwd": [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i],
+    "asis_dgrad_lowres_nblk": [_i, _i, _i],
+    "asis_dgrad_lowres_cap": [_i],
+    "asis_dgrad_lowres_pack": [_vp, _i, _vp, _vp, _vp, _i, _i],
+    "asis_dgrad_lowres": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i],
     "asis_conv3x3_smallcout_dgrad": [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i],
     "asis_conv3x3_smallcout_wgrad": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i],
     "asis_colstats_nparts": [_i64],

@@ -8,6 +8,8 @@ statistics from the GEMM epilogue, then one fused BN+ReLU+upsample kernel that w
 conv's 16-bit operand.  Backward per stage (the only gradients the reference step produces,
 SURVEY.md fact 1): upsample^T + ReLU mask + BN partial sums, BN backward apply, conv dgrad
 (implicit GEMM with flipped weights) and conv wgrad (transposed-read split-K GEMM).
+Between two stages of FeatureDecoder / DecoderSETR the dgrad and the next upsample^T run as ONE kernel at the lower stage's
+resolution (ops.dgrad_lowres, ops.DGRAD_LOWRES): the two linear maps commute.
 
 The same functional core serves two front-ends:
   * ``forward(x)`` — reference-shaped ``nn.Module`` call on an NCHW fp32 tensor, differentiable
@@ -35,7 +37,7 @@ _DGRAD_MX = __import__("os").environ.get("ASIS_DGRAD_MX", "1") not in ("0", "")
 
 class _Stage:
     """Saved tensors of one conv -> BN -> ReLU -> upsample stage."""
-    __slots__ = ("x16", "raw", "scale", "shift", "mean", "invstd", "count", "factor", "stride", "pad", "pool", "cls_lowres")
+    __slots__ = ("x16", "raw", "scale", "shift", "mean", "invstd", "count", "factor", "stride", "pad", "pool", "cls_lowres", "dgrad_lowres")
 
 
 def _conv_weights(owner: _Packed, key: str, conv: nn.Conv2d, split: bool):
@@ -166,8 +168,12 @@ def conv_bn_relu_up_forward(owner: _Packed, key: str, x16, x_lo, conv: nn.Conv2d
 
 def conv_bn_relu_up_backward(owner: _Packed, key: str, st: _Stage, dU, conv: nn.Conv2d, bn: nn.BatchNorm2d,
                              inv_scale: float, grads: Dict[str, torch.Tensor], prefix: str, need_dx: bool,
-                             sync_bn: bool, conv_name: Optional[str] = None, bn_name: Optional[str] = None):
+                             sync_bn: bool, conv_name: Optional[str] = None, bn_name: Optional[str] = None,
+                             lower: Optional[_Stage] = None):
     """dU fp32 [B, fH, fW, C] (scaled by the loss scale) -> grads[...] (unscaled) and dX fp32 or None.
+    ``lower``: the saved stage whose x2-upsampled output is this conv's input.  Where ops.dgrad_lowres covers the pair
+    (ops.DGRAD_LOWRES), the input gradient is not formed at this conv's resolution: the result is the pair ``(g, partial)`` of the
+    lower stage, which its own conv_bn_relu_up_backward call accepts in the place of dU.
     ``dU`` may also be the pair ``(g, partial)`` that ops.upsample_bn_relu_bwd would return, already computed by the consumer
     (the commuted classifier, ops.cls_lowres_bwd): the transposed upsampling is then skipped.
     Parameter names default to ``prefix.0`` (conv) / ``prefix.1`` (BatchNorm)."""
@@ -194,7 +200,11 @@ def conv_bn_relu_up_backward(owner: _Packed, key: str, st: _Stage, dU, conv: nn.
     split = config.split_conv and need_dx
     # the input-gradient convolution of a stride-1 stage takes dx's lo half in the MX form (its two correction terms as one fp8 pass)
     P_ = st.raw.numel() // C
-    mx_bwd = bool(split and stride == 1 and _DGRAD_MX and config.mx_conv_on() and ops.mx_conv_ok(P_, C, conv.in_channels))
+    # with split operands only: the kernel always runs its three 16-bit parts, against ONE part of the unsplit implicit GEMM
+    lowres = bool(split and lower is not None and _dgrad_lowres_ok(key, st, conv, lower))
+    st.dgrad_lowres = lowres
+    # (the commuted form takes the plain 16-bit residual: no MX plane, so no absolute-maximum pass over g and raw either)
+    mx_bwd = bool(split and stride == 1 and not lowres and _DGRAD_MX and config.mx_conv_on() and ops.mx_conv_ok(P_, C, conv.in_channels))
     r = ops.bn_bwd_apply(g, st.raw, st.mean, st.invstd, owner._f32(key + ".g", bn.weight), dgamma_s, dbeta_s,
                          st.count, dt, split, mx=mx_bwd)
     dx16, dx_lo, bpart = r if split else (r[0], None, r[1])
@@ -206,6 +216,9 @@ def conv_bn_relu_up_backward(owner: _Packed, key: str, st: _Stage, dU, conv: nn.
     parallel.wgrad_on_side_stream(lambda: ops.wgrad(dx16, st.x16, C, 3, 3, stride, pad, inv_scale, out=wout), dx16, st.x16)
     if not need_dx:
         return None
+    if lowres:
+        wp = _pack(owner._cache, key + ".wdlowres", conv.weight, lambda p: ops.dgrad_lowres_pack(p.float().contiguous(), dt))
+        return ops.dgrad_lowres(dx16, dx_lo, wp, lower.raw, lower.scale, lower.shift, lower.mean, lower.invstd)
     if stride == 1:
         return _dgrad(owner, key, conv, dx16, dx_lo)
     # stride 2: conv_transpose2d = stride-1 correlation of the zero-inserted gradient with the mirrored weights, padded by
@@ -214,6 +227,18 @@ def conv_bn_relu_up_backward(owner: _Packed, key: str, st: _Stage, dU, conv: nn.
     pp = 2 - pad
     d_hi, d_lo = ops.dilate2(dx16, dx_lo, H + 2 - 2 * pp, W + 2 - 2 * pp)
     return _dgrad(owner, key, conv, d_hi, d_lo, pad=pp)
+
+
+def _dgrad_lowres_ok(key: str, st: _Stage, conv: nn.Conv2d, lower: _Stage) -> bool:
+    """the conv of stage ``st`` (3x3, stride 1, pad 1, no pool) reads the x2-upsampled output of ``lower``, and asis_dgrad_lowres
+    covers the channel pair"""
+    if not ops.dgrad_lowres_on(key) or (getattr(st, "stride", 1) or 1) != 1 or getattr(st, "pad", 1) != 1 or getattr(st, "pool", False):
+        return False
+    if lower.factor != 2 or getattr(lower, "pool", False) or lower.mean is None:
+        return False
+    B, H, W, Ck = lower.raw.shape
+    return bool(tuple(st.raw.shape[:3]) == (B, 2 * H, 2 * W) and conv.in_channels == Ck and
+                ops.dgrad_lowres_ok(conv.out_channels, Ck, H, W))
 
 
 def _dgrad(owner: _Packed, key: str, conv: nn.Conv2d, d16, d_lo, pad: int = 1):
@@ -378,7 +403,8 @@ class FeatureDecoder(_Packed):
         for i in range(4, 0, -1):
             seq = getattr(self, f"decoder_{i}")
             dU = conv_bn_relu_up_backward(self, f"d{i}", saved[i - 1], dU, seq[0], seq[1], inv_scale, grads,
-                                          f"decoder_{i}", need_dx=(i > 1 or need_input_grad), sync_bn=self.sync_bn)
+                                          f"decoder_{i}", need_dx=(i > 1 or need_input_grad), sync_bn=self.sync_bn,
+                                          lower=saved[i - 2] if i > 1 else None)
             if stage_done is not None:
                 stage_done()
         return dU

@@ -183,3 +183,26 @@ mx_dense = os.environ.get("ASIS_MX_DENSE", "1") not in ("0", "")
 
 def mx_dense_on() -> bool:
     return mx_dense and operand_dtype == torch.float16
+
+# Input gradients of the FeatureDecoder / DecoderSETR convs of stages 4, 3, 2 at the resolution of the stage below: the transposed
+# x2 upsampling runs before the channel product (csrc/dgradlowres.hip), so the product works on a quarter of the pixels and the fp32
+# gradient map of the upsampled stage output is never written.  ASIS_DGRAD_LOWRES = 1 (default): every boundary; 0: the implicit-GEMM
+# dgrad + asis_upsample_bn_relu_bwd as before; a list such as "d3,d4": only the convs of those stages (named like ASIS_UNSPLIT); anything else is an error.
+# Taken with split_conv only: the kernel always runs three 16-bit parts, the unsplit implicit GEMM one.
+_DGRAD_LOWRES_ALL = ("d2", "d3", "d4")
+
+
+def parse_dgrad_lowres(v: str) -> frozenset:
+    v = (v or "").strip().lower()
+    if v in ("", "0"):
+        return frozenset()
+    if v == "1":
+        return frozenset(_DGRAD_LOWRES_ALL)
+    keys = [k.strip() for k in v.split(",") if k.strip()]
+    bad = [k for k in keys if k not in _DGRAD_LOWRES_ALL]
+    if bad:
+        raise ValueError(f"ASIS_DGRAD_LOWRES={v!r}: expected 0, 1 or a list of {', '.join(_DGRAD_LOWRES_ALL)} (unknown: {', '.join(bad)})")
+    return frozenset(keys)
+
+
+dgrad_lowres = parse_dgrad_lowres(os.environ.get("ASIS_DGRAD_LOWRES", "1"))

@@ -13,7 +13,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, config
 from ._lib import ACT_GELU, ACT_GELU_GRAD, ACT_NONE, ACT_RELU, ACT_SILU_MUL, GemmDesc, check, lib  # noqa: F401
 
 T16_DEFAULT = torch.float16
@@ -897,6 +897,58 @@ def cls_lowres_bwd(d16: torch.Tensor, d_lo: Optional[torch.Tensor], raw: torch.T
         out = torch.empty((Cout, Cin, 3, 3), device=raw.device, dtype=torch.float32)
     reduce_rows(slabs, inv_scale, out.view(-1))
     return g, partial, out
+
+
+# decoder input gradients with the conv commuted with the transposed x2 upsampling of the stage below (csrc/dgradlowres.hip).  The
+# switch: a set of stage keys ("d2", "d3", "d4": the conv whose input gradient it is) from ASIS_DGRAD_LOWRES (config.dgrad_lowres),
+# or True / False for all / none
+DGRAD_LOWRES = config.dgrad_lowres
+
+
+def dgrad_lowres_on(key: str) -> bool:
+    return bool(DGRAD_LOWRES) if isinstance(DGRAD_LOWRES, bool) else key in DGRAD_LOWRES
+
+
+def dgrad_lowres_ok(Co: int, Ck: int, H: int, W: int) -> bool:
+    """shapes asis_dgrad_lowres covers: Co (the conv's output channels) a multiple of 16, Ck (its input channels = the channels of
+    the stage below) 128, 256 or 512, the low-resolution map H x W at least 2 x 2"""
+    return bool(Co >= 16 and Co % 16 == 0 and Co <= 4096 and Ck in (128, 256, 512) and H >= 2 and W >= 2 and H * W * Co < (1 << 27))
+
+
+def dgrad_lowres_pack(w: torch.Tensor, dtype: torch.dtype):
+    """fp32 conv weight [Co, Ck, 3, 3] -> (hi, lo) 16-bit operand planes of asis_dgrad_lowres: [Co / 16, 5, Ck, 32] each"""
+    _dev(w)
+    Co, Ck = w.shape[0], w.shape[1]
+    if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError("dgrad_lowres_pack: contiguous float32 [Co, Ck, 3, 3] expected")
+    hi = torch.empty((max(Co // 16, 1), 5, Ck, 32), device=w.device, dtype=dtype)
+    lo = torch.empty_like(hi)
+    check(lib().asis_dgrad_lowres_pack(_stream(), _dt(dtype), w.data_ptr(), hi.data_ptr(), lo.data_ptr(), Co, Ck),
+          "asis_dgrad_lowres_pack")
+    return hi, lo
+
+
+def dgrad_lowres(d16: torch.Tensor, d_lo: Optional[torch.Tensor], wpack, raw: torch.Tensor, scale, shift, mean, invstd):
+    """d16 (+ d_lo) 16-bit [B, 2H, 2W, Co]: the output gradient of a 3x3 / pad 1 conv whose input is the x2-upsampled BatchNorm + ReLU
+    of ``raw`` fp32 [B, H, W, Ck]; ``wpack`` = dgrad_lowres_pack of its weight -> (g fp32 [B, H, W, Ck], partial [nblk, 2, Ck]), the
+    pair ops.upsample_bn_relu_bwd would return for the conv's input gradient (include/asis_hip.h: asis_dgrad_lowres)."""
+    _dev(d16, d_lo, raw)
+    _not_mx("dgrad_lowres", d_lo)
+    B, H, W, Ck = raw.shape
+    Co = d16.shape[3]
+    w_hi, w_lo = wpack
+    if not d16.is_contiguous() or tuple(d16.shape[:3]) != (B, 2 * H, 2 * W) or (d_lo is not None and
+                                                                                 (d_lo.shape != d16.shape or not d_lo.is_contiguous())):
+        raise ValueError("dgrad_lowres: d16 / d_lo must be contiguous [B, 2H, 2W, Co]")
+    if raw.dtype != torch.float32 or not raw.is_contiguous() or w_hi.dtype != d16.dtype or w_hi.numel() != (Co // 16) * 5 * Ck * 32:
+        raise ValueError("dgrad_lowres: raw must be contiguous float32 [B, H, W, Ck] and the weight pack that of a [Co, Ck, 3, 3] conv")
+    nblk = lib().asis_dgrad_lowres_nblk(B, H, W)
+    g = torch.empty_like(raw)
+    partial = torch.empty((nblk, 2, Ck), device=raw.device, dtype=torch.float32)
+    check(lib().asis_dgrad_lowres(_stream(), _dt(d16.dtype), d16.data_ptr(), _p(d_lo), w_hi.data_ptr(), w_lo.data_ptr(), raw.data_ptr(),
+                                  _f32c(scale).data_ptr(), _f32c(shift).data_ptr(), _f32c(mean).data_ptr(), _f32c(invstd).data_ptr(),
+                                  g.data_ptr(), partial.data_ptr(), nblk, B, H, W, Co, Ck), "asis_dgrad_lowres")
+    return g, partial
 
 
 def conv3x3_smallcout_dgrad(dy_hi: torch.Tensor, dy_lo: Optional[torch.Tensor], w: torch.Tensor) -> torch.Tensor:

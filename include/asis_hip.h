@@ -447,6 +447,27 @@ int asis_cls_lowres_bwd(void* stream, int dtype, const void* d16, const void* d_
                         const float* shift, const float* mean, const float* invstd, const float* w, float* g, float* partial,
                         float* slabs, int nblk, int B, int H, int W, int Cin, int Cout);
 
+/* Input gradient of a 3x3 / stride 1 / pad 1 decoder conv (Ck -> Co channels at [2H, 2W]) COMMUTED with the transposed x2 upsampling
+ * of the stage below it (csrc/dgradlowres.hip) — the wide-channel, MFMA form of asis_cls_lowres_bwd.  up^T acts on space and W_tap^T
+ * on channels, so the channel product runs at [H, W]: with d = d16 (+ d_lo, may be null), 16-bit [B, 2H, 2W, Co] (the conv's output
+ * gradient, still carrying the loss scale),  e[tap,c] = up^T(shift_tap(d[c]))  (a shifted position outside the map is dropped; the
+ * bilinear taps are the tap_ac_true expressions of asis_upsample_bn_relu_bwd) and
+ *   g[b,i,j,k] = (raw*scale + shift > 0) ? sum_{tap,c} w[c,k,tap] e[tap,c] : 0      fp32 [B, H, W, Ck]
+ *   partial[nblk][2][Ck] = sum g | sum g*xhat,  nblk = asis_dgrad_lowres_nblk(B, H, W)     (asis_reduce_rows finishes them)
+ * — what asis_upsample_bn_relu_bwd computes from the conv's fp32 input gradient dU, which is never written.  raw / scale / shift /
+ * mean / invstd: the lower stage's fp32 conv output [B, H, W, Ck] and its BatchNorm vectors.  The product runs as three 16-bit MFMA
+ * parts e_hi W_hi + e_lo W_hi + e_hi W_lo with fp32 accumulation.  w_hi / w_lo: asis_dgrad_lowres_pack of the conv's fp32 weight
+ * [Co][Ck][3][3], (Co / 16) * 5 * Ck * 32 16-bit values each.  Co a multiple of 16, Ck in {128, 256, 512}, H, W >= 2, one image of d
+ * below 2^30 bytes.  No atomics: every sum runs in a fixed order. */
+int asis_dgrad_lowres_nblk(int B, int H, int W); /* 0 for B, H or W < 1 */
+/* most workgroups per launch (default 2048; out of 1..65536 restores it); returns the former value.  A small cap makes a small map run
+ * several tiles per workgroup, as the large maps do. */
+int asis_dgrad_lowres_cap(int cap);
+int asis_dgrad_lowres_pack(void* stream, int dtype, const float* w, void* w_hi, void* w_lo, int Co, int Ck);
+int asis_dgrad_lowres(void* stream, int dtype, const void* d16, const void* d_lo, const void* w_hi, const void* w_lo, const float* raw,
+                      const float* scale, const float* shift, const float* mean, const float* invstd, float* g, float* partial,
+                      int nblk, int B, int H, int W, int Co, int Ck);
+
 /* Weight gradient of the same 3x3 / stride 1 / pad 1 classifier conv (`backbones/decoders.py:135` under
  * `loss.backward()`, `train.py:432`): dy 16-bit [B,H,W,CoP], x 16-bit [B,H,W,Cin] -> `nblk` fp32 slab rows of
  * [Cout,Cin,3,3] partial sums (one per workgroup; sum them with asis_reduce_rows).  Cin in {8,16,32,64}. */
