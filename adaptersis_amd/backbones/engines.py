@@ -61,6 +61,26 @@ class pre_vit(_Packed):
         return out
 
 
+def loss_and_dz(engine, logits: torch.Tensor, target: torch.Tensor, S: float):
+    """The loss stage of every engine's ``train_step``: logits fp32 NHWC [B,h,w,C], target int64 [B,H,W] ->
+    (loss [1], dz fp32 [B,H,W,C] = S * d loss / d resized logits) for ``engine.loss_kind``, a key of ``SegEngine.LOSSES``.
+    No host sync.  The Lovasz losses keep their sort scratch on the engine between steps."""
+    n_region, lmode, eps, n_ce = SegEngine.LOSSES[engine.loss_kind]
+    if lmode != ops.LOSS_LOVASZ:
+        loss, coef, _ = ops.seg_loss_fwd(logits, target, n_region, lmode, eps, n_ce, None, S)
+        return loss, ops.seg_loss_bwd(logits, target, coef, n_region, lmode, n_ce, None)
+    need = ops.lovasz_scratch_bytes(target.numel(), logits.shape[-1])
+    scratch = getattr(engine, "_lovasz_scratch", None)
+    if scratch is None or scratch.numel() < need or scratch.device != logits.device:
+        scratch = engine._lovasz_scratch = torch.empty((need,), device=logits.device, dtype=torch.uint8)
+    dz, ce = None, None
+    if n_ce:  # CrossentropyND half: its dz is the buffer the Lovasz gradient is added into
+        ce, coef, _ = ops.seg_loss_fwd(logits, target, 0, ops.LOSS_NONE, eps, n_ce, None, S)
+        dz = ops.seg_loss_bwd(logits, target, coef, 0, ops.LOSS_NONE, n_ce, None)
+    loss, _, dz = ops.lovasz_softmax(logits, target, n_region, "mean", S, dz=dz, scratch=scratch)
+    return (loss if ce is None else ce.add_(loss)), dz
+
+
 class SegEngine(nn.Module):
     """One object owning the frozen ViT, the CNN encoder, the adapters, the decode head and the optimizer.
 
@@ -79,6 +99,10 @@ class SegEngine(nn.Module):
         "dc_and_ce": (1, ops.LOSS_SOFTDICE, 1.0, 2),    # train.py:426 (commented alternative)
         "tversky": (1, ops.LOSS_TVERSKY, 1.0, 0),       # train.py:50 import
         "ce_dc": (1, ops.LOSS_DICE, 10e-20, 1),         # eval/eval_dinov2_unet.py:291-297, eval_dinov2_setr_cross_ete.py:334-340
+        # segloss/lovasz_loss.py: LovaszSoftmax()(softmax(out)) through asis_lovasz_softmax (eps unused), and CrossentropyND on
+        # the resized logits plus that term (the analogue of "ce_dc"); see loss_and_dz
+        "lovasz": (1, ops.LOSS_LOVASZ, 0.0, 0),
+        "ce_lovasz": (1, ops.LOSS_LOVASZ, 0.0, 1),
     }
 
     def __init__(self, model, backbone_encoder, cross_vit: CAViT, cross_cnn: CACNN, seg_decoder, *,
@@ -492,9 +516,7 @@ class SegEngine(nn.Module):
             else:
                 logits, saved = dec._forward_core(cat[0], cat[1], save=True, training=True)
         target = target.long().contiguous()
-        n_region, lmode, eps, n_ce = self.LOSSES[self.loss_kind]
-        loss, coef, _ = ops.seg_loss_fwd(logits, target, n_region, lmode, eps, n_ce, None, S)
-        dz = ops.seg_loss_bwd(logits, target, coef, n_region, lmode, n_ce, None)
+        loss, dz = loss_and_dz(self, logits, target, S)
         B, hh, ww, C = logits.shape
         r = ops.resize_bilinear_bwd(dz, hh, ww, config.operand_dtype, config.split_conv)
         d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])
@@ -977,9 +999,7 @@ class EndToEndEngine(nn.Module):
         lo = ops.cast_pad(t2, D, dt, part=1).view(B, h, w, D) if config.split_conv else None
         logits, saved = dec._forward_core(hi, lo, save=True, training=True)
         target = target.long().contiguous()
-        n_region, lmode, eps, n_ce = SegEngine.LOSSES[self.loss_kind]
-        loss, coef, _ = ops.seg_loss_fwd(logits, target, n_region, lmode, eps, n_ce, None, S)
-        dz = ops.seg_loss_bwd(logits, target, coef, n_region, lmode, n_ce, None)
+        loss, dz = loss_and_dz(self, logits, target, S)
         _, hh, ww, C = logits.shape
         r = ops.resize_bilinear_bwd(dz, hh, ww, dt, config.split_conv)
         d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])

@@ -1472,6 +1472,7 @@ def convt2x2_gather(dcat: torch.Tensor, B: int, H: int, W: int, Cout: int, coff:
 
 
 LOSS_DICE, LOSS_IOU, LOSS_SOFTDICE, LOSS_TVERSKY, LOSS_NONE = 0, 1, 2, 3, 4
+LOSS_LOVASZ = 5  # not a mode of asis_seg_loss_fwd: the engines route it to lovasz_softmax (asis_lovasz_softmax)
 
 
 def seg_loss_fwd(logits: torch.Tensor, target: torch.Tensor, n_region: int, mode: int = LOSS_DICE, eps: float = 1e-19,
@@ -1571,6 +1572,57 @@ def reduce_rows(partial: torch.Tensor, scale: float = 1.0, out: Optional[torch.T
     check(lib().asis_reduce_rows(_stream(), _f32c(partial).data_ptr(), n, K, float(scale), out.data_ptr()),
           "asis_reduce_rows")
     return out
+
+
+LOVASZ_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
+
+
+def lovasz_scratch_bytes(n_pixels: int, num_classes: int) -> int:
+    """bytes of caller-owned scratch ``asis_lovasz_softmax`` needs for ``n_pixels`` = B*H*W (needs no GPU)."""
+    nb = lib().asis_lovasz_scratch_bytes(int(n_pixels), int(num_classes))
+    if nb < 0:
+        check(int(nb), "asis_lovasz_scratch_bytes")
+    return int(nb)
+
+
+def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, n_softmax: int = 1, reduction: str = "mean",
+                   grad_scale: float = 1.0, dz: Optional[torch.Tensor] = None, return_order: bool = False,
+                   scratch: Optional[torch.Tensor] = None):
+    """Lovasz-Softmax (`segloss/lovasz_loss.py:39-60`) of softmax^n_softmax(resize(logits)) against the labels, forward and
+    gradient in one call.  logits fp32 NHWC [B,h,w,C]; target int64 [B,H,W] -> (loss [1], per_class [C], dz fp32 [B,H,W,C]) with
+    dz = grad_scale * d loss / d resized logits; a given ``dz`` is added into (and returned).  reduction "none": the losses are
+    ``per_class``, ``loss`` is their sum and dz the gradient of that sum.  ``return_order`` appends keys fp32 [C,N] (the errors
+    in pixel order) and order int32 [C,N] (pixel index at each sorted position: descending error, ties by ascending index).
+    ``scratch``: a uint8 buffer of at least ``lovasz_scratch_bytes(B*H*W, C)`` to reuse between calls (default: a fresh one)."""
+    _dev(logits, target, dz, scratch)
+    if logits.dim() != 4 or target.dim() != 3:
+        raise ValueError("lovasz_softmax: logits must be NHWC [B,h,w,C] and target [B,H,W]")
+    B, h, w, Cc = logits.shape
+    H, W = target.shape[-2:]
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] != B:
+        raise ValueError("lovasz_softmax: target must be contiguous int64 [B,H,W]")
+    if reduction not in LOVASZ_REDUCTIONS:
+        raise ValueError(f"lovasz_softmax: reduction must be one of {sorted(LOVASZ_REDUCTIONS)}")
+    N = B * H * W
+    need = lovasz_scratch_bytes(N, Cc)
+    if scratch is None:
+        scratch = torch.empty((need,), device=logits.device, dtype=torch.uint8)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+        raise ValueError(f"lovasz_softmax: scratch must be a contiguous uint8 buffer of at least {need} bytes")
+    accumulate = dz is not None
+    if dz is None:
+        dz = torch.empty((B, H, W, Cc), device=logits.device, dtype=torch.float32)
+    elif tuple(dz.shape) != (B, H, W, Cc):
+        raise ValueError("lovasz_softmax: dz must be float32 [B,H,W,C]")
+    loss = torch.empty((1,), device=logits.device, dtype=torch.float32)
+    per_class = torch.empty((Cc,), device=logits.device, dtype=torch.float32)
+    keys = torch.empty((Cc, N), device=logits.device, dtype=torch.float32) if return_order else None
+    order = torch.empty((Cc, N), device=logits.device, dtype=torch.int32) if return_order else None
+    check(lib().asis_lovasz_softmax(_stream(), _f32c(logits).data_ptr(), target.data_ptr(), B, h, w, H, W, Cc, int(n_softmax),
+                                    LOVASZ_REDUCTIONS[reduction], float(grad_scale), int(accumulate), scratch.data_ptr(),
+                                    loss.data_ptr(), per_class.data_ptr(), _f32c(dz).data_ptr(), _p(keys), _p(order)),
+          "asis_lovasz_softmax")
+    return (loss, per_class, dz, keys, order) if return_order else (loss, per_class, dz)
 
 
 # --------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import json
 import math
 import os
 from pathlib import Path
+from typing import Optional
 
 import torch
 from torch import nn
@@ -187,14 +188,17 @@ def build_modules(args, head: str, num_classes: int, dev):
     return model, backbone_encoder, cross_vit, cross_cnn, seg_decoder
 
 
-def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: str = "dice", open_datasets=None, validate=None):
+def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Optional[str] = None, open_datasets=None, validate=None):
     """``head``: "feature" = `train.py` (FeatureDecoder, SGD lr / 0.99 / 3e-5, `train.py:178-191`); "mla" = `train_mla.py`
     (DecoderMLA, SGD lr * batch * world / 16, momentum 0.9, no weight decay, `train_mla.py:178-184`).
-    ``num_classes`` (head and engine), ``loss`` (a key of ``SegEngine.LOSSES``), ``open_datasets(args) -> (train set, val set,
+    ``num_classes`` (head and engine), ``loss`` (a key of ``SegEngine.LOSSES``; default: ``--loss``, "dice" in a namespace
+    built without it), ``open_datasets(args) -> (train set, val set,
     collate_fn)`` and ``validate`` (signature of ``validate_network``) are what `train_multi_class.py` changes; the defaults
     are `train.py`'s."""
     open_datasets = open_datasets or _open_datasets
     validate = validate or validate_network
+    if loss is None:
+        loss = getattr(args, "loss", "dice")
     utils.init_distributed_mode(args)
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda", args.gpu)
@@ -414,6 +418,9 @@ def get_args_parser():
     p.add_argument("--clip_grad", default=None, type=float, help="adamw: clip the global gradient norm at this value")
     p.add_argument("--layer_decay", default=None, type=float,
                    help="adamw: layer-wise learning-rate decay of the ViT blocks (engines that optimise the backbone)")
+    # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
+    p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
+                   help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that")
     return p
 
 

@@ -106,13 +106,14 @@ def train_seg(args):
         args.cross_test_path = args.data_path
     if args.data_path != "synthetic":
         _task(args)   # argument errors before any model is built
-    return _t.train_seg(args, head="mla", num_classes=args.num_classes, loss="iou", open_datasets=open_datasets,
+    return _t.train_seg(args, head="mla", num_classes=args.num_classes, loss=getattr(args, "loss", "iou"), open_datasets=open_datasets,
                         validate=functools.partial(validate_network, problem_type=args.problem_type))
 
 
 def get_args_parser():
     p = _mla.get_args_parser()
     p.description = "Multi-class segmentation on EndoVis2017 (train_multi_class.py)"
+    p.set_defaults(loss="iou")   # train_multi_class.py:390-393
     p.add_argument("--num_classes", default=8, type=int, help="classes of the MLA head and of the soft-IoU loss")
     p.add_argument("--cross_test_path", default=None, type=str, help="root of the validation split (default: --data_path)")
     p.add_argument("--dataset", default="endovis2017", choices=DATASETS)

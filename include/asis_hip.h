@@ -658,6 +658,27 @@ int asis_resize_bilinear_bwd(void* stream, int dtype, const float* dz, int B, in
 /* out[k] = scale * sum_n partial[n][k], summed in double in a fixed order */
 int asis_reduce_rows(void* stream, const float* partial, int n, int K, float scale, float* out);
 
+/* Lovasz-Softmax (segloss/lovasz_loss.py:39-60; csrc/lovasz.hip), fused with the resize like the losses above:
+ *   q = softmax^n_softmax(resize(logits)), n_softmax 0 or 1; per class c over the N = B*H*W pixels of the whole batch
+ *   e[i] = |(target[i] == c) - q_c[i]|, sorted descending by the fp32 bit pattern, ties by ascending flat pixel index
+ *   (b*H + y)*W + x (a stable sort); loss_c = sum_k e(k) g_k with g = lovasz_grad of the class flags in that order, evaluated in
+ *   double from integer counts: class pixel 1/U, other I/(U(U-1)), I = G - f_k, U = G + b_k; no pixel of the class: g_0 = 1.
+ *   A label outside 0..C-1 is a pixel of no class.  d loss_c / d q_c[i] = -g (class pixel), +g (other), 0 where e == 0.
+ *   reduction 0: loss = mean of the loss_c (gradient factor 1/C); 1: sum; 2: "none" = the vector per_class, loss[0] its sum
+ *     and dz the gradient of that sum (the classes do not mix before the softmax transpose).
+ *   loss 1 float, per_class C floats; dz fp32 [B,H,W,C] = grad_scale * d loss / d resized logits (through the softmax transpose
+ *     when n_softmax = 1), stored, or added to dz when accumulate != 0 (how a cross-entropy gradient is joined without a pass).
+ *   keys fp32 [C][N], order int32 [C][N] (optional, NULL = off): e in pixel order and the pixel index at each sorted position.
+ *   scratch: asis_lovasz_scratch_bytes(N, C) bytes owned by the caller (about 20.5 bytes per pixel and class: two key and two
+ *     payload buffers, the [N][C] gradient, histograms; 0.68 GB at 12 x 588^2 x 8), 8-byte aligned; returns an int64_t, callable
+ *     without a GPU; -1 for N < 1, N >= 2^31 or C outside 1..16.  asis_lovasz_tile(): keys one workgroup handles per sort pass.
+ *   The result is bit-identical from call to call.  C <= 16, N < 2^31. */
+int asis_lovasz_tile(void);
+int64_t asis_lovasz_scratch_bytes(int64_t N, int C);
+int asis_lovasz_softmax(void* stream, const float* logits, const int64_t* target, int B, int h, int w, int H, int W, int C,
+                        int n_softmax, int reduction, float grad_scale, int accumulate, void* scratch, float* loss,
+                        float* per_class, float* dz, float* keys, int32_t* order);
+
 /* ---------------------------------------------------------------------------------------------
  * Backward of conv -> BN(train) -> ReLU -> upsample stages, weight gradients, optimizer.
  * ------------------------------------------------------------------------------------------- */
