@@ -68,12 +68,12 @@ def lib() -> C.CDLL:
     _lib = C.CDLL(LIB_PATH)
     _declare(_lib)
     _lib.asis_last_error.restype = _lib.asis_gemm_form_name.restype = C.c_char_p
-    _lib.asis_lovasz_scratch_bytes.restype = C.c_int64
+    _lib.asis_lovasz_scratch_bytes.restype = _lib.asis_hardpixel_scratch_bytes.restype = C.c_int64
     return _lib
 
 
 # name -> argtypes ; every function returns int (asis_gemm_form_name, like asis_last_error, a C string, and
-# asis_lovasz_scratch_bytes an int64_t: set in lib())
+# asis_lovasz_scratch_bytes / asis_hardpixel_scratch_bytes an int64_t: set in lib())
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "asis_version": [],
@@ -186,6 +186,9 @@ SIGNATURES = {
     "asis_lovasz_tile": [],
     "asis_lovasz_scratch_bytes": [_i64, _i],  # returns int64_t: set in lib()
     "asis_lovasz_softmax": [_vp, _vp, _vp] + [_i] * 8 + [_f, _i] + [_vp] * 6,
+    "asis_hardpixel_tile": [],
+    "asis_hardpixel_scratch_bytes": [_i64],  # returns int64_t: set in lib()
+    "asis_hardpixel_loss": [_vp] * 4 + [_i] * 8 + [_f, _f, _i64, _i, _f, _i] + [_vp] * 5,
     "asis_ew_blocks": [_i64],
     "asis_bn_bwd_nblk": [_i64, _i],
     "asis_maxpool_bn_relu_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i],

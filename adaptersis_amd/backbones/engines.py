@@ -61,18 +61,39 @@ class pre_vit(_Packed):
         return out
 
 
+def _loss_scratch(engine, attr: str, need: int, device) -> torch.Tensor:
+    """the scratch of a sort / select loss, kept on the engine between steps"""
+    scratch = getattr(engine, attr, None)
+    if scratch is None or scratch.numel() < need or scratch.device != device:
+        scratch = torch.empty((need,), device=device, dtype=torch.uint8)
+        setattr(engine, attr, scratch)
+    return scratch
+
+
 def loss_and_dz(engine, logits: torch.Tensor, target: torch.Tensor, S: float):
     """The loss stage of every engine's ``train_step``: logits fp32 NHWC [B,h,w,C], target int64 [B,H,W] ->
     (loss [1], dz fp32 [B,H,W,C] = S * d loss / d resized logits) for ``engine.loss_kind``, a key of ``SegEngine.LOSSES``.
-    No host sync.  The Lovasz losses keep their sort scratch on the engine between steps."""
+    No host sync.  The Lovasz and the hard-pixel losses keep their scratch on the engine between steps."""
     n_region, lmode, eps, n_ce = SegEngine.LOSSES[engine.loss_kind]
-    if lmode != ops.LOSS_LOVASZ:
+    if lmode not in (ops.LOSS_LOVASZ, ops.LOSS_TOPK, ops.LOSS_FOCAL):
         loss, coef, _ = ops.seg_loss_fwd(logits, target, n_region, lmode, eps, n_ce, None, S)
         return loss, ops.seg_loss_bwd(logits, target, coef, n_region, lmode, n_ce, None)
-    need = ops.lovasz_scratch_bytes(target.numel(), logits.shape[-1])
-    scratch = getattr(engine, "_lovasz_scratch", None)
-    if scratch is None or scratch.numel() < need or scratch.device != logits.device:
-        scratch = engine._lovasz_scratch = torch.empty((need,), device=logits.device, dtype=torch.uint8)
+    if lmode != ops.LOSS_LOVASZ:
+        N = target.numel()
+        scratch = _loss_scratch(engine, "_hardpixel_scratch", ops.hardpixel_scratch_bytes(N), logits.device)
+        if lmode == ops.LOSS_FOCAL:   # FocalLoss(gamma)(softmax(out)): every pixel, alpha = ones, smooth 1e-5
+            return ops.hardpixel_loss(logits, target, ops.HARDPIXEL_FOCAL, N, n_softmax=n_region,
+                                      gamma=getattr(engine, "focal_gamma", 2.0), grad_scale=S, scratch=scratch)
+        K = int(N * getattr(engine, "topk_percent", 10.0) / 100)   # TopKLoss: int(num_voxels * k / 100)
+        if K < 1:
+            raise ValueError(f"topk_percent selects no pixel of {N}")
+        dz, dc = None, None
+        if n_region:  # SoftDiceLoss(apply_nonlin=softmax_helper) half: its dz is the buffer the top-k gradient is added into
+            dc, coef, _ = ops.seg_loss_fwd(logits, target, n_region, ops.LOSS_SOFTDICE, eps, 0, None, S)
+            dz = ops.seg_loss_bwd(logits, target, coef, n_region, ops.LOSS_SOFTDICE, 0, None)
+        loss, dz = ops.hardpixel_loss(logits, target, ops.HARDPIXEL_CE, K, grad_scale=S, dz=dz, scratch=scratch)
+        return (loss if dc is None else dc.add_(loss)), dz
+    scratch = _loss_scratch(engine, "_lovasz_scratch", ops.lovasz_scratch_bytes(target.numel(), logits.shape[-1]), logits.device)
     dz, ce = None, None
     if n_ce:  # CrossentropyND half: its dz is the buffer the Lovasz gradient is added into
         ce, coef, _ = ops.seg_loss_fwd(logits, target, 0, ops.LOSS_NONE, eps, n_ce, None, S)
@@ -103,6 +124,13 @@ class SegEngine(nn.Module):
         # the resized logits plus that term (the analogue of "ce_dc"); see loss_and_dz
         "lovasz": (1, ops.LOSS_LOVASZ, 0.0, 0),
         "ce_lovasz": (1, ops.LOSS_LOVASZ, 0.0, 1),
+        # hard-pixel losses through asis_hardpixel_loss (see loss_and_dz).  "topk": segloss/ND_Crossentropy.py TopKLoss(k=topk_percent)
+        # on the raw resized logits (the convention of "ce_dc" / "ce_lovasz"); "dc_and_topk": segloss/dice_loss.py
+        # DC_and_topk_loss({}, {"k": topk_percent}) = SoftDice (n_region 1, smooth 1) through asis_seg_loss_fwd + that;
+        # "focal": segloss/focal_loss.py FocalLoss(gamma=focal_gamma)(softmax(out)) (n_region = its n_softmax)
+        "topk": (0, ops.LOSS_TOPK, 0.0, 0),
+        "dc_and_topk": (1, ops.LOSS_TOPK, 1.0, 0),
+        "focal": (1, ops.LOSS_FOCAL, 0.0, 0),
     }
 
     def __init__(self, model, backbone_encoder, cross_vit: CAViT, cross_cnn: CACNN, seg_decoder, *,
@@ -111,7 +139,7 @@ class SegEngine(nn.Module):
                  train_encoder: bool = False, train_backbone: bool = False, optimize_backbone: bool = False,
                  blocks_per_bucket: int = 4, grad_compress: Optional[str] = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
-                 layer_decay: Optional[float] = None):
+                 layer_decay: Optional[float] = None, topk_percent: float = 10.0, focal_gamma: float = 2.0):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -131,7 +159,10 @@ class SegEngine(nn.Module):
         ``optimizer``: "sgd" (default: ``optim.SGD`` with ``momentum`` / ``weight_decay``, the reference scripts) or "adamw"
         (``optim.AdamW`` with ``betas``, ``eps``, ``weight_decay``, global-norm clipping at ``clip_grad``, ``no_decay`` for 1-D and
         token parameters; ``layer_decay`` scales the learning rate of the ViT bucket per block, so it needs
-        ``optimize_backbone``).  ``clip_grad`` with "sgd" raises: the SGD kernels do not clip."""
+        ``optimize_backbone``).  ``clip_grad`` with "sgd" raises: the SGD kernels do not clip.
+
+        ``topk_percent``: the ``k`` of ``TopKLoss`` for the losses "topk" / "dc_and_topk" (the worst k % of the batch's pixels);
+        ``focal_gamma``: the ``gamma`` of ``FocalLoss`` for "focal"."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -142,6 +173,11 @@ class SegEngine(nn.Module):
         if loss not in self.LOSSES:
             raise ValueError(f"loss must be one of {sorted(self.LOSSES)}")
         self.loss_kind = loss
+        if not 0.0 < topk_percent <= 100.0:
+            raise ValueError("topk_percent must be in (0, 100]")
+        if focal_gamma < 0.0:
+            raise ValueError("focal_gamma must be >= 0")
+        self.topk_percent, self.focal_gamma = float(topk_percent), float(focal_gamma)
         self.is_mla = type(seg_decoder).__name__ == "DecoderMLA"
         # UNet head (BASELINE config 2): fed with the adapter-stream map alone, (B, h, w, D)
         self.stream_only = type(seg_decoder).__name__ == "UNet"

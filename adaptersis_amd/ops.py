@@ -1473,6 +1473,7 @@ def convt2x2_gather(dcat: torch.Tensor, B: int, H: int, W: int, Cout: int, coff:
 
 LOSS_DICE, LOSS_IOU, LOSS_SOFTDICE, LOSS_TVERSKY, LOSS_NONE = 0, 1, 2, 3, 4
 LOSS_LOVASZ = 5  # not a mode of asis_seg_loss_fwd: the engines route it to lovasz_softmax (asis_lovasz_softmax)
+LOSS_TOPK, LOSS_FOCAL = 6, 7  # likewise: routed to hardpixel_loss (asis_hardpixel_loss), kind 0 / kind 1
 
 
 def seg_loss_fwd(logits: torch.Tensor, target: torch.Tensor, n_region: int, mode: int = LOSS_DICE, eps: float = 1e-19,
@@ -1623,6 +1624,61 @@ def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, n_softmax: int = 
                                     loss.data_ptr(), per_class.data_ptr(), _f32c(dz).data_ptr(), _p(keys), _p(order)),
           "asis_lovasz_softmax")
     return (loss, per_class, dz, keys, order) if return_order else (loss, per_class, dz)
+
+
+HARDPIXEL_CE, HARDPIXEL_FOCAL = 0, 1
+
+
+def hardpixel_scratch_bytes(n_pixels: int) -> int:
+    """bytes of caller-owned scratch ``asis_hardpixel_loss`` needs for ``n_pixels`` = B*H*W (needs no GPU)."""
+    nb = lib().asis_hardpixel_scratch_bytes(int(n_pixels))
+    if nb < 0:
+        check(int(nb), "asis_hardpixel_scratch_bytes")
+    return int(nb)
+
+
+def hardpixel_loss(logits: torch.Tensor, target: torch.Tensor, kind: int, K: int, *, n_softmax: int = 0, gamma: float = 2.0,
+                   smooth: float = 1e-5, class_weight: Optional[torch.Tensor] = None, size_average: bool = True,
+                   grad_scale: float = 1.0, dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None,
+                   return_selection: bool = False):
+    """Mean (``size_average``) or sum of the ``K`` largest per-pixel losses of the whole batch, forward and gradient in one call:
+    ``kind`` 0 the cross entropy of resize(logits) (`segloss/ND_Crossentropy.py:34-47`, K = int(N k / 100)), 1 the focal loss of
+    softmax^n_softmax(resize(logits)) (`segloss/focal_loss.py:7-91`, K = N).  logits fp32 NHWC [B,h,w,C]; target int64 [B,H,W];
+    ``class_weight`` fp32 [C] (the cross-entropy weight / the focal alpha) -> (loss [1], dz fp32 [B,H,W,C]) with
+    dz = grad_scale * d loss / d resized logits, exactly 0 on pixels that are not selected; a given ``dz`` is added into on the
+    selected ones (and returned).  ``return_selection`` appends (values fp32 [N], selected uint8 [N]).  Ties at the K-th value go
+    to the lower pixel index.  ``scratch``: a uint8 buffer of at least ``hardpixel_scratch_bytes(B*H*W)`` to reuse between calls
+    (default: a fresh one).  No host sync."""
+    _dev(logits, target, class_weight, dz, scratch)
+    if logits.dim() != 4 or target.dim() != 3:
+        raise ValueError("hardpixel_loss: logits must be NHWC [B,h,w,C] and target [B,H,W]")
+    B, h, w, Cc = logits.shape
+    H, W = target.shape[-2:]
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] != B:
+        raise ValueError("hardpixel_loss: target must be contiguous int64 [B,H,W]")
+    if class_weight is not None and (class_weight.numel() != Cc or class_weight.dtype != torch.float32):
+        raise ValueError("hardpixel_loss: class_weight must be float32 [C]")
+    N = B * H * W
+    if not 1 <= int(K) <= N:
+        raise ValueError(f"hardpixel_loss: K={K} must be in 1..B*H*W={N}")
+    need = hardpixel_scratch_bytes(N)
+    if scratch is None:
+        scratch = torch.empty((need,), device=logits.device, dtype=torch.uint8)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+        raise ValueError(f"hardpixel_loss: scratch must be a contiguous uint8 buffer of at least {need} bytes")
+    accumulate = dz is not None
+    if dz is None:
+        dz = torch.empty((B, H, W, Cc), device=logits.device, dtype=torch.float32)
+    elif tuple(dz.shape) != (B, H, W, Cc) or dz.dtype != torch.float32 or not dz.is_contiguous():
+        raise ValueError("hardpixel_loss: dz must be contiguous float32 [B,H,W,C]")
+    loss = torch.empty((1,), device=logits.device, dtype=torch.float32)
+    values = torch.empty((N,), device=logits.device, dtype=torch.float32) if return_selection else None
+    selected = torch.empty((N,), device=logits.device, dtype=torch.uint8) if return_selection else None
+    check(lib().asis_hardpixel_loss(_stream(), _f32c(logits).data_ptr(), target.data_ptr(), _p(_f32c(class_weight)), B, h, w, H, W,
+                                    Cc, int(kind), int(n_softmax), float(gamma), float(smooth), int(K), int(bool(size_average)),
+                                    float(grad_scale), int(accumulate), scratch.data_ptr(), loss.data_ptr(), dz.data_ptr(),
+                                    _p(values), _p(selected)), "asis_hardpixel_loss")
+    return (loss, dz, values, selected) if return_selection else (loss, dz)
 
 
 # --------------------------------------------------------------------------------------------

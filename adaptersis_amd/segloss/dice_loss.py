@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from .ND_Crossentropy import TopKLoss
 from .dice import seg_loss
 
 
@@ -66,3 +67,21 @@ class DC_and_CE_loss(nn.Module):
 
     def forward(self, net_output, target):
         return seg_loss(net_output, target, 0, ops.LOSS_SOFTDICE, 1.0, n_ce=1)
+
+
+class DC_and_topk_loss(nn.Module):
+    """`dice_loss.py:478-492`: ``TopKLoss(**ce_kwargs)(x, t) + SoftDiceLoss(apply_nonlin=softmax_helper, **soft_dice_kwargs)(x, t)``
+    on NCHW logits; ``t`` is (B,1,H,W)."""
+
+    def __init__(self, soft_dice_kwargs, ce_kwargs, aggregate="sum"):
+        super().__init__()
+        if aggregate != "sum":
+            raise NotImplementedError("nah son")
+        self.aggregate = aggregate
+        self.ce = TopKLoss(**ce_kwargs)
+        self.dc = SoftDiceLoss(apply_nonlin=softmax_helper, **soft_dice_kwargs)
+
+    def forward(self, net_output, target):
+        dc_loss = self.dc(net_output, target)
+        ce_loss = self.ce(net_output, target)
+        return ce_loss + dc_loss

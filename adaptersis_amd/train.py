@@ -163,6 +163,11 @@ def _optimizer_args(args) -> dict:
             "layer_decay": args.layer_decay}
 
 
+def _loss_args(args) -> dict:
+    """The parameters of the hard-pixel losses (--topk_percent, --focal_gamma) as ``SegEngine`` arguments."""
+    return {"topk_percent": getattr(args, "topk_percent", 10.0), "focal_gamma": getattr(args, "focal_gamma", 2.0)}
+
+
 def build_modules(args, head: str, num_classes: int, dev):
     """The five modules of `train.py:170-191` on ``dev``, constructed in the reference's order (so a seeded run draws the same
     initial weights wherever it is called from: ``train_seg`` and ``adaptersis_amd.predict``):
@@ -211,13 +216,14 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     if head == "mla":
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
-                             weight_decay=0.0 if wd is None else wd, num_classes=num_classes, loss=loss, **_optimizer_args(args))
+                             weight_decay=0.0 if wd is None else wd, num_classes=num_classes, loss=loss, **_optimizer_args(args),
+                             **_loss_args(args))
     else:
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=args.lr,
                              weight_decay=3e-5 if wd is None else wd,
                              mode="train_adapters" if getattr(args, "train_adapters", False) else "reference_exact",
                              train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss,
-                             **_optimizer_args(args))
+                             **_optimizer_args(args), **_loss_args(args))
     optimizer = engine.optimizer
 
     dataset_train, dataset_val, collate = open_datasets(args)
@@ -420,7 +426,11 @@ def get_args_parser():
                    help="adamw: layer-wise learning-rate decay of the ViT blocks (engines that optimise the backbone)")
     # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
     p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
-                   help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that")
+                   help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that; "
+                        "topk = TopKLoss (the worst --topk_percent %% of the batch's pixels), dc_and_topk = SoftDice + that, "
+                        "focal = segloss/focal_loss.py FocalLoss on softmax(out)")
+    p.add_argument("--topk_percent", default=10.0, type=float, help="--loss topk / dc_and_topk: the k of TopKLoss, in percent")
+    p.add_argument("--focal_gamma", default=2.0, type=float, help="--loss focal: the gamma of FocalLoss")
     return p
 
 

@@ -679,6 +679,36 @@ int asis_lovasz_softmax(void* stream, const float* logits, const int64_t* target
                         int n_softmax, int reduction, float grad_scale, int accumulate, void* scratch, float* loss,
                         float* per_class, float* dz, float* keys, int32_t* order);
 
+/* Hard-pixel losses (csrc/hardpixel.hip), fused with the resize like the losses above: the top-k cross entropy
+ * (segloss/ND_Crossentropy.py:34-47) and the focal loss (segloss/focal_loss.py:7-91).  N = B*H*W, z = the resized logits of
+ * pixel i = (b*H + y)*W + x, t = target[i]:
+ *   kind 0 (n_softmax = 0 only): v_i = class_weight[t] (logsumexp(z) - z_t) = CrossEntropyLoss(weight, reduce=False) on logits
+ *     without a nonlinearity.
+ *   kind 1: q = z (n_softmax = 0: the buffer holds probabilities) or softmax(z) (1); the one-hot row of t, clamped to
+ *     [smooth/(C-1), 1-smooth] if smooth > 0 (C >= 2 then); pt = sum_c onehot_c q_c + smooth;
+ *     v_i = -class_weight[t] max(1 - pt, 0)^gamma log(pt), class_weight = alpha (focal_loss.py:75-85; the clamp at 0 differs from
+ *     the reference only where that returns NaN: pt an ulp above 1 with a non-integer gamma; the factor's derivative is 0 there).
+ *   class_weight fp32 [C] or NULL = ones.  A label outside 0..C-1: v_i = 0 and no gradient; the pixel still counts in N (the
+ *     reference's ignore_index = -100 stays in num_voxels).
+ *   Selection: the K largest v_i, 1 <= K <= N, ordered by value through an order-preserving map of the fp32 bits (-0 = +0),
+ *     ties by ascending i: an MSB radix select (four 8-bit histogram passes find the K-th largest bit pattern T and
+ *     r = K - #(v > T); among the v == T the first r in pixel order are taken).  K = N selects everything without those passes.
+ *   loss (1 float) = sum of the selected v_i / K; size_average = 0: the plain sum (sums in double, in a fixed order).
+ *   dz fp32 [B,H,W,C] = grad_scale * d loss / d z on selected pixels (kind 0: class_weight[t] (softmax(z) - onehot) / K; kind 1
+ *     through the clamped one-hot and, n_softmax = 1, the softmax transpose); on unselected pixels exactly 0, or left untouched
+ *     when accumulate != 0, which adds the gradient into dz on the selected ones.
+ *   values fp32 [N] (optional): v in pixel order; selected uint8 [N] (optional): 1 where the pixel was taken.
+ *   scratch: asis_hardpixel_scratch_bytes(N) bytes owned by the caller (4 bytes per pixel, 12 per 2048 pixels and 4.3 KB:
+ *     16.6 MB at 12 x 588^2), 8-byte aligned; returns an int64_t, callable without a GPU; -1 for N < 1 or N >= 2^31.
+ *     asis_hardpixel_tile(): values one workgroup handles per pass.
+ *   No host sync; the result is bit-identical from call to call.  C <= 16, N < 2^31. */
+int asis_hardpixel_tile(void);
+int64_t asis_hardpixel_scratch_bytes(int64_t N);
+int asis_hardpixel_loss(void* stream, const float* logits, const int64_t* target, const float* class_weight, int B, int h, int w,
+                        int H, int W, int C, int kind, int n_softmax, float gamma, float smooth, int64_t K, int size_average,
+                        float grad_scale, int accumulate, void* scratch, float* loss, float* dz, float* values,
+                        uint8_t* selected);
+
 /* ---------------------------------------------------------------------------------------------
  * Backward of conv -> BN(train) -> ReLU -> upsample stages, weight gradients, optimizer.
  * ------------------------------------------------------------------------------------------- */
