@@ -19,6 +19,8 @@
 // Workgroup = 4 waves = 128 queries of one (image, head); K / V^T tiles of 64 keys are staged by LDS-DMA into rings of three /
 // two slots (40 KiB, XOR-swizzled 128-B rows, conflict-free ds_read_b128), software-pipelined: see attn_fwd_pipe_kernel.
 // The backward lives in attn_bwd_pipe.hip; asis_transpose_tokens (the V^T image of a row-major V) at the end of this file.
+#include <stdlib.h>
+
 #include <type_traits>
 
 #include "asis_common.h"
@@ -28,6 +30,10 @@ namespace {
 constexpr int QT = 128;  // queries per workgroup
 constexpr int KT = 64;   // keys per tile
 constexpr int HD = 64;   // head dim
+
+enum { FIRST, MID, TAIL };  // the three kinds of key tile, see step()
+template <int M>
+using mode_c = std::integral_constant<int, M>;
 
 __device__ __forceinline__ int perm23(int r) {  // swap bits 2 and 3
   return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1);
@@ -47,9 +53,11 @@ __device__ __forceinline__ int perm23(int r) {  // swap bits 2 and 3
 // tile is staged [key][d] exactly like K and the P.V MFMA's A operand (8 consecutive keys of one d per lane) is assembled by
 // the transposing LDS read ds_read_b64_tr_b16 (two per fragment).  The training forward uses it (both stacked passes and
 // their log-sum-exp in one launch); in the frozen trunk the batched V^T GEMMs are hidden on a side stream and stay.
+// Between the first and the last tile the row maximum is off the critical path: the exponentials run against the running
+// maximum as it stands and the row sums tell whether that was safe (step(); MAXFIRST = the order before that, same bits).
 // A half-tile pipelined rebuild on the backward's structure was measured in round 5 and dropped: the kernel is bound by the
 // vector issue of the two waves that share a SIMD (profiles/r05_attn_fwd_half_ab.txt).
-template <typename T, int SCHED, bool VROWS = false>
+template <typename T, int SCHED, bool VROWS = false, bool MAXFIRST = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(const T* __restrict__ q, const T* __restrict__ k, int64_t ldqk,
                                                               const T* __restrict__ vt, int64_t ldvt, T* __restrict__ o, T* __restrict__ o_lo,
                                                               int64_t ldo, int H, int N1, float scale_log2e,
@@ -148,6 +156,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(const T* __restri
   for (int r = 0; r < 16; ++r) nmb[r] = 0.f;
   const int prow = perm23(fr);
   constexpr float RESCALE_THR = 6.0f;
+  constexpr float SUM_FAST = 48.0f;  // 0.75 * 2^RESCALE_THR
+  int mf_left = 0, mf_span = 2;      // MID tiles that still form their maximum first, and how many the next miss costs: step()
 
   auto k_frags = [&](int slot, v8 (&ka)[2][4]) {
     const T* Ks = Kr + slot * (KT * HD);
@@ -176,9 +186,103 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(const T* __restri
       for (int kb = 0; kb < 2; ++kb) sacc[kb] = T16<T>::mfma32(ka[kb][s], qf[s], sacc[kb]);
   };
 
-  // one iteration: `cur` holds S(t); `nxt` receives S(t+1)
-  auto step = [&](int t, int kslot_next, f32x16 (&cur)[2], f32x16 (&nxt)[2], auto tail_tag) {
-    constexpr bool tail = decltype(tail_tag)::value;  // the last tile: masks, no successor
+  auto tile_max = [&](const f32x16 (&cur)[2]) {  // FOLD: relative to m_run (the offset the chain was opened with)
+    float mx = -1e30f;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, cur[kb][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (!FOLD) mx *= scale_log2e;
+    return mx;
+  };
+  // the online-softmax rescale of a wave in which some row maximum moved by more than RESCALE_THR (always at the first tile)
+  auto rescale = [&](bool first, float mx, f32x16 (&cur)[2]) {
+    if (FOLD) {
+      const float m_new = first ? mx : fmaxf(m_run, m_run + mx);
+      const float delta = m_run - m_new;
+      if (!first) {
+        const float alpha = __builtin_amdgcn_exp2f(delta);
+        l_run *= alpha;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          oacc[0][r] *= alpha;
+          oacc[1][r] *= alpha;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        cur[0][r] += delta;
+        cur[1][r] += delta;
+        nmb[r] = -m_new;
+      }
+      // one definition of the new offset block, tied to the old one's registers: without it the block alternates between two
+      // register sets and the fast path pays eight v_mov_b64 per tile for that
+      asm volatile("" : "+v"(nmb));
+      m_run = m_new;
+    } else {
+      const float m_new = fmaxf(m_run, mx);
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      m_run = m_new;
+      l_run *= alpha;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        oacc[0][r] *= alpha;
+        oacc[1][r] *= alpha;
+      }
+    }
+  };
+  // P = exp2(S - m_run) of one tile as the P.V operand, and the lane's two partial row sums
+  auto exp_tile = [&](const f32x16 (&cur)[2], v8 (&pf)[2][2], float& ps0, float& ps1) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    if (FOLD) {
+      // (row sums as four more MFMAs per tile, ones[32 x keys] . P, were tried: slower than the 32 adds -- the matrix pipe is
+      // the shared resource of the two waves on a SIMD)
+      ps0 = 0.f, ps1 = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const float p0 = __builtin_amdgcn_exp2f(cur[kb][r]), p1 = __builtin_amdgcn_exp2f(cur[kb][r + 1]);
+          ps0 += p0;
+          ps1 += p1;
+          pf[kb][r >> 3][r & 7] = (T)p0;
+          pf[kb][r >> 3][(r & 7) + 1] = (T)p1;
+        }
+    } else {
+      const f32x2 sc2 = {scale_log2e, scale_log2e}, nm2 = {-m_run, -m_run};
+      f32x2 ps2 = {0.f, 0.f};
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const f32x2 s2 = {cur[kb][r], cur[kb][r + 1]};
+          const f32x2 tt = __builtin_elementwise_fma(s2, sc2, nm2);
+          f32x2 p2;
+          p2.x = __builtin_amdgcn_exp2f(tt.x);
+          p2.y = __builtin_amdgcn_exp2f(tt.y);
+          ps2 += p2;
+          pf[kb][r >> 3][r & 7] = (T)p2.x;
+          pf[kb][r >> 3][(r & 7) + 1] = (T)p2.y;
+        }
+      ps0 = ps2.x, ps1 = ps2.y;
+    }
+  };
+
+  // one iteration: `cur` holds S(t); `nxt` receives S(t+1).  Tile 0 (FIRST) and the last tile (TAIL: masks, no successor) form
+  // the row maximum before anything else.  A tile between them (MID) runs speculatively: S(t+1) goes to the matrix pipe at
+  // once and the exponentials use the running maximum as it stands.  A lane whose partial row sum stays below
+  // 0.75 * 2^RESCALE_THR has seen no p, hence no score, that could have moved the maximum by RESCALE_THR (0.75: the error
+  // of v_exp_f32 and of the adds is orders below it; the negated comparison sends inf and NaN the other way), so a wave of
+  // such lanes never forms the maximum.  Any other wave takes it as before, and if it does rescale it redoes the
+  // exponentials and (FOLD) the S(t+1) chain with the new offset: every value is the one the max-first order computes.
+  // Where maxima keep moving (peaked scores: profiles/attn_fwd_rowmax_ab.txt) that redone work would cost more than the
+  // maximum did (a redone S chain is 40 % of a tile), so after a tile that left the fast path the wave runs the next 2, then
+  // 8, then 32 tiles max-first (mf_left, mf_span: wave-uniform): the 28 tiles of the trunk redo at most three.
+  auto step = [&](int t, int kslot_next, f32x16 (&cur)[2], f32x16 (&nxt)[2], auto mode_tag) {
+    constexpr int mode = decltype(mode_tag)::value;
+    constexpr bool tail = mode == TAIL;
+    constexpr bool spec = mode == MID && !MAXFIRST;
     const int key0 = t * KT;
     const bool more = !tail;
     if (t + 2 < nt) dma_k(t + 2, kslot_next == 2 ? 0 : kslot_next + 1);
@@ -194,83 +298,39 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(const T* __restri
           if (key >= N) cur[kb][r] = -1e30f;
         }
     }
-    float mx = -1e30f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, cur[kb][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (!FOLD) mx *= scale_log2e;
-    if (FOLD) {
-      // cur holds s - m_run (the offset its chain was opened with); mx is the tile maximum relative to m_run
-      if (t == 0 || __any(mx > RESCALE_THR)) {
-        const float m_new = t == 0 ? mx : fmaxf(m_run, m_run + mx);
-        const float delta = m_run - m_new;
-        if (t != 0) {
-          const float alpha = __builtin_amdgcn_exp2f(delta);
-          l_run *= alpha;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            oacc[0][r] *= alpha;
-            oacc[1][r] *= alpha;
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          cur[0][r] += delta;
-          cur[1][r] += delta;
-          nmb[r] = -m_new;
-        }
-        m_run = m_new;
-      }
-    } else if (__any(mx > m_run + RESCALE_THR)) {
-      const float m_new = fmaxf(m_run, mx);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      m_run = m_new;
-      l_run *= alpha;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        oacc[0][r] *= alpha;
-        oacc[1][r] *= alpha;
-      }
+    v8 pf[2][2];
+    float ps0, ps1;
+    // the max-first front part: always outside MID, in a MID tile after one that left the fast path
+    bool looked = !spec;
+    if (!spec || mf_left > 0) {
+      const float mx = tile_max(cur);
+      const bool first = FOLD && (mode == FIRST || (tail && t == 0));
+      const bool resc = first || __any(FOLD ? mx > RESCALE_THR : mx > m_run + RESCALE_THR);
+      if (resc) rescale(first, mx, cur);
+      if (spec) --mf_left;
+      looked = true;
     }
     // S(t+1) goes to the matrix pipe here, in the same basic block as the exponentials of tile t
     if (!tail) s_mfma(ka, nxt);
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    v8 pf[2][2];
-    if (FOLD) {
-      // (row sums as four more MFMAs per tile, ones[32 x keys] . P, were tried: slower than the 32 adds -- the matrix pipe is
-      // the shared resource of the two waves on a SIMD)
-      float ps0 = 0.f, ps1 = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float p0 = __builtin_amdgcn_exp2f(cur[kb][r]), p1 = __builtin_amdgcn_exp2f(cur[kb][r + 1]);
-          ps0 += p0;
-          ps1 += p1;
-          pf[kb][r >> 3][r & 7] = (T)p0;
-          pf[kb][r >> 3][(r & 7) + 1] = (T)p1;
+    exp_tile(cur, pf, ps0, ps1);
+    if (spec && !looked) {
+      if (__any(!(ps0 + ps1 < SUM_FAST))) {
+        mf_left = mf_span;
+        mf_span = mf_span < 32 ? 4 * mf_span : 32;
+        const float mx = tile_max(cur);
+        if (__any(FOLD ? mx > RESCALE_THR : mx > m_run + RESCALE_THR)) {
+          rescale(false, mx, cur);
+          exp_tile(cur, pf, ps0, ps1);
+          if (FOLD) {  // the ring slot of K(t+1) stays valid until the barrier below; a second read, so that the
+                       // fragments are not 32 registers kept alive across the branch
+            asm volatile("" ::: "memory");
+            k_frags(kslot_next, ka);
+            s_mfma(ka, nxt);
+          }
         }
-      l_run += ps0 + ps1;
-    } else {
-    const f32x2 sc2 = {scale_log2e, scale_log2e}, nm2 = {-m_run, -m_run};
-    f32x2 ps2 = {0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const f32x2 s2 = {cur[kb][r], cur[kb][r + 1]};
-        const f32x2 tt = __builtin_elementwise_fma(s2, sc2, nm2);
-        f32x2 p2;
-        p2.x = __builtin_amdgcn_exp2f(tt.x);
-        p2.y = __builtin_amdgcn_exp2f(tt.y);
-        ps2 += p2;
-        pf[kb][r >> 3][r & 7] = (T)p2.x;
-        pf[kb][r >> 3][(r & 7) + 1] = (T)p2.y;
       }
-    l_run += ps2.x + ps2.y;
     }
+    l_run += ps0 + ps1;
     const T* Vs = Vr + (t & 1) * (KT * HD);
 #pragma unroll
     for (int db = 0; db < 2; ++db) {
@@ -324,20 +384,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(const T* __restri
     k_frags(0, ka);
     s_mfma(ka, sA);
   }
-  int slot = 1;  // ring slot of K(t+1)
   int t = 0;
-  for (; t + 2 < nt; t += 2) {  // tiles 0 .. nt-2 are full and have a successor
-    step(t, slot, sA, sB, std::false_type{});
-    slot = slot == 2 ? 0 : slot + 1;
-    step(t + 1, slot, sB, sA, std::false_type{});
-    slot = slot == 2 ? 0 : slot + 1;
+  if (nt > 1) {
+    step(0, 1, sA, sB, mode_c<FIRST>{});
+    int slot = 2;  // ring slot of K(t+1)
+    for (t = 1; t + 2 < nt; t += 2) {  // tiles 1 .. nt-2 are full and have a successor
+      step(t, slot, sB, sA, mode_c<MID>{});
+      slot = slot == 2 ? 0 : slot + 1;
+      step(t + 1, slot, sA, sB, mode_c<MID>{});
+      slot = slot == 2 ? 0 : slot + 1;
+    }
+    if (t + 1 < nt) {
+      step(t, slot, sB, sA, mode_c<MID>{});
+      ++t;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sA[0][r] = sB[0][r], sA[1][r] = sB[1][r];
+    }
   }
-  if (t + 1 < nt) {
-    step(t, slot, sA, sB, std::false_type{});
-    step(t + 1, 0, sB, sA, std::true_type{});
-  } else {
-    step(t, 0, sA, sB, std::true_type{});
-  }
+  step(t, 0, sA, sB, mode_c<TAIL>{});
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
@@ -398,16 +463,23 @@ static int attention_fwd_impl(void* stream, int dtype, const void* q, const void
   // one kernel, four forms: a pre-scaled q (the folded form: -m rides in the score chain) or the scale applied in the softmax;
   // V pre-transposed or row-major (transposing LDS reads)
   const bool fold = prescaled != 0;
-#define ASIS_ATTN_PIPE_LAUNCH(SC, VR)                                                                                  \
-  hipLaunchKernelGGL((attn_fwd_pipe_kernel<T, SC, VR>), grid, block, 0, s, static_cast<const T*>(q),                   \
+  // ASIS_ATTN_MAXFIRST=1: every tile forms its row maximum first (the order before the speculative one; same bits, for A/B
+  // runs and the identity test).  Read on every call so that one process can run both.
+  const char* mf_env = getenv("ASIS_ATTN_MAXFIRST");
+  const bool maxfirst = mf_env && mf_env[0] == '1';
+#define ASIS_ATTN_PIPE_LAUNCH_MF(SC, VR, MF)                                                                           \
+  hipLaunchKernelGGL((attn_fwd_pipe_kernel<T, SC, VR, MF>), grid, block, 0, s, static_cast<const T*>(q),               \
                      static_cast<const T*>(k), ldqk, static_cast<const T*>(vt), ldvt, static_cast<T*>(o),              \
                      static_cast<T*>(o_lo), ldo, H, N1, sl, lse2, B1, N2, prescaled, mx_amax)
+#define ASIS_ATTN_PIPE_LAUNCH(SC, VR) \
+  do { if (maxfirst) ASIS_ATTN_PIPE_LAUNCH_MF(SC, VR, true); else ASIS_ATTN_PIPE_LAUNCH_MF(SC, VR, false); } while (0)
   if (int rc = asis_dispatch16(dtype, "asis_attention_fwd", [&](auto t) {
         using T = decltype(t);
         if (vrows) { if (fold) ASIS_ATTN_PIPE_LAUNCH(3, true); else ASIS_ATTN_PIPE_LAUNCH(0, true); }
         else { if (fold) ASIS_ATTN_PIPE_LAUNCH(3, false); else ASIS_ATTN_PIPE_LAUNCH(0, false); }
       })) return rc;
 #undef ASIS_ATTN_PIPE_LAUNCH
+#undef ASIS_ATTN_PIPE_LAUNCH_MF
   ASIS_CHECK_LAUNCH("asis_attention_fwd");
   return ASIS_OK;
 }
