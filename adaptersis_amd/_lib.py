@@ -69,11 +69,12 @@ def lib() -> C.CDLL:
     _declare(_lib)
     _lib.asis_last_error.restype = _lib.asis_gemm_form_name.restype = C.c_char_p
     _lib.asis_lovasz_scratch_bytes.restype = _lib.asis_hardpixel_scratch_bytes.restype = C.c_int64
+    _lib.asis_surface_quantile_scratch_bytes.restype = C.c_int64
     return _lib
 
 
 # name -> argtypes ; every function returns int (asis_gemm_form_name, like asis_last_error, a C string, and
-# asis_lovasz_scratch_bytes / asis_hardpixel_scratch_bytes an int64_t: set in lib())
+# asis_lovasz_scratch_bytes / asis_hardpixel_scratch_bytes / asis_surface_quantile_scratch_bytes an int64_t: set in lib())
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "asis_version": [],
@@ -210,6 +211,8 @@ SIGNATURES = {
     "asis_predict_mask_views": [_vp] * 5 + [_i] * 5 + [_vp] * 10,
     "asis_predict_mask_tiles": [_vp] * 6 + [_i] * 4 + [_f] + [_i] * 4 + [_vp] * 10,
     "asis_surface_stats": [_vp] * 5 + [_i] * 6 + [_vp, _i] + [_vp] * 6 + [_i],
+    "asis_surface_quantile_scratch_bytes": [_i, _i, _i],  # returns int64_t: set in lib()
+    "asis_surface_quantiles": [_vp] * 4 + [_i] * 7 + [_vp, _i] + [_vp] * 3,
     "asis_dropout_f32": [_vp, _vp, _vp, _vp, _i64, C.c_uint64, _i, _f, _f, _vp, _i],
     "asis_dropout_t16": [_vp, _i, _vp, _vp, _i64, C.c_uint64, _i, _f, _i],
     "asis_dropout_mask": [_vp, _vp, _i64, C.c_uint64, _i, _f],

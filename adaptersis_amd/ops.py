@@ -2205,18 +2205,30 @@ def surface_thresholds(tolerances) -> list:
     return [int(math.floor(t * t)) for t in tol]
 
 
-def surface_plan(B: int, H: int, W: int, C: int, budget: Optional[int] = None):
+def surface_plan(B: int, H: int, W: int, C: int, budget: Optional[int] = None, percentiles: bool = False):
     """-> (frames per call, classes per call): the largest whose vertical-distance maps (uint16, both sides) fit ``budget``
-    (default ``SURFACE_WORKSPACE_BYTES``); one class of one frame is always allowed."""
+    (default ``SURFACE_WORKSPACE_BYTES``); one class of one frame is always allowed.  ``percentiles``: the int32 distances at the
+    edge pixels of both sides (``dq`` of asis_surface_quantiles, per frame whatever the number of classes) count as well."""
     budget = SURFACE_WORKSPACE_BYTES if budget is None else int(budget)
     per_class = 2 * H * W * 2
-    nc = max(1, min(C, budget // per_class))
-    nb = max(1, min(B, budget // (per_class * nc))) if nc == C else 1
+    per_frame = 2 * H * W * 4 if percentiles else 0
+    nc = max(1, min(C, (budget - per_frame) // per_class))
+    nb = max(1, min(B, budget // (per_class * nc + per_frame))) if nc == C else 1
     return nb, nc
 
 
+def surface_percentiles(percentiles) -> list:
+    """Percents in 0..100, each a multiple of 0.01 (to within 1e-9) -> the integers q in 0..10000 (hundredths of a percent)
+    that asis_surface_quantiles takes; at most 4."""
+    from .segloss.surface import percentile_qs
+    try:
+        return percentile_qs(percentiles)
+    except ValueError as e:
+        raise ValueError(f"surface_stats: {e}") from None
+
+
 def surface_stats(pred: torch.Tensor, target: torch.Tensor, num_classes: int, tolerances, *, pred_lut=None, lut=None,
-                  return_d2: Optional[str] = None):
+                  return_d2: Optional[str] = None, percentiles=None):
     """Boundary statistics of label maps against their ground truth (csrc/surface.hip; definitions in include/asis_hip.h).
     ``pred``, ``target``: contiguous uint8 [B,H,W] raw pixel values on the device; ``pred_lut`` / ``lut``: uint8 [256] label tables
     (None = identity; a value >= C is no class); ``tolerances`` in pixels, at most 8.
@@ -2224,7 +2236,12 @@ def surface_stats(pred: torch.Tensor, target: torch.Tensor, num_classes: int, to
        sums float64 [B, C, 2] = sum over E(P) of sqrt(d2_G), sum over E(G) of sqrt(d2_P) (bit-identical between calls);
        with ``return_d2`` = "pred" / "target" also the exact squared-distance field of that side's edge pixels, int32 [B,C,H,W]
        (-1 where the class has no edge pixel on that side of the frame).
+    ``percentiles``: None, or at most 4 percents in 0..100, multiples of 0.01: after ``sums`` (before ``d2``) also
+       ord int64 [B, C, P, 3, 2] = the order statistics (v[lo], v[hi]) of the squared distances over E(P), over E(G) and over
+       the two pooled (asis_surface_quantiles: a radix select on the device; ranks and interpolation in segloss/surface.py);
+       -1 for a class that is not on both sides of the frame.
     Frames and classes are processed in chunks so that the intermediate maps stay under ``SURFACE_WORKSPACE_BYTES``."""
+    qs = surface_percentiles(percentiles) if percentiles is not None else None
     _dev(pred, target)
     for name, t in (("pred", pred), ("target", target)):
         if t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous():
@@ -2250,11 +2267,18 @@ def surface_stats(pred: torch.Tensor, target: torch.Tensor, num_classes: int, to
     ints = torch.zeros((B, Cc, 7 + 2 * T), device=dev, dtype=torch.int64)
     sums = torch.zeros((B, Cc, 2), device=dev, dtype=torch.float64)
     d2 = torch.full((B, Cc, H, W), -1, device=dev, dtype=torch.int32) if return_d2 else None
-    nb, nc = surface_plan(B, H, W, Cc)
+    nb, nc = surface_plan(B, H, W, Cc, percentiles=qs is not None)
     edges = torch.empty((nb, 2, H, W), device=dev, dtype=torch.uint8)
     g = torch.empty((nb, 2, nc, H, W), device=dev, dtype=torch.int16)     # uint16 on the device
     partial = torch.empty((nb, 2, nc, H), device=dev, dtype=torch.float64)
     thr_c = (C.c_int32 * max(T, 1))(*thr)
+    ord_ = None
+    if qs is not None:
+        P = len(qs)
+        q_c = (C.c_int32 * P)(*qs)
+        ord_ = torch.full((B, Cc, P, 3, 2), -1, device=dev, dtype=torch.int64)
+        dq = torch.empty((nb, 2, H, W), device=dev, dtype=torch.int32)
+        scratch = torch.empty((surface_quantile_scratch_bytes(nb, nc, P),), device=dev, dtype=torch.uint8)
     for b0 in range(0, B, nb):
         n = min(nb, B - b0)
         for c0 in range(0, Cc, nc):
@@ -2263,7 +2287,19 @@ def surface_stats(pred: torch.Tensor, target: torch.Tensor, num_classes: int, to
                                            g.data_ptr(), partial.data_ptr(), ints[b0:b0 + n].data_ptr(), sums[b0:b0 + n].data_ptr(),
                                            _p(d2[b0:b0 + n]) if d2 is not None else None, 1 if return_d2 == "target" else 0),
                   "asis_surface_stats")
-    return (ints, sums, d2) if d2 is not None else (ints, sums)
+            if qs is not None:      # edges, g and ints of the chunk are still those of the call above
+                check(lib().asis_surface_quantiles(_stream(), edges.data_ptr(), g.data_ptr(), ints[b0:b0 + n].data_ptr(), n, H, W, Cc,
+                                                   c0, min(nc, Cc - c0), T, q_c, P, dq.data_ptr(), scratch.data_ptr(),
+                                                   ord_[b0:b0 + n].data_ptr()), "asis_surface_quantiles")
+    return (ints, sums) + ((ord_,) if ord_ is not None else ()) + ((d2,) if d2 is not None else ())
+
+
+def surface_quantile_scratch_bytes(B: int, nc: int, P: int) -> int:
+    """Bytes of the histogram / state scratch of asis_surface_quantiles for ``B`` frames and ``nc`` classes per call."""
+    n = lib().asis_surface_quantile_scratch_bytes(int(B), int(nc), int(P))
+    if n < 0:
+        check(int(n), "asis_surface_quantile_scratch_bytes")
+    return int(n)
 
 
 # ---- dropout of the MaskTransformer head (csrc/dropout.hip: counter-based masks, include/asis_hip.h) -----------------------------

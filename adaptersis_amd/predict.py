@@ -12,7 +12,8 @@ as uint8, resized on the device (``ops.frame_resize``, PIL-exact) and normalised
 bilinear resize of the logits, argmax, pixel value; optionally the overlay and the per-class pixel counts against the ground
 truth); with ``--surface`` the boundary statistics of every frame are made from that mask and the ground truth where they already
 are, on the device (``ops.surface_stats``: exact distance transform; Dice, normalised surface distance, Hausdorff and mean
-surface distance per class under ``"surface"`` in ``metrics.json``, ``segloss/surface.py``); PNGs are written by a small thread pool under ``--pred_dir`` with the input's relative path and stem.
+surface distance per class under ``"surface"`` in ``metrics.json``, ``segloss/surface.py``; with ``--hd_percentile`` also the
+percentile Hausdorff distance, HD95 by default, its order statistics selected on the device); PNGs are written by a small thread pool under ``--pred_dir`` with the input's relative path and stem.
 
 Batches: frames are grouped by native size, sizes in ascending order, paths sorted inside a size, ``--batch_size_per_gpu``
 frames per batch (the last batch of a size may be short).  The composition is a function of the file list and the batch size
@@ -98,6 +99,7 @@ def get_args_parser():
                    help="with --masks: per-frame Dice and boundary metrics (normalised surface distance at these tolerances, in "
                         "pixels at native size; Hausdorff; mean surface distance) under 'surface' in metrics.json; no value = "
                         + " ".join(f"{t:g}" for t in DEFAULT_TOLERANCES))
+    add_hd_percentile(p)
     p.add_argument("--tta_flip", action="store_true", help="test-time augmentation: also predict every frame mirrored, at every size")
     p.add_argument("--tta_sizes", nargs="+", type=int, default=None, metavar="S",
                    help="test-time augmentation: input sizes of the views (default: --imsize alone); each as --imsize is given to train")
@@ -458,13 +460,33 @@ def surface_tolerances(args) -> Optional[List[float]]:
     return tol
 
 
+def add_hd_percentile(p) -> None:
+    p.add_argument("--hd_percentile", nargs="*", type=float, default=None, metavar="P",
+                   help="with --surface: percentile Hausdorff distances (percents, multiples of 0.01, at most 4) per class under "
+                        "'surface' in metrics.json: hd_pct over the pooled boundary distances, hd_pct_sym the larger of the two "
+                        "directed percentiles; no value = 95")
+
+
+def hd_percentiles(args) -> Optional[List[float]]:
+    """The percents of ``--hd_percentile`` (None = not asked for; no value = 95), checked like ``surface_tolerances``."""
+    if getattr(args, "hd_percentile", None) is None:
+        return None
+    if getattr(args, "surface", None) is None:
+        raise ValueError("--hd_percentile needs --surface: the percentiles are taken over the boundary distances")
+    pct = [float(v) for v in args.hd_percentile] or [95.0]
+    from . import ops
+    ops.surface_percentiles(pct)
+    return pct
+
+
 def surface_batch(meter, mask: torch.Tensor, target: torch.Tensor, args, lut) -> None:
     """Boundary statistics of one batch, on the device: ``mask`` as ``SegEngine.predict`` encoded it (read back through the label
     table that ``--encode`` inverts), ``target`` the raw ground truth with the dataset's table.  Only the statistics come to the
     host, into ``meter``."""
     from . import ops
-    ints, sums = ops.surface_stats(mask, target, args.num_classes, meter.tol, pred_lut=_fr.ENCODINGS[args.encode][1], lut=lut)
-    meter.update(ints.cpu().numpy(), sums.cpu().numpy())
+    out = ops.surface_stats(mask, target, args.num_classes, meter.tol, pred_lut=_fr.ENCODINGS[args.encode][1], lut=lut,
+                            percentiles=meter.pct)
+    meter.update(*(t.cpu().numpy() for t in out))
 
 
 def metrics_from_counts(counts: np.ndarray) -> dict:
@@ -481,7 +503,10 @@ def metrics_from_counts(counts: np.ndarray) -> dict:
 
 def surface_line(s: dict) -> str:
     nsd = " ".join(f"{t:g}px " + ("-" if v is None else f"{v:.4f}") for t, v in zip(s["tolerances"], s["mean_nsd"]))
-    return (f"* boundary (classes 1..): Dice {s['mean_dice']}  NSD [{nsd}]  Hausdorff {s['mean_hd']}  mean surface distance "
+    pct = ""
+    if "percentiles" in s:      # the first percentile asked for
+        pct = f"  HD{s['percentiles'][0]:g} {s['mean_hd_pct'][0]} (directed maximum {s['mean_hd_pct_sym'][0]})"
+    return (f"* boundary (classes 1..): Dice {s['mean_dice']}  NSD [{nsd}]  Hausdorff {s['mean_hd']}{pct}  mean surface distance "
             f"{s['mean_assd']}  unmatched (frame, class) pairs {sum(p['unmatched'] for p in s['per_class'])}")
 
 
@@ -500,13 +525,14 @@ def predict_seg(args, engine: Optional[SegEngine] = None) -> dict:
     the writer threads), "drain_seconds" (waiting for the writers after the last batch), "frames_per_second"}."""
     _fr.encode_table(args.encode, args.num_classes)          # argument errors before any model is built
     tolerances = surface_tolerances(args)
+    percentiles = hd_percentiles(args)
     tiles = tiles_of(args)
     views = None if tiles is not None else views_of(args)
     with_conf = (views is not None or tiles is not None) and bool(args.confidence)
     meter = None
     if tolerances is not None:
         from .segloss.surface import SurfaceMeter
-        meter = SurfaceMeter(args.num_classes, tolerances)
+        meter = SurfaceMeter(args.num_classes, tolerances, percentiles)
     frames = _Frames(args)
     batches = plan_batches(frames.sizes, args.batch_size_per_gpu)
     engine = engine or build_engine(args)

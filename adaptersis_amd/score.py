@@ -39,6 +39,7 @@ def get_args_parser():
     p.add_argument("--surface", nargs="*", type=float, default=None, metavar="TAU",
                    help="boundary metrics at these tolerances (pixels); no value = "
                         + " ".join(f"{t:g}" for t in _p.DEFAULT_TOLERANCES))
+    _p.add_hd_percentile(p)
     return p
 
 
@@ -95,21 +96,21 @@ def score(args) -> dict:
     _fr.encode_table(args.encode, C)
     tol = [] if args.surface is None else ([float(t) for t in args.surface] or list(_p.DEFAULT_TOLERANCES))
     ops.surface_thresholds(tol)
+    pct = _p.hd_percentiles(args)
     if not torch.cuda.is_available():
         raise RuntimeError("adaptersis_amd.score needs an MI355X (there is no CPU path)")
     pairs = _Pairs(args)
-    meter = SurfaceMeter(C, tol) if args.surface is not None else None
+    meter = SurfaceMeter(C, tol, pct) if args.surface is not None else None
     pred_lut = _fr.ENCODINGS[args.encode][1]
     counts = np.zeros((C, 3), dtype=np.int64)
     for idx in _p.plan_batches(pairs.sizes, args.batch_size_per_gpu):
         items = [pairs.load(i) for i in idx]
         pred = torch.from_numpy(np.stack([it[0] for it in items])).cuda().contiguous()
         target = torch.from_numpy(np.stack([it[1] for it in items])).cuda().contiguous()
-        ints, sums = ops.surface_stats(pred, target, C, tol, pred_lut=pred_lut, lut=pairs.lut)
-        ints, sums = ints.cpu().numpy(), sums.cpu().numpy()
-        counts += ints[:, :, :3].sum(0)
+        out = [t.cpu().numpy() for t in ops.surface_stats(pred, target, C, tol, pred_lut=pred_lut, lut=pairs.lut, percentiles=pct)]
+        counts += out[0][:, :, :3].sum(0)
         if meter is not None:
-            meter.update(ints, sums)
+            meter.update(*out)
     metrics = _p.metrics_from_counts(counts)
     metrics["frames"] = len(pairs.stems)
     if meter is not None:

@@ -877,6 +877,25 @@ int asis_surface_stats(void* stream, const uint8_t* pred, const uint8_t* target,
                        int H, int W, int C, int c0, int nc, const int32_t* thr, int T, uint8_t* edges, uint16_t* g,
                        double* partial, int64_t* ints, double* sums, int32_t* d2, int d2_side);
 
+/* Percentile Hausdorff (csrc/surface.hip): exact order statistics of the distance multisets of every (frame, class), selected on
+ * the device.  With P, G, E(.) and d2 as above, three multisets of exact integers per (frame, class):
+ *     set 0 = { d2_G(p) : p in E(P) }, n = e_pred;   set 1 = { d2_P(g) : g in E(G) }, n = e_lab;   set 2 = the two pooled.
+ *   A percentile is an integer q in 0..10000, hundredths of a percent (9500 = 95 %, 9950 = 99.5 %).  With v[0..n-1] the set
+ *     sorted ascending: r = (n - 1) q in 64-bit integers, lo = r / 10000, rem = r % 10000, hi = lo + (rem != 0).  The device
+ *     returns the integers v[lo] and v[hi]; the host forms sqrt(v[lo]) + (rem / 10000) (sqrt(v[hi]) - sqrt(v[lo])) in float64:
+ *     numpy.percentile(sqrt(v), q / 100) with linear interpolation, the rank taken exactly.
+ *     hd_pct = that percentile of set 2;  hd_pct_sym = the larger of the percentiles of set 0 and set 1.
+ *   Called for the chunk (B, c0, nc) directly after asis_surface_stats, while edges, g and ints of that chunk are valid (T as
+ *     there: the rows of ints have 7 + 2 T entries).  q int32 [P] on the HOST, 1 <= P <= 4.
+ *   dq int32 [B][2][H][W]: workspace (d2 at the query edge pixels; nothing else of it is written or read).
+ *   scratch: asis_surface_quantile_scratch_bytes(B, nc, P) bytes, 16-byte aligned (histograms and the state of the select).
+ *   ord int64 [B][C][P][3][2] = (v[lo], v[hi]) per set, written for the classes c0 .. c0 + nc - 1 that are matched in the frame
+ *     (edge pixels on both sides); the caller pre-fills it with -1 and the entries of unmatched classes are not written.
+ *   Integer arithmetic only; ord is bit-identical between calls. */
+int64_t asis_surface_quantile_scratch_bytes(int B, int nc, int P);
+int asis_surface_quantiles(void* stream, const uint8_t* edges, const uint16_t* g, const int64_t* ints, int B, int H, int W, int C,
+                           int c0, int nc, int T, const int32_t* q, int P, int32_t* dq, void* scratch, int64_t* ord);
+
 /* ---------------------------------------------------------------------------------------------
  * Dropout of the MaskTransformer decode head (backbones/masktrans_block.py:11-89: nn.Dropout(p) on the attention probabilities,
  * the projection output, behind GELU and behind fc2; eval_dinov2_masktrans.py:136-139 builds it with p = 0.1).  csrc/dropout.hip.
