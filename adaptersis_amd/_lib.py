@@ -206,6 +206,8 @@ SIGNATURES = {
     "asis_augment": [_vp] * 13 + [_i, _i],
     "asis_augment_geo_u8": [_vp] * 12 + [_i, _i],
     "asis_clahe": [_vp] * 13 + [_i, _i, _i],
+    "asis_nonrigid_map": [_vp] * 7 + [_i] + [_vp] * 3 + [_i, _i],
+    "asis_nonrigid_remap": [_vp] * 6 + [_i, _i],
     "asis_frame_resize": [_vp] * 5 + [_i, _vp, _vp, _i] + [_vp] * 6 + [_i] * 5,
     "asis_predict_mask": [_vp, _vp] + [_i] * 6 + [_vp] * 9,
     "asis_predict_mask_views": [_vp] * 5 + [_i] * 5 + [_vp] * 10,

@@ -12,23 +12,9 @@
 // image and layer at N = 1766 — this head is two layers on a 288 GB part) built from batched asis_gemm launches and the two
 // row kernels below; the fused flash kernels serve every path without dropout.
 #include "asis_common.h"
+#include "philox.h"
 
 namespace {
-
-struct philox4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += W0; k1 += W1;
-  }
-  return philox4{c0, c1, c2, c3};
-}
 
 // the four keep flags of elements 4 * blk .. 4 * blk + 3 of dropout layer `site`
 __device__ __forceinline__ void keep4(uint64_t seed, uint32_t site, uint64_t blk, uint32_t thr, bool k[4]) {

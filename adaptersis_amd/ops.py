@@ -1921,9 +1921,14 @@ def augment(img_u8: torch.Tensor, mask_u8: torch.Tensor, tables: dict):
     out = torch.empty((B, 3, S, S), device=img_u8.device, dtype=torch.float32)
     mout = torch.empty((B, S, S), device=img_u8.device, dtype=torch.int64)
     cl = tables.get("clahe")
-    if cl is not None and tables.get("clahe_any", True):
-        # CLAHE samples in the batch (train.py:161): geometric stage -> uint8, tile LUTs, blend + Lab -> RGB + tables + / 255
+    nonrigid = bool(tables.get("nonrigid_any", False))
+    if nonrigid or (cl is not None and tables.get("clahe_any", True)):
+        # CLAHE samples in the batch (train.py:161): geometric stage -> uint8, tile LUTs, blend + Lab -> RGB + tables + / 255.
+        # Non-rigid samples (train.py:151-158): map + remap between the two; the per-sample flag of the CLAHE kernels leaves a
+        # sample without CLAHE to the tables and / 255
         from .tools import clahe as _cl
+        if cl is None:
+            cl = torch.zeros((B, 2), device=img_u8.device, dtype=torch.int32)
         if cl.dtype != torch.int32 or tuple(cl.shape) != (B, 2) or not cl.is_contiguous():
             raise ValueError("augment: table clahe must be contiguous int32 (B, 2)")
         _dev(cl)
@@ -1933,6 +1938,8 @@ def augment(img_u8: torch.Tensor, mask_u8: torch.Tensor, tables: dict):
                                         tables["xofs"].data_ptr(), tables["yofs"].data_ptr(), tables["xa"].data_ptr(),
                                         tables["ya"].data_ptr(), tables["mx"].data_ptr(), tables["my"].data_ptr(),
                                         geo8.data_ptr(), mout.data_ptr(), B, S), "asis_augment_geo_u8")
+        if nonrigid:
+            geo8, mout = nonrigid_remap(geo8, mout, nonrigid_map(tables, S))
         luts = torch.empty((B, _cl.TILES, _cl.TILES, 256), device=img_u8.device, dtype=torch.uint8)
         check(lib().asis_clahe(_stream(), geo8.data_ptr(), cl.data_ptr(), lt["gamma"].data_ptr(), lt["cbrt"].data_ptr(),
                                lt["l2yf"].data_ptr(), lt["ab2xz"].data_ptr(), lt["invgamma"].data_ptr(),
@@ -1943,6 +1950,49 @@ def augment(img_u8: torch.Tensor, mask_u8: torch.Tensor, tables: dict):
                              tables["xofs"].data_ptr(), tables["yofs"].data_ptr(), tables["xa"].data_ptr(),
                              tables["ya"].data_ptr(), tables["mx"].data_ptr(), tables["my"].data_ptr(), tables["lut"].data_ptr(),
                              out.data_ptr(), mout.data_ptr(), B, S), "asis_augment")
+    return out, mout
+
+
+def nonrigid_map(tables: dict, S: int, return_field: bool = False):
+    """The coordinate maps of the non-rigid block (csrc/nonrigid.hip) from the tables of
+    ``tools.augment.TrainAugment.nonrigid_tables`` -> int32 [B,S,S,2] = (x, y) source coordinate in 1/32 pixel.
+    ``return_field``: also the elastic displacement field fp32 [B,2,S,S] (zero for samples of another kind)."""
+    kind = tables["nr_kind"]
+    B = kind.shape[0]
+    gauss = tables["nr_gauss"]
+    want = {"nr_kind": (torch.int32, (B,)), "nr_par": (torch.float32, (B, 8)), "nr_seed": (torch.int64, (B,)),
+            "nr_gx": (torch.float32, (B, S)), "nr_gy": (torch.float32, (B, S)), "nr_gauss": (torch.float32, tuple(gauss.shape))}
+    for k, (dt, shp) in want.items():
+        t = tables[k]
+        if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"nonrigid_map: table {k} must be contiguous {dt} {shp}")
+    _dev(*[tables[k] for k in want])
+    if gauss.dim() != 1 or gauss.numel() % 2 != 1:
+        raise ValueError("nonrigid_map: table nr_gauss must hold 2 r + 1 weights")
+    dev = kind.device
+    tmp = torch.empty((B, 2, S, S), device=dev, dtype=torch.float32)
+    out = torch.empty((B, S, S, 2), device=dev, dtype=torch.int32)
+    field = torch.zeros((B, 2, S, S), device=dev, dtype=torch.float32) if return_field else None
+    check(lib().asis_nonrigid_map(_stream(), kind.data_ptr(), tables["nr_par"].data_ptr(), tables["nr_seed"].data_ptr(),
+                                  tables["nr_gx"].data_ptr(), tables["nr_gy"].data_ptr(), gauss.data_ptr(), gauss.numel() // 2,
+                                  tmp.data_ptr(), out.data_ptr(), field.data_ptr() if return_field else None, B, S),
+          "asis_nonrigid_map")
+    return (out, field) if return_field else out
+
+
+def nonrigid_remap(img_u8: torch.Tensor, mask: torch.Tensor, map_q5: torch.Tensor):
+    """uint8 [B,S,S,3] + int64 [B,S,S] through a Q5 map int32 [B,S,S,2] (``nonrigid_map``): integer bilinear for the image,
+    nearest for the mask, reflect-101 border -> (uint8 [B,S,S,3], int64 [B,S,S])."""
+    _dev(img_u8, mask, map_q5)
+    B, S = img_u8.shape[0], img_u8.shape[1]
+    if img_u8.dtype != torch.uint8 or mask.dtype != torch.int64 or map_q5.dtype != torch.int32 or img_u8.shape != (B, S, S, 3) \
+            or mask.shape != (B, S, S) or map_q5.shape != (B, S, S, 2) \
+            or not (img_u8.is_contiguous() and mask.is_contiguous() and map_q5.is_contiguous()):
+        raise ValueError("nonrigid_remap: img uint8 [B,S,S,3], mask int64 [B,S,S] and map int32 [B,S,S,2], contiguous")
+    out = torch.empty_like(img_u8)
+    mout = torch.empty_like(mask)
+    check(lib().asis_nonrigid_remap(_stream(), img_u8.data_ptr(), mask.data_ptr(), map_q5.data_ptr(), out.data_ptr(),
+                                    mout.data_ptr(), B, S), "asis_nonrigid_remap")
     return out, mout
 
 

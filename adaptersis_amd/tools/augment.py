@@ -8,7 +8,8 @@ What the reference composes (albumentations, version unpinned in `README.md:12`;
     OneOf([RandomSizedCrop(min_max_height=(294, 588), height=588, width=588, p=0.5),
            PadIfNeeded(588, 588, border_mode=BORDER_CONSTANT)], p=1)        -> crop with prob 0.5 / (0.5 + 1.0) = 1/3, else no-op
     HorizontalFlip(p=0.5); RandomRotate90(p=0.5)
-    OneOf([ElasticTransform, GridDistortion, OpticalDistortion], p=0)       -> never applied
+    OneOf([ElasticTransform, GridDistortion, OpticalDistortion], p=0)       -> never applied (``non_rigid_p``: the switch the
+                                                                               reference comments out, `#p=0.8 if ... else 0`)
     CLAHE(p=0.8); RandomBrightnessContrast(p=0.8); RandomGamma(p=0.8)
 
 Built here: crop + cv2.resize back to S x S (INTER_LINEAR, 8-bit fixed-point form; mask INTER_NEAREST), flip, rot90,
@@ -17,6 +18,14 @@ CLAHE (OpenCV's 8-bit RGB <-> Lab integer paths + tiled contrast-limited equalis
 albumentations applies them to uint8 images), float / 255.  A batch with CLAHE samples runs three kernels (the tile histograms
 need the whole geometrically transformed image), a batch without any runs the single fused one.
 The random draws come from this module's own ``numpy`` generator — the same distributions, not albumentations' stream.
+
+Non-rigid block (``non_rigid_p`` > 0; ``csrc/nonrigid.hip``): each member is a resample through a coordinate map, so a batch
+with such a sample runs geometric stage -> map (Q5 fixed point, 1/32 pixel) -> integer bilinear remap (reflect-101) -> the CLAHE
+kernels, whose per-sample flag switches CLAHE off while the tables and / 255 still apply.  Restated from albumentations 1.x
+(``elastic_transform``, ``grid_distortion``, ``optical_distortion``) and OpenCV 4.x (``remap``, ``initUndistortRectifyMap``)
+as published; neither library can be run here, so parity is unpinned as for CLAHE.  Stated deviations: the elastic member's
+``warpAffine`` + ``remap`` are composed into ONE resample (one interpolation instead of two); its noise is this project's Philox
+stream, not numpy's; the mask is sampled at the rounded QUANTISED coordinate (OpenCV rounds the float map).
 """
 from __future__ import annotations
 
@@ -72,12 +81,65 @@ def gamma_lut(gamma: float) -> np.ndarray:
     return (np.power(np.arange(0, 256, dtype=np.float64) / 255.0, gamma) * 255.0).astype(np.uint8)
 
 
+# ---- non-rigid block: host tables ------------------------------------------------------------------------------------
+NR_NONE, NR_ELASTIC, NR_GRID, NR_OPTICAL = 0, 1, 2, 3
+NR_RMAX = 64      # largest Gauss radius of asis_nonrigid_map
+
+
+def gauss_table(sigma: float) -> np.ndarray:
+    """scipy ``gaussian_filter`` kernel (``_gaussian_kernel1d``, truncate = 4): radius int(4 sigma + 0.5), weights
+    exp(-i^2 / 2 sigma^2) / sum, computed in float64 -> fp32 [2 r + 1]."""
+    r = int(4.0 * float(sigma) + 0.5)
+    if r > NR_RMAX:
+        raise ValueError(f"gauss_table: sigma {sigma} needs radius {r} > {NR_RMAX}")
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x * x)
+    return (w / w.sum()).astype(np.float32)
+
+
+def grid_table(S: int, num_steps: int, steps) -> np.ndarray:
+    """One axis of albumentations ``grid_distortion``: the source coordinate of every output index, float64 [S].  The loop as
+    published, quirks included: ``step = S // num_steps`` segments of ``np.linspace(prev, cur, end - start)`` (both ends, so a
+    join repeats a value); the last segment is pinned to ``S`` only when it overruns, so where ``step`` divides ``S`` the table
+    ends wherever the steps add up to, above or below ``S``."""
+    step = S // num_steps
+    xx = np.zeros(S, np.float64)
+    prev = 0.0
+    for idx in range(num_steps + 1):
+        start = idx * step
+        end = start + step
+        if end > S:
+            end, cur = S, float(S)
+        else:
+            cur = prev + step * float(steps[idx])
+        xx[start:end] = np.linspace(prev, cur, max(end - start, 0))
+        prev = cur
+    return xx
+
+
+def elastic_affine(S: int, pts) -> np.ndarray:
+    """albumentations ``elastic_transform``: M = cv2.getAffineTransform(pts1, pts1 + pts) around the centre square; returns
+    the INVERSE map A float64 [2, 3] (what ``warpAffine`` samples through), source = A (x, y, 1)."""
+    c, s = float(S // 2), float(S // 3)
+    pts1 = np.array([[c + s, c + s], [c + s, c - s], [c - s, c - s]], np.float64)
+    pts2 = pts1 + np.asarray(pts, np.float64)
+    P = np.concatenate([pts1, np.ones((3, 1))], 1)
+    M = np.eye(3)
+    M[:2] = np.linalg.solve(P, pts2).T
+    return np.linalg.inv(M)[:2]
+
+
 class TrainAugment:
     def __init__(self, size: int = 588, seed: int = 0, crop_p: float = 0.5, pad_p: float = 1.0, flip_p: float = 0.5,
                  rot_p: float = 0.5, clahe_p: float = 0.8, bc_p: float = 0.8, gamma_p: float = 0.8,
-                 min_crop: Optional[int] = None, clahe_clip=(1.0, 4.0)):
+                 min_crop: Optional[int] = None, clahe_clip=(1.0, 4.0), non_rigid_p: float = 0.0,
+                 elastic=(120.0, 6.0, 3.6), grid=(5, 0.3), optical=(2.0, 0.5)):
         if size < 16:
             raise ValueError("TrainAugment: size must be at least 16 (8 x 8 CLAHE tile grid)")
+        # A.ElasticTransform(alpha, sigma, alpha_affine), A.GridDistortion(num_steps, distort_limit),
+        # A.OpticalDistortion(distort_limit, shift_limit): `train.py:151-158`, members' p = 0.5, 0.5, 1
+        self.non_rigid_p, self.elastic, self.grid, self.optical = float(non_rigid_p), tuple(elastic), tuple(grid), tuple(optical)
+        self._gauss = gauss_table(self.elastic[1])
         self.size = size
         self.clahe_p, self.clahe_clip = clahe_p, clahe_clip        # A.CLAHE(clip_limit=4.0) -> clip ~ U(1, 4), tiles (8, 8)
         self.min_crop = int(size * 0.5) if min_crop is None else min_crop      # min_max_height=(int(588*0.5), 588)
@@ -87,11 +149,13 @@ class TrainAugment:
 
     # ---- parameter draws (host) -----------------------------------------------------------------------------------
     def draw(self, n: int):
-        """-> list of per-sample dicts (crop box or None, flip, rotk, alpha, beta, gamma)."""
+        """-> list of per-sample dicts (crop box or None, flip, rotk, nonrigid: None or the member's draws, clahe, alpha, beta,
+        gamma), drawn in the pipeline's order."""
         S, r = self.size, self.rng
         out = []
         for _ in range(n):
-            p: Dict = {"crop": None, "flip": False, "rotk": 0, "clahe": None, "alpha": 1.0, "beta": 0.0, "gamma": None}
+            p: Dict = {"crop": None, "flip": False, "rotk": 0, "nonrigid": None, "clahe": None, "alpha": 1.0, "beta": 0.0,
+                       "gamma": None}
             if r.random_sample() < self.p_crop:
                 ch = int(r.randint(self.min_crop, S + 1))          # random.randint(min, max), both inclusive
                 cw = ch                                            # w2h_ratio = 1.0
@@ -102,6 +166,8 @@ class TrainAugment:
             p["flip"] = bool(r.random_sample() < self.flip_p)
             if r.random_sample() < self.rot_p:
                 p["rotk"] = int(r.randint(0, 4))
+            if self.non_rigid_p > 0:                               # at 0 the stream of draws is the one without the block
+                p["nonrigid"] = self._draw_nonrigid()
             if r.random_sample() < self.clahe_p:
                 p["clahe"] = float(r.uniform(*self.clahe_clip))
             if r.random_sample() < self.bc_p:
@@ -111,6 +177,52 @@ class TrainAugment:
                 p["gamma"] = r.uniform(80, 120) / 100.0
             out.append(p)
         return out
+
+    def _draw_nonrigid(self):
+        """albumentations ``OneOf``: with probability ``non_rigid_p`` one member, by the members' normalised p (1/4, 1/4, 1/2)."""
+        r = self.rng
+        if not r.random_sample() < self.non_rigid_p:
+            return None
+        u = r.random_sample()
+        if u < 0.25:
+            seed = (int(r.randint(0, 1 << 32, dtype=np.uint64)) << 32) | int(r.randint(0, 1 << 32, dtype=np.uint64))
+            aa = self.elastic[2]
+            return {"kind": "elastic", "seed": seed, "pts": r.uniform(-aa, aa, size=(3, 2))}
+        if u < 0.5:
+            n, lim = int(self.grid[0]), self.grid[1]
+            return {"kind": "grid", "xsteps": 1.0 + r.uniform(-lim, lim, size=n + 1), "ysteps": 1.0 + r.uniform(-lim, lim, size=n + 1)}
+        d, sh = self.optical
+        k = float(r.uniform(-d, d))
+        # shift_limit = 0.5: Python's round() of U(-0.5, 0.5) is always 0, as in the reference; the draw is kept
+        return {"kind": "optical", "k": k, "dx": round(r.uniform(-sh, sh)), "dy": round(r.uniform(-sh, sh))}
+
+    def nonrigid_tables(self, params, device) -> Dict[str, torch.Tensor]:
+        """The tables of ``asis_nonrigid_map`` for the draws ``params`` (``p.get("nonrigid")`` absent or None = kind none)."""
+        S, B = self.size, len(params)
+        kind = np.zeros(B, np.int32)
+        par = np.zeros((B, 8), np.float32)
+        seed = np.zeros(B, np.uint64)
+        gx = np.zeros((B, S), np.float32); gy = np.zeros((B, S), np.float32)
+        for b, p in enumerate(params):
+            nr = p.get("nonrigid")
+            if nr is None:
+                continue
+            if nr["kind"] == "elastic":
+                kind[b] = NR_ELASTIC
+                par[b, 0] = self.elastic[0]
+                par[b, 1:7] = elastic_affine(S, nr["pts"]).reshape(-1)
+                seed[b] = np.uint64(int(nr["seed"]) & 0xFFFFFFFFFFFFFFFF)
+            elif nr["kind"] == "grid":
+                kind[b] = NR_GRID
+                gx[b] = grid_table(S, int(self.grid[0]), nr["xsteps"])
+                gy[b] = grid_table(S, int(self.grid[0]), nr["ysteps"])
+            elif nr["kind"] == "optical":
+                kind[b] = NR_OPTICAL
+                par[b, :3] = (nr["k"], nr["dx"], nr["dy"])
+            else:
+                raise ValueError(f"TrainAugment: unknown non-rigid kind {nr['kind']!r}")
+        t = dict(nr_kind=kind, nr_par=par, nr_seed=seed.view(np.int64), nr_gx=gx, nr_gy=gy, nr_gauss=self._gauss)
+        return {k: torch.from_numpy(v).to(device, non_blocking=True) for k, v in t.items()}
 
     def tables(self, params, device) -> Dict[str, torch.Tensor]:
         S = self.size
@@ -138,6 +250,9 @@ class TrainAugment:
         t = dict(geo=geo, xofs=xofs, yofs=yofs, xa=xa, ya=ya, mx=mx, my=my, lut=lut, clahe=clahe)
         out = {k: torch.from_numpy(v).to(device, non_blocking=True) for k, v in t.items()}
         out["clahe_any"] = bool(clahe[:, 0].any())      # host flag: no CLAHE sample -> the single fused kernel
+        out["nonrigid_any"] = any(p.get("nonrigid") is not None for p in params)   # host flag: none -> today's launches
+        if out["nonrigid_any"]:
+            out.update(self.nonrigid_tables(params, device))
         return out
 
     def __call__(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, params=None):

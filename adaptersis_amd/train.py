@@ -60,7 +60,7 @@ _AUGMENTERS = {}
 _IDENTITY = {"crop": None, "flip": False, "rotk": 0, "alpha": 1.0, "beta": 0.0, "gamma": None}
 
 
-def _to_device_batch(inp, target, train: bool):
+def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0):
     """Batch from the loader -> (float [B,3,S,S] in [0,1], long [B,S,S]) on the device.  uint8 HWC batches (``tools.dataset.Robomis``
     without a host transform) go through the GPU augmentation pipeline (`train.py:139-163`) when training, and through the same
     kernel with identity parameters (= `/255`, `tools/dataset.py:159`; the reference's val transform is a no-op Resize to the
@@ -75,8 +75,8 @@ def _to_device_batch(inp, target, train: bool):
     from .tools.augment import TrainAugment
     S = inp.shape[1]
     aug = _AUGMENTERS.get(S)
-    if aug is None:
-        aug = _AUGMENTERS[S] = TrainAugment(size=S, seed=1000 + utils.get_rank())
+    if aug is None or (train and aug.non_rigid_p != non_rigid_p):     # --aug_non_rigid: training batches only
+        aug = _AUGMENTERS[S] = TrainAugment(size=S, seed=1000 + utils.get_rank(), non_rigid_p=non_rigid_p if train else 0.0)
     return aug(inp.contiguous(), target.to(torch.uint8).contiguous(), None if train else [dict(_IDENTITY) for _ in range(inp.shape[0])])
 
 
@@ -204,6 +204,9 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     validate = validate or validate_network
     if loss is None:
         loss = getattr(args, "loss", "dice")
+    non_rigid_p = float(getattr(args, "aug_non_rigid", 0.0))
+    if not 0.0 <= non_rigid_p <= 1.0:
+        raise ValueError("--aug_non_rigid must be a probability in [0, 1]")
     utils.init_distributed_mode(args)
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda", args.gpu)
@@ -225,6 +228,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                              train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss,
                              **_optimizer_args(args), **_loss_args(args))
     optimizer = engine.optimizer
+    engine.aug_non_rigid = non_rigid_p      # read by train(): its signature is the reference's and carries no arguments
 
     dataset_train, dataset_val, collate = open_datasets(args)
     workers = args.num_workers if collate is not None else 0      # PNG decode runs in loader workers; tensors in memory do not need any
@@ -323,7 +327,7 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
     for (inp, target, idx) in metric_logger.log_every(loader, 20, "Epoch: [{}]".format(epoch)):
         if ragged:
             parallel.set_batch_ratio(int(inp.shape[0]))
-        loss = engine.train_step(*_to_device_batch(inp, target, train=True))
+        loss = engine.train_step(*_to_device_batch(inp, target, train=True, non_rigid_p=getattr(engine, "aug_non_rigid", 0.0)))
         torch.cuda.synchronize()  # the reference syncs and reads the loss every step (train.py:439-440)
         metric_logger.update(loss=loss.item())
         metric_logger.update(lr=optimizer.param_groups[0]["lr"])
@@ -431,6 +435,10 @@ def get_args_parser():
                         "focal = segloss/focal_loss.py FocalLoss on softmax(out)")
     p.add_argument("--topk_percent", default=10.0, type=float, help="--loss topk / dc_and_topk: the k of TopKLoss, in percent")
     p.add_argument("--focal_gamma", default=2.0, type=float, help="--loss focal: the gamma of FocalLoss")
+    # extension: the switch the reference comments out (`train.py:158-159`, `#p=0.8 if self.use_vis_aug_non_rigid else 0`)
+    p.add_argument("--aug_non_rigid", default=0.0, type=float,
+                   help="probability of the non-rigid block OneOf([ElasticTransform, GridDistortion, OpticalDistortion]) of the "
+                        "GPU augmentation (uint8 datasets, training batches only); 0 = the reference as it stands")
     return p
 
 

@@ -797,6 +797,25 @@ int asis_augment_geo_u8(void* stream, const uint8_t* img, const uint8_t* mask, c
 int asis_clahe(void* stream, const uint8_t* rgb, const int32_t* clahe, const uint16_t* tab_gamma, const uint16_t* tab_cbrt,
                const uint16_t* tab_l2yf, const int32_t* tab_ab2xz, const uint8_t* tab_invgamma, const int32_t* coef_fwd,
                const int32_t* coef_inv, uint8_t* luts, const uint8_t* lut, float* out, int B, int S, int tiles);
+/* Non-rigid stage of the same pipeline (train.py:155-159: OneOf([ElasticTransform(alpha=120, sigma=6, alpha_affine=3.6),
+ * GridDistortion, OpticalDistortion(distort_limit=2, shift_limit=0.5)])); csrc/nonrigid.hip, tables from
+ * adaptersis_amd/tools/augment.py.  It runs between asis_augment_geo_u8 and asis_clahe, as one resample through a map.
+ *   asis_nonrigid_map: map int32 [B,S,S,2] = (x, y) source coordinate of every output pixel in 1/32 pixel (Q5, round half to
+ *     even: OpenCV's INTER_BITS).  kind int32 [B]: 0 none (map = 32 (x, y)), 1 elastic, 2 grid, 3 optical.
+ *     params fp32 [B,8]: elastic (alpha, A00, A01, A02, A10, A11, A12, 0) with A the inverse of the random affine;
+ *     optical (k, dx, dy, 0...).  seed int64 [B]: Philox key of the elastic noise, n(f, y, x) = 2 U - 1 from word e & 3 of
+ *     philox4x32_10(counter (e >> 2, f, 0), key seed), e = y S + x.  gx, gy fp32 [B,S]: the grid-distortion tables.
+ *     gauss fp32 [2 r + 1], 0 <= r <= 64: the normalised Gaussian, applied separably with half-sample reflection (period 2 S).
+ *     tmp fp32 [B,2,S,S]: workspace of the row pass.  field (optional) fp32 [B,2,S,S]: alpha * blurred noise, written for
+ *     elastic samples only.  Two launches; workgroups of the row pass whose sample is not elastic return at once.
+ *   asis_nonrigid_remap: img uint8 [B,S,S,3], mask int64 [B,S,S] (what asis_augment_geo_u8 writes) -> the same types through
+ *     the map.  With ix = qx >> 5, fx = qx & 31: out = ((32-fx)(32-fy) p00 + fx (32-fy) p01 + (32-fx) fy p10 + fx fy p11 + 512)
+ *     >> 10, every tap reflected by reflect-101 (period 2 (S - 1)); mask: nearest at ((qx + 16) >> 5, (qy + 16) >> 5).
+ *     The outputs must not alias the inputs. */
+int asis_nonrigid_map(void* stream, const int32_t* kind, const float* params, const int64_t* seed, const float* gx, const float* gy,
+                      const float* gauss, int r, float* tmp, int32_t* map, float* field, int B, int S);
+int asis_nonrigid_remap(void* stream, const uint8_t* img, const int64_t* mask, const int32_t* map, uint8_t* out, int64_t* mask_out,
+                        int B, int S);
 
 /* Frame resize of the datasets' host path (tools/dataset.py:51-53: PIL resize((S, S), BILINEAR) for the frame, NEAREST for the
  * mask), bit-identical to Pillow's 8-bit resample; csrc/frame_resize.hip, tables from adaptersis_amd/tools/frame_resize.py.
