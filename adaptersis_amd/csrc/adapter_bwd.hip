@@ -430,9 +430,12 @@ __global__ __launch_bounds__(256) void msda_vgrad_kernel(const int* __restrict__
   const int e0 = o[pix], e1 = o[pix + 1];
   const int2* r = rec + (int64_t)bm * cap;
   const int D = M * Dh;
-  // fixed-point grid: |w| <= 1 and |d out| <= amax < 2^(e + 1), so |w d| 2^(29 - e) < 2^30
+  // fixed-point grid: |w| <= 1 and |d out| <= amax < 2^(e + 1), so |w d| 2^(29 - e) < 2^30.  Both scale factors are built as
+  // exponent fields and must be normal floats: 2^(29 - e) for every e <= 127, 2^(e - 29) only for e >= -97.  Below that the grid
+  // stays at 2^-126 and products under it round to zero (e = -98 made isc 0.0, e = -99 made sc +inf and isc -inf).  No upper
+  // clamp: a grid held at e = 90 saturated the int conversion from amax = 2^92 on.
   int e = (int)((__builtin_bit_cast(uint32_t, *amax) >> 23) & 0xFF) - 127;
-  e = e < -100 ? -100 : (e > 90 ? 90 : e);
+  e = e < -97 ? -97 : e;
   const float sc = __builtin_bit_cast(float, (uint32_t)(127 + 29 - e) << 23), isc = __builtin_bit_cast(float, (uint32_t)(127 - 29 + e) << 23);
   for (int d0 = 2 * lane; d0 < Dh; d0 += 128) {     // Dh <= 128: one trip; wider heads: lanes loop
     long long a0 = 0, a1 = 0;

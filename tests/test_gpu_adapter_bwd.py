@@ -87,13 +87,35 @@ def test_msda_value_grad_sorted_at_the_adapter_geometry(dev):
             old = ops.MSDA_SORTED
             ops.MSDA_SORTED = form != "matrix"
             try:
-                outs[form], _ = ops.msda_bwd(value, offaw, ref, sh, st, dout, B, Lq, M, L, P)
+                outs[form], doffaw = ops.msda_bwd(value, offaw, ref, sh, st, dout, B, Lq, M, L, P)
             finally:
                 ops.MSDA_SORTED = old
         assert torch.equal(outs["sorted"], outs["sorted2"])
         e = rel_l2(outs["sorted"], outs["matrix"])
         print(f"MSDA d value, Lq {Lq}: sorted vs dense matrix rel-L2 {e:.2e}")
         assert e < 1e-3
+        _check_doffaw_sample(value, offaw, ref, shapes, dout, doffaw, B, Lq, M, Dh, L, P)
+
+
+def _check_doffaw_sample(value, offaw, ref, shapes, dout, doffaw, B, Lq, M, Dh, L, P, per_image=32):
+    """d offsets / d logits at this geometry (D = 1024, M = 8: the xor-shuffle reduction of msda_bwd_kernel) against the float64
+    restatement, element by element with the bounds of tests/test_gpu_msda_routes.py, on 64 rows: the first 32 queries of each
+    image all of whose sampling coordinates lie 2^-8 px or more from a cell boundary (about one query in five), where the kernel's
+    fp32 position and the reference choose the same cell."""
+    from tests import msda_ref as R
+    n = M * L * P * 2
+    oc, rc = offaw.cpu(), ref.cpu()
+    px, py = R._positions(rc, oc[:, :n].reshape(B, Lq, M, L, P, 2), shapes, torch.float64)
+    p = torch.stack([px, py])
+    clear = ((p - p.round()).abs() >= 2.0 ** -8).flatten(3).all(-1).all(0)          # [B, Lq]
+    qsel = [torch.nonzero(clear[b]).flatten()[:per_image] for b in range(B)]
+    assert all(len(q) == per_image for q in qsel)
+    for b in range(B):       # one image at a time, its sampled queries as a problem of their own (rows are independent)
+        rows = b * Lq + qsel[b]
+        r = R.msda_reference(value[b:b + 1].cpu(), oc[rows], rc[qsel[b]], shapes, M, P, dout=dout.cpu()[rows])
+        got = doffaw.cpu()[rows]
+        R.assert_within(f"Lq {Lq} image {b} d off", got[:, :n], r["ref"]["doff"], R.tol_doff(r, Dh), "sampled row, (m,l,p,xy)")
+        R.assert_within(f"Lq {Lq} image {b} d logit", got[:, n:], r["ref"]["dlogit"], R.tol_dlogit(r, Dh, L * P), "sampled row, (m,l,p)")
 
 
 def test_dwconv_gelu_backward(dev):
