@@ -118,6 +118,10 @@ SIGNATURES = {
     "asis_gelu16": [_vp, _i, _vp, _vp, _vp, _i64],
     "asis_gelu_split": [_vp, _i, _vp, _vp, _vp, _i64],
     "asis_cast_colsum": [_vp, _i, _vp, _i64, _vp, _i64, _f, _vp, _i64, _i],
+    "asis_layernorm_gather": [_vp, _i, _vp, _i64, _vp, _vp, _f, _vp, _i64, _vp, _i, _i, _i64, _i],
+    "asis_scaled_index_add": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i],
+    "asis_gather_cast_colsum": [_vp, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i64, _i],
+    "asis_layernorm_bwd_scatter": [_vp, _vp, _i64, _vp, _i64, _vp, _f, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i64, _i64, _i],
     "asis_swiglu_bwd": [_vp, _i, _vp, _vp, _vp, _i64, _i],
     "asis_colsum": [_vp, _i, _vp, _i64, _vp, _i64, _i],
     "asis_ls_linear_finish": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i],

@@ -26,6 +26,7 @@ from torch import nn
 
 from .. import config, ops
 from ..dinov2.layers.blocks import _Packed, _pack, run_blocks
+from ..droppath import DropPathSampler
 from ..optim import SGD, AdamW, FlatBucket
 from ..parallel import StageReducer, world_size
 from .adapter_blocks import CACNN, CAViT, deform_inputs
@@ -139,7 +140,8 @@ class SegEngine(nn.Module):
                  train_encoder: bool = False, train_backbone: bool = False, optimize_backbone: bool = False,
                  blocks_per_bucket: int = 4, grad_compress: Optional[str] = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
-                 layer_decay: Optional[float] = None, topk_percent: float = 10.0, focal_gamma: float = 2.0):
+                 layer_decay: Optional[float] = None, topk_percent: float = 10.0, focal_gamma: float = 2.0,
+                 drop_path_seed: int = 0):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -162,7 +164,10 @@ class SegEngine(nn.Module):
         ``optimize_backbone``).  ``clip_grad`` with "sgd" raises: the SGD kernels do not clip.
 
         ``topk_percent``: the ``k`` of ``TopKLoss`` for the losses "topk" / "dc_and_topk" (the worst k % of the batch's pixels);
-        ``focal_gamma``: the ``gamma`` of ``FocalLoss`` for "focal"."""
+        ``focal_gamma``: the ``gamma`` of ``FocalLoss`` for "focal".
+
+        ``drop_path_seed``: seed of the stochastic-depth draws of a model built with ``drop_path_rate`` > 0 (droppath.py); they
+        act in the training forward of ``train_backbone`` only, and every rank draws its own."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -257,6 +262,9 @@ class SegEngine(nn.Module):
                 buckets.append(self.vit_bucket)
         if layer_decay is not None and not (train_backbone and optimize_backbone):
             raise ValueError("layer_decay scales the learning rates of the ViT blocks: it needs train_backbone and optimize_backbone")
+        self.drop_path = make_drop_path_sampler(model, drop_path_seed, process_group)
+        if self.drop_path is not None and not train_backbone:
+            raise ValueError("drop_path_rate drops samples in the training forward of the ViT blocks: it needs train_backbone")
         self.optimizer = make_optimizer(optimizer, buckets, lr=lr, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps,
                                         clip_grad=clip_grad, no_decay=no_decay, depth=len(model.blocks),
                                         layer_decay=[layer_decay if b is self.vit_bucket else None for b in buckets])
@@ -644,8 +652,12 @@ class SegEngine(nn.Module):
         segs = [(B, N + 1), (B, N)]
         xcat = torch.cat([xa.view(Ra, D), tokens.reshape(Rb, D)], 0)
         bsaves, feats, fin, asaves = [], [], [], []
+        # stochastic depth: this step's draws for every block, their index tables in one host-to-device copy (droppath.py)
+        keeps = self.drop_path.step(segs, inp.device) if self.drop_path is not None else [None] * nb
+        blk_train = lambda j, xin: m.blocks[j].forward_train_rows(xin, segs) if keeps[j] is None else \
+            m.blocks[j].forward_train_rows(xin, segs, keep=keeps[j])
         for i, blk in enumerate(m.blocks[: nb - (nl - 1)]):
-            xcat, sv = blk.forward_train_rows(xcat, segs)
+            xcat, sv = blk_train(i, xcat)
             bsaves.append(sv)
             if i >= nb - nl:
                 feats.append(m._final_norm(xcat[:Ra].view(B, N + 1, D))[:, 1:])
@@ -655,7 +667,7 @@ class SegEngine(nn.Module):
         c2d = c.view(B * Lc, D)
         for s in range(nl):
             if s > 0:
-                xcat, sv = m.blocks[nb - nl + s].forward_train_rows(xcat, segs)
+                xcat, sv = blk_train(nb - nl + s, xcat)
                 bsaves.append(sv)
                 feats.append(m._final_norm(xcat[:Ra].view(B, N + 1, D))[:, 1:])
                 fin.append(xcat)
@@ -953,6 +965,16 @@ def make_optimizer(kind: str, buckets, *, lr, momentum, weight_decay, betas=(0.9
     raise ValueError("optimizer must be 'sgd' or 'adamw'")
 
 
+def make_drop_path_sampler(model, seed: int, process_group=None):
+    """the ``DropPathSampler`` of an engine that trains ``model``'s blocks, seeded with this process's rank; None when every
+    block's ``sample_drop_ratio`` is 0 (nothing changes on that path)"""
+    rates = [float(getattr(blk, "sample_drop_ratio", 0.0)) for blk in model.blocks]
+    if not any(rates):
+        return None
+    rank = dist.get_rank(process_group) if (dist.is_available() and dist.is_initialized()) else 0
+    return DropPathSampler(rates, seed=seed, rank=rank)
+
+
 def make_vit_bucket(model, blocks_per_bucket: int, process_group, momentum: bool = False, min_first_blocks: int = 0,
                     compress: Optional[str] = None):
     """Flat gradient bucket of the whole backbone in gradient-ready order (final norm, blocks last..first, then the token
@@ -995,8 +1017,10 @@ class EndToEndEngine(nn.Module):
 
     def __init__(self, model, seg_decoder, *, lr: float = 0.01, momentum: float = 0.9, weight_decay: float = 0.0,
                  loss: str = "ce_dc", process_group=None, blocks_per_bucket: int = 4, optimizer: str = "sgd",
-                 betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True):
+                 betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
+                 drop_path_seed: int = 0):
         super().__init__()
+        self.drop_path = make_drop_path_sampler(model, drop_path_seed, process_group)   # stochastic depth of ``train_step``
         if loss not in SegEngine.LOSSES:
             raise ValueError(f"loss must be one of {sorted(SegEngine.LOSSES)}")
         self.model, self.seg_decoder, self.loss_kind, self.process_group = model, seg_decoder, loss, process_group
@@ -1028,7 +1052,10 @@ class EndToEndEngine(nn.Module):
         B, _, H, W = inp.shape
         h, w = H // self.patch, W // self.patch
         N, D = h * w, m.embed_dim
-        tok, vsaved = m.forward_train(inp)
+        if self.drop_path is not None:
+            tok, vsaved = m.forward_train(inp, keep=self.drop_path.step([(B, N + 1)], inp.device))
+        else:
+            tok, vsaved = m.forward_train(inp)
         t2 = torch.empty((B * N, D), device=inp.device, dtype=torch.float32)
         ops.copy_channels(vsaved_tokens_view(tok, B, N, D), t2.view(B, N * D))
         hi = ops.cast_pad(t2, D, dt).view(B, h, w, D)

@@ -1,10 +1,9 @@
 // HBM-bound row kernels: LayerNorm, cls/pos-embed add, fp32->16-bit packing, patch im2col.
 // One wave64 per row, 16-byte accesses, fp32 statistics (cdna_hip_programming.md G13).
 #include "asis_common.h"
+#include "row_routines.h"   // LN_MAXC, ln_row
 
 namespace {
-
-constexpr int LN_MAXC = 8;  // float4 chunks per lane -> D <= 2048
 
 template <typename T, bool OUT_F32>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx,
@@ -14,50 +13,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const int nchunk = D >> 2;
-  const float4* xr = reinterpret_cast<const float4*>(x + row * ldx);
-  float4 v[LN_MAXC];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nchunk) {
-      v[i] = xr[c];
-      s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nchunk) {
-      const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-      q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
-  const float4* w4 = reinterpret_cast<const float4*>(w);
-  const float4* b4 = reinterpret_cast<const float4*>(b);
-#pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nchunk) {
-      const float4 ww = w4[c], bb = b4[c];
-      const float o0 = (v[i].x - mean) * rstd * ww.x + bb.x;
-      const float o1 = (v[i].y - mean) * rstd * ww.y + bb.y;
-      const float o2 = (v[i].z - mean) * rstd * ww.z + bb.z;
-      const float o3 = (v[i].w - mean) * rstd * ww.w + bb.w;
-      if (OUT_F32) {
-        reinterpret_cast<float4*>(reinterpret_cast<float*>(y) + row * ldy)[c] = make_float4(o0, o1, o2, o3);
-      } else {
-        uint2 p;
-        p.x = pack2<T>(o0, o1);
-        p.y = pack2<T>(o2, o3);
-        reinterpret_cast<uint2*>(reinterpret_cast<T*>(y) + row * ldy)[c] = p;
-      }
-    }
-  }
+  if (OUT_F32) ln_row<T, true>(x + row * ldx, w, b, eps, reinterpret_cast<float*>(y) + row * ldy, D, lane);
+  else ln_row<T, false>(x + row * ldx, w, b, eps, reinterpret_cast<T*>(y) + row * ldy, D, lane);
 }
 
 // D == 256 * NCH exactly: no predicates, RPW rows per wave so that RPW * NCH 16-byte loads per lane are in flight

@@ -6,14 +6,13 @@
 //                                 cs = colsum(dout):  dW = gamma G,  db = gamma cs,  dgamma = rowsum(W * G) + b cs
 // One wave64 per row for the row kernels, 16-byte accesses, fp32 arithmetic.
 #include "asis_common.h"
+#include "row_routines.h"   // LN_MAXC, ln_bwd_block, cast_colsum_block
 
 namespace {
 
-constexpr int LN_MAXC = 8;  // float4 chunks per lane -> D <= 2048
-
 // dx[row] = (res ? res[row] : 0) + rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * w
 // partial[blk][0][c] = sum_rows dy * xhat (d weight),  partial[blk][1][c] = sum_rows dy (d bias)
-// Each block owns ROWS_PER_BLOCK consecutive rows, 4 waves striding over them; statistics are recomputed from x.
+// Each block owns ROWS_PER_BLOCK consecutive rows, 4 waves striding over them; statistics are recomputed from x (row_routines.h).
 template <int MAXC>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, int64_t lddy,
                                                             const float* __restrict__ x, int64_t ldx,
@@ -22,135 +21,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             float* __restrict__ dx, int64_t lddx,
                                                             float* __restrict__ partial, int64_t rows, int D,
                                                             int rows_per_block) {
-  __shared__ float red[3][2][MAXC * 64 * 4];  // waves 1..3 park their column sums here
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int nchunk = D >> 2;
-  const float4* w4 = reinterpret_cast<const float4*>(w);
-  float4 gw[MAXC], gb[MAXC], ww[MAXC];
-#pragma unroll
-  for (int i = 0; i < MAXC; ++i) {
-    gw[i] = gb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int c = lane + 64 * i;
-    ww[i] = c < nchunk ? w4[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > rows) r1 = rows;
-  const float invD = 1.0f / (float)D;
-  // the next row's loads (x, dy, residual) are issued before this row's three wave reductions: two rows in flight per wave
-  constexpr bool PF = MAXC <= 6;   // 6 x MAXC float4 of row data + 3 x MAXC of sums / weight must fit 256 VGPRs
-  float4 v[MAXC], g[MAXC], e[MAXC];
-  auto load_row = [&](int64_t row, float4* vv, float4* gg, float4* ee) {
-    const float4* xr = reinterpret_cast<const float4*>(x + row * ldx);
-    const float4* gr = reinterpret_cast<const float4*>(dy + row * lddy);
-    const float4* rr = res ? reinterpret_cast<const float4*>(res + row * ldr) : nullptr;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        vv[i] = xr[c];
-        gg[i] = gr[c];
-        if (rr) ee[i] = rr[c];
-      }
-    }
-  };
-  int64_t row = r0 + wid;
-  if constexpr (PF) {
-    if (row < r1) load_row(row, v, g, e);
-  }
-  for (; row < r1; row += 4) {
-    float4 vn[PF ? MAXC : 1], gn[PF ? MAXC : 1], en[PF ? MAXC : 1];
-    if constexpr (PF) {
-      if (row + 4 < r1) load_row(row + 4, vn, gn, en);
-    } else {
-      load_row(row, v, g, e);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) * invD;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
-        q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
-      }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * invD + eps);
-    float a = 0.f, bq = 0.f;  // sum g, sum g*xhat
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        v[i].x *= rstd; v[i].y *= rstd; v[i].z *= rstd; v[i].w *= rstd;  // xhat
-        gw[i].x += g[i].x * v[i].x; gw[i].y += g[i].y * v[i].y; gw[i].z += g[i].z * v[i].z; gw[i].w += g[i].w * v[i].w;
-        gb[i].x += g[i].x; gb[i].y += g[i].y; gb[i].z += g[i].z; gb[i].w += g[i].w;
-        g[i].x *= ww[i].x; g[i].y *= ww[i].y; g[i].z *= ww[i].z; g[i].w *= ww[i].w;
-        a += (g[i].x + g[i].y) + (g[i].z + g[i].w);
-        bq += (g[i].x * v[i].x + g[i].y * v[i].y) + (g[i].z * v[i].z + g[i].w * v[i].w);
-      }
-    }
-    a = wave_sum(a) * invD;
-    bq = wave_sum(bq) * invD;
-    float4* o = reinterpret_cast<float4*>(dx + row * lddx);
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        float4 t;
-        t.x = rstd * (g[i].x - a - v[i].x * bq);
-        t.y = rstd * (g[i].y - a - v[i].y * bq);
-        t.z = rstd * (g[i].z - a - v[i].z * bq);
-        t.w = rstd * (g[i].w - a - v[i].w * bq);
-        if (res) {
-          t.x += e[i].x; t.y += e[i].y; t.z += e[i].z; t.w += e[i].w;
-        }
-        o[c] = t;
-      }
-    }
-    if constexpr (PF) {
-#pragma unroll
-      for (int i = 0; i < MAXC; ++i) {
-        v[i] = vn[i];
-        g[i] = gn[i];
-        e[i] = en[i];
-      }
-    }
-  }
-  // column sums over the block's rows: waves 1..3 -> LDS -> wave 0 adds and writes
-  if (wid > 0) {
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      reinterpret_cast<float4*>(red[wid - 1][0])[i * 64 + lane] = gw[i];
-      reinterpret_cast<float4*>(red[wid - 1][1])[i * 64 + lane] = gb[i];
-    }
-  }
-  __syncthreads();
-  if (wid == 0) {
-    float4* pw = reinterpret_cast<float4*>(partial + ((int64_t)blockIdx.x * 2 + 0) * D);
-    float4* pb = reinterpret_cast<float4*>(partial + ((int64_t)blockIdx.x * 2 + 1) * D);
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        float4 sw = gw[i], sb = gb[i];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const float4 t = reinterpret_cast<const float4*>(red[k][0])[i * 64 + lane];
-          const float4 u = reinterpret_cast<const float4*>(red[k][1])[i * 64 + lane];
-          sw.x += t.x; sw.y += t.y; sw.z += t.z; sw.w += t.w;
-          sb.x += u.x; sb.y += u.y; sb.z += u.z; sb.w += u.w;
-        }
-        pw[c] = sw;
-        pb[c] = sb;
-      }
-    }
-  }
+  ln_bwd_block<MAXC>(dy, lddy, x, ldx, w, eps, res, ldr, dx, lddx, partial, rows, D, rows_per_block, RowIdentity());
 }
 
 // exact (libm erff) derivative is used in the backward: one pass, not in a GEMM epilogue
@@ -260,52 +131,7 @@ template <typename T, int MAXC>
 __global__ __launch_bounds__(256) void cast_colsum_kernel(const float* __restrict__ x, int64_t ldx, T* __restrict__ out,
                                                           int64_t ldo, float scale, float* __restrict__ partial,
                                                           int64_t rows, int D, int rows_per_block) {
-  __shared__ float red[3][MAXC * 64 * 4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int nchunk = D >> 2;
-  float4 acc[MAXC];
-#pragma unroll
-  for (int i = 0; i < MAXC; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > rows) r1 = rows;
-  for (int64_t row = r0 + wid; row < r1; row += 4) {
-    const float4* xr = reinterpret_cast<const float4*>(x + row * ldx);
-    uint2* o = reinterpret_cast<uint2*>(out + row * ldo);
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        const float4 v = xr[c];
-        acc[i].x += v.x; acc[i].y += v.y; acc[i].z += v.z; acc[i].w += v.w;
-        uint2 p;
-        p.x = pack2<T>(v.x * scale, v.y * scale);
-        p.y = pack2<T>(v.z * scale, v.w * scale);
-        o[c] = p;
-      }
-    }
-  }
-  if (wid > 0) {
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) reinterpret_cast<float4*>(red[wid - 1])[i * 64 + lane] = acc[i];
-  }
-  __syncthreads();
-  if (wid == 0) {
-    float4* pw = reinterpret_cast<float4*>(partial + (int64_t)blockIdx.x * D);
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nchunk) {
-        float4 s = acc[i];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const float4 t = reinterpret_cast<const float4*>(red[k])[i * 64 + lane];
-          s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
-        }
-        pw[c] = s;
-      }
-    }
-  }
+  cast_colsum_block<T, MAXC, false>(x, ldx, out, ldo, scale, partial, rows, D, rows_per_block, RowIdentity());
 }
 
 // one wave per output feature n: dW[n,:] = gs * gamma[n] * G[n,:];  dgamma[n] = gs * (sum_k W[n,k] G[n,k] + b[n] cs[n]);

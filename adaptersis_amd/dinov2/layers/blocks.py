@@ -21,7 +21,7 @@ from typing import Callable, Optional, Tuple, Union
 import torch
 from torch import nn
 
-from ... import config, ops
+from ... import config, droppath, ops
 
 
 _VT_STREAMS = {}
@@ -439,14 +439,17 @@ class SwiGLUFFNFused(SwiGLUFFN):
 
 
 class Block(_Packed):
-    """`dinov2/layers/block.py:38-114`, eval branch (`:111-113`); drop_path is 0 on this path."""
+    """`dinov2/layers/block.py:38-114`.  ``drop_path`` is kept on ``sample_drop_ratio`` and never drawn here: stochastic depth acts
+    only where a caller hands ``keep=`` to ``forward_train_rows`` (the training forward of an unfrozen backbone: droppath.py)."""
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, proj_bias=True, ffn_bias=True, drop=0.0,
                  attn_drop=0.0, init_values=None, drop_path=0.0, act_layer=nn.GELU, norm_layer=nn.LayerNorm,
                  attn_class=Attention, ffn_layer=Mlp):
         super().__init__()
-        if drop_path or drop:
-            raise ValueError("stochastic depth / dropout are 0 on the AdapterSIS path")
+        if drop:
+            raise ValueError("dropout is 0 on the AdapterSIS path")
+        if not 0.0 <= float(drop_path) < 1.0:
+            raise ValueError(f"drop_path must be in [0, 1): got {drop_path}")
         self.norm1 = norm_layer(dim)
         self.attn = attn_class(dim, num_heads=num_heads, qkv_bias=qkv_bias, proj_bias=proj_bias)
         self.ls1 = LayerScale(dim, init_values=init_values) if init_values else nn.Identity()
@@ -681,36 +684,30 @@ class Block(_Packed):
         return x3
 
     # ---- training path (block.py:89-114 under autograd; BASELINE config 4 / north_star "forward/backward") ----------
-    def forward_train(self, x: torch.Tensor):
+    def forward_train(self, x: torch.Tensor, keep=None):
         """x fp32 (B, N, D) -> (out fp32 (B, N, D), saved activations for ``backward``).  Same arithmetic as
         ``forward`` except that fc1 keeps its 16-bit pre-activation (GELU runs as its own pass) and q, k, v come from
-        one [3D] GEMM (V^T by a token transpose)."""
+        one [3D] GEMM (V^T by a token transpose).  ``keep``: see ``forward_train_rows``."""
         B, N, D = x.shape
         x2 = x.reshape(B * N, D)
         if x2.dtype != torch.float32 or not x2.is_contiguous():
             x2 = x2.float().contiguous()
-        out, saved = self.forward_train_rows(x2, [(B, N)])
+        out, saved = self.forward_train_rows(x2, [(B, N)]) if keep is None else self.forward_train_rows(x2, [(B, N)], keep=keep)
         return out.view(B, N, D), saved
 
-    def forward_train_rows(self, x2: torch.Tensor, segs):
-        """``forward_train`` on several token batches stacked along the rows of one fp32 [R, D] matrix (``segs`` =
-        [(B, N), ...], see ``forward_rows``): every GEMM / LayerNorm / GELU launch — and in the backward every weight-gradient
-        GEMM — covers all rows, so the parameter gradients of the two ViT passes of the unfrozen adapter step (BASELINE
-        config 4) are summed by construction; only the attention runs per batch."""
+    def _attn_train(self, xn: torch.Tensor, segs):
+        """qkv GEMM + attention of the training forward on the rows of ``xn`` (16-bit [R, D], ``segs`` cover them)
+        -> (qkv, o, o_lo | None, lse)"""
         dt = config.operand_dtype
-        D = x2.shape[1]
-        m = self.mlp
-        g1 = self._f32("g1", self.ls1.gamma) if isinstance(self.ls1, LayerScale) else None
-        g2 = self._f32("g2", self.ls2.gamma) if isinstance(self.ls2, LayerScale) else None
+        D = xn.shape[1]
         a = self.attn
-        xn = ops.layernorm(x2, self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias), self.norm1.eps, dt)
         qkv = ops.gemm(xn, a._w16("qkv", a.qkv.weight), bias_n=a._f32("qkv_b", a.qkv.bias), b_lo=a._w16lo("qkv", a.qkv.weight))
-        o = torch.empty((x2.shape[0], D), device=x2.device, dtype=dt)
+        o = torch.empty((xn.shape[0], D), device=xn.device, dtype=dt)
         o_lo = torch.empty_like(o) if config.split_attn_out else None
-        if sum(B * N for B, N in segs) != x2.shape[0]:
+        if sum(B * N for B, N in segs) != xn.shape[0]:
             raise ValueError("forward_train_rows: segments do not cover the rows")
         # the log-sum-exp of every stacked batch in ONE buffer ([B1, H, N1] then [B2, H, N2]: what attention_bwd_rows reads)
-        lse = torch.empty(x2.shape[0] * a.num_heads, device=x2.device, dtype=torch.float32)
+        lse = torch.empty(xn.shape[0] * a.num_heads, device=xn.device, dtype=torch.float32)
         if len(segs) <= 2 and config.attn_rows:
             # V row-major straight out of the qkv GEMM (transposing LDS reads in the kernel), both batches in one launch
             ops.attention_fwd_qkv(qkv, segs, a.num_heads, a.scale, o, out_lo=o_lo, lse=lse)
@@ -722,26 +719,71 @@ class Block(_Packed):
                 ops.attention_fwd(qkv[r0:r1, :D], qkv[r0:r1, D:2 * D], vt, B, a.num_heads, N, a.scale, out=o[r0:r1],
                                   lse=lse[l0:l1].view(B, a.num_heads, N), out_lo=None if o_lo is None else o_lo[r0:r1])
                 r0, l0 = r1, l1
-        x1 = ops.gemm(o, a._w16("proj", a.proj.weight), out_f32=True, bias_n=a._f32("proj_b", a.proj.bias), scale_n=g1,
-                      res=x2, a_lo=o_lo, b_lo=a._w16lo("proj", a.proj.weight))
-        xn2 = ops.layernorm(x1, self._f32("n2w", self.norm2.weight), self._f32("n2b", self.norm2.bias), self.norm2.eps, dt)
+        return qkv, o, o_lo, lse
+
+    def forward_train_rows(self, x2: torch.Tensor, segs, keep=None):
+        """``forward_train`` on several token batches stacked along the rows of one fp32 [R, D] matrix (``segs`` =
+        [(B, N), ...], see ``forward_rows``): every GEMM / LayerNorm / GELU launch — and in the backward every weight-gradient
+        GEMM — covers all rows, so the parameter gradients of the two ViT passes of the unfrozen adapter step (BASELINE
+        config 4) are summed by construction; only the attention runs per batch.
+
+        ``keep`` = ``(keep_attn, keep_ffn)``: stochastic depth (droppath.py).  A branch entry is ``None`` (nothing dropped: the
+        code path without ``keep``), a ``droppath.BranchKeep`` of a packed step, or one ``(indices, alpha)`` per segment.  A
+        dropped branch runs on the kept samples alone: LayerNorm gathers their rows into a compact 16-bit matrix, the GEMMs
+        and the attention run on it with the shortened segment list, and ``out = x (+ alpha * ls(branch) on kept rows)``;
+        its saved activations are compact.  A branch with nothing kept is skipped."""
+        dt = config.operand_dtype
+        D = x2.shape[1]
+        m = self.mlp
+        g1 = self._f32("g1", self.ls1.gamma) if isinstance(self.ls1, LayerScale) else None
+        g2 = self._f32("g2", self.ls2.gamma) if isinstance(self.ls2, LayerScale) else None
+        a = self.attn
+        segs = list(segs)
+        if sum(B * N for B, N in segs) != x2.shape[0]:
+            raise ValueError("forward_train_rows: segments do not cover the rows")
+        ka, kf = droppath.as_branch_keeps(keep, segs, x2.device)
+        n1w, n1b = self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias)
+        if ka is None:
+            xn = ops.layernorm(x2, n1w, n1b, self.norm1.eps, dt)
+            qkv, o, o_lo, lse = self._attn_train(xn, segs)
+            x1 = ops.gemm(o, a._w16("proj", a.proj.weight), out_f32=True, bias_n=a._f32("proj_b", a.proj.bias), scale_n=g1,
+                          res=x2, a_lo=o_lo, b_lo=a._w16lo("proj", a.proj.weight))
+        elif ka.empty:
+            xn = qkv = o = lse = None
+            x1 = x2
+        else:
+            xn = ops.layernorm_gather(x2, n1w, n1b, self.norm1.eps, dt, ka)
+            qkv, o, o_lo, lse = self._attn_train(xn, ka.segs)
+            y = ops.gemm(o, a._w16("proj", a.proj.weight), out_f32=True, bias_n=a._f32("proj_b", a.proj.bias), scale_n=g1,
+                         a_lo=o_lo, b_lo=a._w16lo("proj", a.proj.weight))
+            x1 = ops.scaled_index_add(x2, y, ka)
+        n2w, n2b = self._f32("n2w", self.norm2.weight), self._f32("n2b", self.norm2.bias)
+        if kf is not None and kf.empty:
+            saved = (x2, xn, qkv, o, lse, x1, None, None, None, segs, (ka, kf))
+            return x1, saved
+        xn2 = ops.layernorm(x1, n2w, n2b, self.norm2.eps, dt) if kf is None else ops.layernorm_gather(x1, n2w, n2b, self.norm2.eps, dt, kf)
+        okw = dict(out_f32=True, scale_n=g2)
+        if kf is None:
+            okw["res"] = x1
         if isinstance(m, Mlp):
             hpre = ops.gemm(xn2, m._w16("fc1", m.fc1.weight), bias_n=m._f32("fc1_b", m.fc1.bias))
             hpost = ops.gelu16(hpre)
-            x3 = ops.gemm(hpost, m._w16("fc2", m.fc2.weight), out_f32=True, bias_n=m._f32("fc2_b", m.fc2.bias), scale_n=g2,
-                          res=x1)
+            x3 = ops.gemm(hpost, m._w16("fc2", m.fc2.weight), bias_n=m._f32("fc2_b", m.fc2.bias), **okw)
         else:  # SwiGLU (ViT-g): hpre = the fp32 [x1 | x2] of w12, hpost = silu(x1) * x2
             hpre = ops.gemm(xn2, m._w16("w12", m.w12.weight), out_f32=True, bias_n=m._f32("w12_b", m.w12.bias))
             hpost = ops.swiglu(hpre, dt)
-            x3 = ops.gemm(hpost, m._w16("w3", m.w3.weight), out_f32=True, bias_n=m._f32("w3_b", m.w3.bias), scale_n=g2,
-                          res=x1)
-        return x3, (x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, list(segs))
+            x3 = ops.gemm(hpost, m._w16("w3", m.w3.weight), bias_n=m._f32("w3_b", m.w3.bias), **okw)
+        if kf is not None:
+            x3 = ops.scaled_index_add(x1, x3, kf)
+        saved = (x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, segs)
+        return x3, (saved if keep is None else saved + ((ka, kf),))
 
     def backward(self, saved, dres: torch.Tensor, inv_scale: float, grads: Optional[dict] = None, prefix: str = "") -> torch.Tensor:
         """dres fp32 [B*N, D] = loss_scale * dL/d(block output) -> loss_scale * dL/d(block input).  With ``grads``
         (name -> fp32 tensor, names as in ``state_dict`` under ``prefix``) the parameter gradients are written too;
         without it only the input gradient is produced (frozen backbone, adapters training)."""
-        x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, segs = saved
+        x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, segs = saved[:10]
+        ka, kf = saved[10] if len(saved) > 10 else (None, None)     # stochastic depth: the kept samples of the two branches
         dt = config.operand_dtype
         D = x2.shape[1]
         a, m = self.attn, self.mlp
@@ -754,31 +796,49 @@ class Block(_Packed):
         k1, k2 = self._ls_pow2("ls1.k", ls1), self._ls_pow2("ls2.k", ls2)
         inv1, inv2 = inv_scale * 2.0 ** -k1, inv_scale * 2.0 ** -k2
         # ---- MLP branch: out = x1 + ls2 * fc2(gelu(fc1(LN2(x1)))) ----
-        d16, cs = ops.cast_colsum(dres, dt) if grads is not None else (ops.cast_pad(dres, D, dt), None)
         if isinstance(m, Mlp):
             lin_out, lin_in, n_out, n_in, act_bwd = m.fc2, m.fc1, "mlp.fc2", "mlp.fc1", ops.gelu16
         else:
             lin_out, lin_in, n_out, n_in, act_bwd = m.w3, m.w12, "mlp.w3", "mlp.w12", ops.swiglu_bwd
-        self._linear_bwd(pre + n_out, lin_out, ls2, pre + "ls2.gamma", d16, cs, hpost, inv_scale, grads)
-        R = d16.shape[0]
-        if isinstance(m, Mlp) and R >= 256 and lin_out.in_features >= 128 and lin_out.in_features % 4 == 0 and D % 32 == 0:
-            # fc2's input gradient with GELU's backward in the GEMM epilogue: d pre = (d16 W) * gelu'(pre)
-            dh = ops.gemm(d16, self._wT16("fc2T", lin_out.weight, ls2, k2), act=ops.ACT_GELU_GRAD, aux=hpre)
+        if kf is not None and kf.empty:      # the branch saw no sample: no parameter gradient, the stream gradient passes
+            dx1 = dres
+            self._zero_grads(grads, [pre + n_out, pre + n_in, pre + "norm2"], pre + "ls2.gamma")
         else:
-            dh = ops.gemm(d16, self._wT16("fc2T", lin_out.weight, ls2, k2))        # 16-bit [R, hidden], times 2^k2
-            dh = act_bwd(hpre, dh)                                                 # GELU' / SwiGLU gate backward
-        self._linear_bwd(pre + n_in, lin_in, None, None, dh, ops.colsum(dh) if grads is not None else None, xn2,
-                         inv2, grads)
-        dln = ops.gemm(dh, self._wT16("fc1T", lin_in.weight), out_f32=True)        # fp32 [R, D], times 2^k2
-        dx1, part = ops.layernorm_bwd(dln, x1, self._nw_pow2("n2w", self.norm2.weight, -k2), self.norm2.eps, res=dres)
-        if grads is not None:
-            red = ops.reduce_rows(part.view(part.shape[0], 2 * D), inv2)
-            grads[pre + "norm2.weight"].copy_(red[:D]); grads[pre + "norm2.bias"].copy_(red[D:])
+            # a dropped branch (kf): d16 = alpha * dres on the kept rows, compact like hpost / hpre / xn2
+            if kf is not None:
+                d16, cs = ops.gather_cast_colsum(dres, dt, kf, colsum=grads is not None)
+            else:
+                d16, cs = ops.cast_colsum(dres, dt) if grads is not None else (ops.cast_pad(dres, D, dt), None)
+            self._linear_bwd(pre + n_out, lin_out, ls2, pre + "ls2.gamma", d16, cs, hpost, inv_scale, grads)
+            R = d16.shape[0]
+            if isinstance(m, Mlp) and R >= 256 and lin_out.in_features >= 128 and lin_out.in_features % 4 == 0 and D % 32 == 0:
+                # fc2's input gradient with GELU's backward in the GEMM epilogue: d pre = (d16 W) * gelu'(pre)
+                dh = ops.gemm(d16, self._wT16("fc2T", lin_out.weight, ls2, k2), act=ops.ACT_GELU_GRAD, aux=hpre)
+            else:
+                dh = ops.gemm(d16, self._wT16("fc2T", lin_out.weight, ls2, k2))        # 16-bit [R, hidden], times 2^k2
+                dh = act_bwd(hpre, dh)                                                 # GELU' / SwiGLU gate backward
+            self._linear_bwd(pre + n_in, lin_in, None, None, dh, ops.colsum(dh) if grads is not None else None, xn2,
+                             inv2, grads)
+            dln = ops.gemm(dh, self._wT16("fc1T", lin_in.weight), out_f32=True)        # fp32 [R, D], times 2^k2
+            if kf is not None:
+                dx1, part = ops.layernorm_bwd_scatter(dln, x1, self._nw_pow2("n2w", self.norm2.weight, -k2), self.norm2.eps, dres, kf)
+            else:
+                dx1, part = ops.layernorm_bwd(dln, x1, self._nw_pow2("n2w", self.norm2.weight, -k2), self.norm2.eps, res=dres)
+            if grads is not None:
+                red = ops.reduce_rows(part.view(part.shape[0], 2 * D), inv2)
+                grads[pre + "norm2.weight"].copy_(red[:D]); grads[pre + "norm2.bias"].copy_(red[D:])
         # ---- attention branch: x1 = x + ls1 * proj(attn(LN1(x))) ----
-        d16, cs = ops.cast_colsum(dx1, dt) if grads is not None else (ops.cast_pad(dx1, D, dt), None)
+        if ka is not None and ka.empty:
+            self._zero_grads(grads, [pre + "attn.proj", pre + "attn.qkv", pre + "norm1"], pre + "ls1.gamma")
+            return dx1
+        if ka is not None:
+            d16, cs = ops.gather_cast_colsum(dx1, dt, ka, colsum=grads is not None)
+            segs = ka.segs
+        else:
+            d16, cs = ops.cast_colsum(dx1, dt) if grads is not None else (ops.cast_pad(dx1, D, dt), None)
         self._linear_bwd(pre + "attn.proj", a.proj, ls1, pre + "ls1.gamma", d16, cs, o, inv_scale, grads)
         dO = ops.gemm(d16, self._wT16("projT", a.proj.weight, ls1, k1))            # 16-bit [R, D], times 2^k1
-        dqkv = torch.empty((x2.shape[0], 3 * D), device=x2.device, dtype=dt)
+        dqkv = torch.empty((d16.shape[0], 3 * D), device=x2.device, dtype=dt)
         if isinstance(lse, (list, tuple)):   # per-batch [B, H, N] tensors (the MaskTransformer block's forward)
             lse = torch.cat([l.reshape(-1) for l in lse])
         q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
@@ -791,11 +851,23 @@ class Block(_Packed):
         self._linear_bwd(pre + "attn.qkv", a.qkv, None, None, dqkv, ops.colsum(dqkv) if grads is not None else None, xn,
                          inv1, grads)
         dln = ops.gemm(dqkv, self._wT16("qkvT", a.qkv.weight), out_f32=True)
-        dx, part = ops.layernorm_bwd(dln, x2, self._nw_pow2("n1w", self.norm1.weight, -k1), self.norm1.eps, res=dx1)
+        if ka is not None:
+            dx, part = ops.layernorm_bwd_scatter(dln, x2, self._nw_pow2("n1w", self.norm1.weight, -k1), self.norm1.eps, dx1, ka)
+        else:
+            dx, part = ops.layernorm_bwd(dln, x2, self._nw_pow2("n1w", self.norm1.weight, -k1), self.norm1.eps, res=dx1)
         if grads is not None:
             red = ops.reduce_rows(part.view(part.shape[0], 2 * D), inv1)
             grads[pre + "norm1.weight"].copy_(red[:D]); grads[pre + "norm1.bias"].copy_(red[D:])
         return dx
+
+    @staticmethod
+    def _zero_grads(grads: Optional[dict], modules, gamma: str) -> None:
+        """a branch of stochastic depth that kept no sample: the gradients of its parameters are zero"""
+        if grads is None:
+            return
+        for name in [mname + sfx for mname in modules for sfx in (".weight", ".bias")] + [gamma]:
+            if name in grads:
+                grads[name].zero_()
 
 
 def run_blocks(blocks, x: torch.Tensor, segs) -> torch.Tensor:

@@ -4,7 +4,8 @@
 ``forward_features`` / ``forward(is_training=True)``.
 
 Only what the hot path uses is implemented: ``block_chunks=0`` (flat ``blocks.{i}`` keys, as in
-`dinov2/configs/ssl_default_config.yaml`), no masks, no register tokens, drop_path 0.
+`dinov2/configs/ssl_default_config.yaml`), no masks, no register tokens; ``drop_path_rate`` sets the per-block rates of
+stochastic depth, which only a training engine of the unfrozen backbone draws (droppath.py).
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ from typing import Optional, Sequence, Tuple, Union
 import torch
 import torch.nn as nn
 
-from ... import config, ops
+from ... import config, droppath, ops
 from ..layers.blocks import _pack
 from ..layers import MemEffAttention, Mlp, NestedTensorBlock as Block, PatchEmbed, SwiGLUFFNFused
 
@@ -29,8 +30,11 @@ class DinoVisionTransformer(nn.Module):
         super().__init__()
         if block_chunks not in (0, None):
             raise ValueError("block_chunks must be 0 on this path (dinov2/configs/ssl_default_config.yaml)")
-        if drop_path_rate or num_register_tokens or interpolate_antialias:
-            raise ValueError("drop_path / register tokens / antialias are not part of the AdapterSIS path")
+        if num_register_tokens or interpolate_antialias:
+            raise ValueError("register tokens / antialias are not part of the AdapterSIS path")
+        # `vision_transformer.py:103-106`: one stochastic-depth rate per block, kept on ``Block.sample_drop_ratio``; drawn by the
+        # engine that trains the backbone (droppath.DropPathSampler), never inside the model
+        self.drop_path_rates = droppath.block_rates(drop_path_rate, depth, drop_path_uniform)
         norm_layer = partial(nn.LayerNorm, eps=1e-6)
         self.num_features = self.embed_dim = embed_dim
         self.num_tokens = 1
@@ -50,9 +54,9 @@ class DinoVisionTransformer(nn.Module):
             raise NotImplementedError(ffn_layer)
         self.blocks = nn.ModuleList([
             block_fn(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, proj_bias=proj_bias,
-                     ffn_bias=ffn_bias, drop_path=0.0, norm_layer=norm_layer, act_layer=act_layer, ffn_layer=ffn,
+                     ffn_bias=ffn_bias, drop_path=self.drop_path_rates[i], norm_layer=norm_layer, act_layer=act_layer, ffn_layer=ffn,
                      init_values=init_values)
-            for _ in range(depth)])
+            for i in range(depth)])
         self.chunked_blocks = False
         self.norm = norm_layer(embed_dim)
         self.head = nn.Identity()
@@ -115,16 +119,20 @@ class DinoVisionTransformer(nn.Module):
         return self.patch_embed.tokens(x)
 
     # -- training path: forward_features under autograd (eval_dinov2_setr_cross_ete.py:145-148,318-321) -----------
-    def forward_train(self, x: torch.Tensor):
-        """images (B,3,H,W) -> (x_norm_patchtokens fp32 (B,N,D) view, saved activations for ``backward``)."""
+    def forward_train(self, x: torch.Tensor, keep=None):
+        """images (B,3,H,W) -> (x_norm_patchtokens fp32 (B,N,D) view, saved activations for ``backward``).  ``keep``: stochastic
+        depth, one entry per block (``None`` or ``(keep_attn, keep_ffn)``: ``Block.forward_train_rows``) over the one token
+        batch [(B, N + 1)]; without it nothing is dropped whatever the blocks' rates."""
         B, nc, w, h = x.shape
         t, a16 = self.patch_tokens_train(x)
         pos = self._pos_for(t.shape[1], w, h)
         xx = ops.add_cls_pos(t, self.cls_token.detach().reshape(-1).float().contiguous(),
                              pos.detach().reshape(-1, self.embed_dim).float().contiguous())
         saved = []
-        for blk in self.blocks:
-            xx, s = blk.forward_train(xx)
+        if keep is not None and len(keep) != len(self.blocks):
+            raise ValueError("forward_train: keep needs one entry per block")
+        for i, blk in enumerate(self.blocks):
+            xx, s = blk.forward_train(xx) if keep is None or keep[i] is None else blk.forward_train(xx, keep=keep[i])
             saved.append(s)
         x_norm = self._final_norm(xx)
         return x_norm[:, 1:], (a16, xx, saved, (B, t.shape[1], w, h))

@@ -616,6 +616,77 @@ def cast_colsum(x: torch.Tensor, dtype: torch.dtype, scale: float = 1.0):
     return out, partial
 
 
+# ---- stochastic depth (csrc/droppath.hip): the row kernels above behind a sample indirection.  ``keep`` = a
+# droppath.BranchKeep: .tab (int32 device table), .K kept of .S samples, .rows full-stream rows, .rows_c compact rows ------------
+def _keep_check(name: str, keep, x: torch.Tensor) -> None:
+    _dev(x, keep.tab)
+    if keep.tab.dtype != torch.int32 or not keep.tab.is_contiguous() or keep.tab.numel() != 3 * keep.K + 3 * keep.S + 2:
+        raise ValueError(f"{name}: keep.tab must be a contiguous int32 table of 3K + 3S + 2 words")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1 or x.shape[0] != keep.rows:
+        raise ValueError(f"{name}: float32 [{keep.rows}, D] rows of the full stream expected")
+
+
+def layernorm_gather(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, out_dtype: torch.dtype, keep) -> torch.Tensor:
+    """LayerNorm of the kept samples' rows of the fp32 [R, D] stream -> compact 16-bit [R', D] (``ops.layernorm`` of a gather)."""
+    _keep_check("layernorm_gather", keep, x)
+    _dev(w, b)
+    D = x.shape[1]
+    out = torch.empty((keep.rows_c, D), device=x.device, dtype=out_dtype)
+    check(lib().asis_layernorm_gather(_stream(), _dt(out_dtype), x.data_ptr(), x.stride(0), _f32c(w).data_ptr(), _f32c(b).data_ptr(),
+                                      float(eps), out.data_ptr(), D, keep.tab.data_ptr(), keep.K, keep.S, keep.rows_c, D),
+          "asis_layernorm_gather")
+    return out
+
+
+def scaled_index_add(x: torch.Tensor, res: torch.Tensor, keep) -> torch.Tensor:
+    """fp32: out [R, D] = x, and x + alpha * res [R', D] on the rows of the kept samples (plain stores: reproducible)."""
+    _keep_check("scaled_index_add", keep, x)
+    _dev(res)
+    D = x.shape[1]
+    if res.dtype != torch.float32 or res.shape != (keep.rows_c, D) or res.stride(1) != 1:
+        raise ValueError("scaled_index_add: res must be the compact float32 [R', D] branch output")
+    out = torch.empty((keep.rows, D), device=x.device, dtype=torch.float32)
+    check(lib().asis_scaled_index_add(_stream(), x.data_ptr(), x.stride(0), res.data_ptr() if keep.rows_c else None,
+                                      res.stride(0) if keep.rows_c else 0, out.data_ptr(), D, keep.tab.data_ptr(), keep.K, keep.S,
+                                      keep.rows, D), "asis_scaled_index_add")
+    return out
+
+
+def gather_cast_colsum(x: torch.Tensor, dtype: torch.dtype, keep, colsum: bool = True):
+    """fp32 [R, D] -> (compact 16-bit [R', D] = alpha * x on the kept rows, partial fp32 [nblk(R'), D] column sums of alpha * x, or
+    None without ``colsum``): ``cast_colsum`` with the sample's own scale, behind the gather."""
+    _keep_check("gather_cast_colsum", keep, x)
+    D = x.shape[1]
+    out = torch.empty((keep.rows_c, D), device=x.device, dtype=dtype)
+    partial = None
+    if colsum:
+        nblk = lib().asis_rowblock_nblk(keep.rows_c)
+        partial = (torch.empty if keep.rows_c else torch.zeros)((nblk, D), device=x.device, dtype=torch.float32)
+    check(lib().asis_gather_cast_colsum(_stream(), _dt(dtype), x.data_ptr(), x.stride(0), out.data_ptr() if keep.rows_c else None, D,
+                                        _p(partial), keep.tab.data_ptr(), keep.K, keep.S, keep.rows_c, D), "asis_gather_cast_colsum")
+    return out, partial
+
+
+def layernorm_bwd_scatter(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, eps: float, res: torch.Tensor, keep):
+    """dy fp32 [R', D] (compact), x / res fp32 [R, D] -> (dx [R, D] = res + LN^T(dy) on the kept rows, res elsewhere;
+    partial fp32 [nblk(R'), 2, D] = (d weight, d bias) sums over the R' rows)."""
+    _keep_check("layernorm_bwd_scatter", keep, x)
+    _dev(dy, res, w)
+    D = x.shape[1]
+    if res.dtype != torch.float32 or res.shape != x.shape or res.stride(1) != 1:
+        raise ValueError("layernorm_bwd_scatter: res must be float32 [R, D] like x")
+    if dy.dtype != torch.float32 or dy.shape != (keep.rows_c, D) or dy.stride(1) != 1:
+        raise ValueError("layernorm_bwd_scatter: dy must be the compact float32 [R', D] gradient")
+    out = torch.empty((keep.rows, D), device=x.device, dtype=torch.float32)
+    nblk = lib().asis_rowblock_nblk(keep.rows_c)
+    partial = (torch.empty if keep.rows_c else torch.zeros)((nblk, 2, D), device=x.device, dtype=torch.float32)   # nothing kept: no partial is written
+    check(lib().asis_layernorm_bwd_scatter(_stream(), dy.data_ptr() if keep.rows_c else None, dy.stride(0) if keep.rows_c else 0,
+                                           x.data_ptr(), x.stride(0), _f32c(w).data_ptr(), float(eps), res.data_ptr(), res.stride(0),
+                                           out.data_ptr(), D, partial.data_ptr(), keep.tab.data_ptr(), keep.K, keep.S, keep.rows,
+                                           keep.rows_c, D), "asis_layernorm_bwd_scatter")
+    return out, partial
+
+
 def ls_linear_finish(G: torch.Tensor, W: Optional[torch.Tensor], bias, gamma, cs, grad_scale: float, dW: torch.Tensor,
                      db: Optional[torch.Tensor], dgamma: Optional[torch.Tensor]) -> None:
     """See include/asis_hip.h: (G, cs) -> dW, db, dgamma of ``x + gamma * (A W^T + b)`` (gamma None: plain Linear)."""

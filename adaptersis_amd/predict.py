@@ -381,7 +381,8 @@ def build_engine(args) -> SegEngine:
         torch.manual_seed(args.seed)
     model, enc, cv, cn, dec = _t.build_modules(args, args.head, args.num_classes, dev)
     eng = SegEngine(model, enc, cv, cn, dec, num_classes=args.num_classes)
-    load_checkpoint(path, dec, {"cross_vit": cv, "cross_cnn": cn, "backbone_encoder": enc},
+    # "backbone": the ViT of a run with --optimize_backbone (absent from any other checkpoint: the pretrained weights stay)
+    load_checkpoint(path, dec, {"cross_vit": cv, "cross_cnn": cn, "backbone_encoder": enc, "backbone": model},
                     hint=f" (--head {args.head} --num_classes {args.num_classes})", ck=ck)
     print(f"loaded {path} (epoch {ck.get('epoch')}, entries {sorted(k for k in ck if isinstance(ck[k], dict))})")
     return eng

@@ -163,6 +163,33 @@ def _optimizer_args(args) -> dict:
             "layer_decay": args.layer_decay}
 
 
+def _backbone_args(args) -> dict:
+    """The backbone fine-tuning flags (--train_backbone, --optimize_backbone, --drop_path_seed) as ``SegEngine`` arguments; a
+    namespace built without them, or with all of them at their defaults: nothing is passed and the engine is what it was."""
+    out = {}
+    if getattr(args, "train_backbone", False):
+        out["train_backbone"] = True
+    if getattr(args, "optimize_backbone", False):
+        out["optimize_backbone"] = True
+    if getattr(args, "drop_path_seed", 0):
+        out["drop_path_seed"] = int(args.drop_path_seed)
+    return out
+
+
+def check_backbone_args(args) -> Optional[str]:
+    """What is wrong with the combination of the backbone fine-tuning flags, or None"""
+    if getattr(args, "train_backbone", False) and not getattr(args, "train_adapters", False):
+        return "--train_backbone needs --train_adapters (the unfrozen variant of the adapter flow)"
+    if getattr(args, "optimize_backbone", False) and not getattr(args, "train_backbone", False):
+        return "--optimize_backbone needs --train_backbone"
+    r = float(getattr(args, "drop_path", 0.0))
+    if not 0.0 <= r < 1.0:
+        return "--drop_path must be in [0, 1)"
+    if r > 0.0 and not getattr(args, "train_backbone", False):
+        return "--drop_path drops samples in the training forward of the ViT blocks: it needs --train_backbone"
+    return None
+
+
 def _loss_args(args) -> dict:
     """The parameters of the hard-pixel losses (--topk_percent, --focal_gamma) as ``SegEngine`` arguments."""
     return {"topk_percent": getattr(args, "topk_percent", 10.0), "focal_gamma": getattr(args, "focal_gamma", 2.0)}
@@ -176,7 +203,8 @@ def build_modules(args, head: str, num_classes: int, dev):
     D = W.VIT_CONFIGS[arch][0]
     # dinov2/eval/setup.py:62-75 + models/__init__.py:14-29 (teacher, img_size 518, layerscale 1e-5, block_chunks 0)
     model = vits.__dict__[arch](patch_size=args.patch_size, img_size=518, init_values=1e-5, ffn_layer=ARCH_FFN[arch],
-                                block_chunks=0)
+                                block_chunks=0, drop_path_rate=float(getattr(args, "drop_path", 0.0)),
+                                drop_path_uniform=bool(getattr(args, "drop_path_uniform", False)))
     if args.pretrained_weights and os.path.isfile(args.pretrained_weights):
         utils.load_pretrained_weights(model, args.pretrained_weights, args.checkpoint_key)   # dinov2/utils/utils.py:20-33
     else:
@@ -207,6 +235,9 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     non_rigid_p = float(getattr(args, "aug_non_rigid", 0.0))
     if not 0.0 <= non_rigid_p <= 1.0:
         raise ValueError("--aug_non_rigid must be a probability in [0, 1]")
+    bad = check_backbone_args(args)
+    if bad:
+        raise ValueError(bad)
     utils.init_distributed_mode(args)
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     dev = torch.device("cuda", args.gpu)
@@ -220,13 +251,13 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
                              weight_decay=0.0 if wd is None else wd, num_classes=num_classes, loss=loss, **_optimizer_args(args),
-                             **_loss_args(args))
+                             **_loss_args(args), **_backbone_args(args))
     else:
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=args.lr,
                              weight_decay=3e-5 if wd is None else wd,
                              mode="train_adapters" if getattr(args, "train_adapters", False) else "reference_exact",
                              train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss,
-                             **_optimizer_args(args), **_loss_args(args))
+                             **_optimizer_args(args), **_loss_args(args), **_backbone_args(args))
     optimizer = engine.optimizer
     engine.aug_non_rigid = non_rigid_p      # read by train(): its signature is the reference's and carries no arguments
 
@@ -273,6 +304,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
         extra = {"cross_vit": cross_vit, "cross_cnn": cross_cnn}
         if engine.train_encoder:
             extra["backbone_encoder"] = backbone_encoder
+        if getattr(args, "optimize_backbone", False):   # a fine-tuned ViT is part of the trained model: saved and restored
+            extra["backbone"] = model
     utils.restart_from_checkpoint(os.path.join(args.output_dir, "checkpoint.pth.tar"), run_variables=to_restore,
                                   state_dict=seg_decoder, **extra, optimizer=optimizer, scheduler=scheduler)
     start_epoch, best_acc = to_restore["epoch"], to_restore["best_acc"]
@@ -389,8 +422,20 @@ def validate_network(val_loader, model, feature_model, backbone_encoder, cross_v
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
 
 
+class _ArgumentParser(argparse.ArgumentParser):
+    """``ArgumentParser`` that also rejects combinations of the backbone fine-tuning flags no engine can be built from
+    (``check_backbone_args``), as a usage error like any other"""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        bad = check_backbone_args(ns)
+        if bad:
+            self.error(bad)
+        return ns, rest
+
+
 def get_args_parser():
-    p = argparse.ArgumentParser("Evaluation with semantic segmentation on RobustMIS2019")
+    p = _ArgumentParser("Evaluation with semantic segmentation on RobustMIS2019")
     p.add_argument("--n_last_blocks", default=4, type=int)
     p.add_argument("--avgpool_patchtokens", default=False, type=utils.bool_flag)
     p.add_argument("--arch", default="vit_large", type=str)
@@ -427,7 +472,17 @@ def get_args_parser():
     p.add_argument("--adam_eps", default=1e-8, type=float)
     p.add_argument("--clip_grad", default=None, type=float, help="adamw: clip the global gradient norm at this value")
     p.add_argument("--layer_decay", default=None, type=float,
-                   help="adamw: layer-wise learning-rate decay of the ViT blocks (engines that optimise the backbone)")
+                   help="adamw: layer-wise learning-rate decay of the ViT blocks (needs --train_backbone --optimize_backbone)")
+    # extension: fine-tune the ViT itself (BASELINE config 4: SegEngine train_backbone / optimize_backbone) with stochastic depth
+    p.add_argument("--train_backbone", action="store_true",
+                   help="with --train_adapters: both ViT passes run with saved activations and the backward reaches every block")
+    p.add_argument("--optimize_backbone", action="store_true",
+                   help="with --train_backbone: the optimizer also steps the ViT; the checkpoint gains a 'backbone' entry")
+    p.add_argument("--drop_path", default=0.0, type=float, metavar="R",
+                   help="stochastic depth rate of the ViT (DINOv2's drop_path_rate; needs --train_backbone): block i gets "
+                        "linspace(0, R, depth)[i]; above 0.1 a branch runs on a random subset of the batch only")
+    p.add_argument("--drop_path_uniform", action="store_true", help="every block gets --drop_path")
+    p.add_argument("--drop_path_seed", default=0, type=int, help="seed of the stochastic-depth draws (the generator is seeded with this and the rank)")
     # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
     p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
                    help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that; "

@@ -341,6 +341,31 @@ int asis_ls_linear_finish(void* stream, const float* G, const float* W, const fl
                           const float* cs, float grad_scale, float* dW, float* db, float* dgamma, int N, int K);
 
 /* ---------------------------------------------------------------------------------------------
+ * Stochastic depth in DINOv2's subset form (dinov2/layers/block.py:117-138): a residual branch runs on the K kept of the S
+ * stacked samples only, on a COMPACT [rows_c, D] matrix; these are the row kernels above behind a sample indirection.
+ * tab: int32 device table of one branch (adaptersis_amd/droppath.py builds it), 3K + 3S + 2 words:
+ *   cpre[K+1] compact row prefix of the kept samples | src[K] first full-stream row of each | alpha[K] (float) its scale |
+ *   spre[S+1] full-stream row prefix of all samples | cpos[S] first compact row of a sample, -1 = dropped | salpha[S] (float)
+ * Rows are int32 in the table (< 2^31).  The kept samples are distinct: plain stores, no atomics, reproducible.
+ * asis_layernorm_gather:      y[r] (16-bit, compact) = LayerNorm(x[row of r]) — the per-row arithmetic of asis_layernorm
+ * asis_scaled_index_add:      out[r] = x[r] (+ salpha * res[compact row of r] when r's sample is kept), fp32; out != x
+ * asis_gather_cast_colsum:    out[r] (16-bit, compact) = alpha * x[row of r]; partial[asis_rowblock_nblk(rows_c)][D] = column sums
+ *                             of alpha * x over the block's rows (NULL: the cast alone)
+ * asis_layernorm_bwd_scatter: dx[row of r] = res[row of r] + LN^T(dy[r]) with the statistics of x[row of r] (asis_layernorm_bwd),
+ *                             dx = res on the rows of dropped samples; partial[asis_rowblock_nblk(rows_c)][2][D] over the rows_c rows
+ * K == 0 (nothing kept): nothing compact is read or written; the two full-stream kernels copy.
+ * ------------------------------------------------------------------------------------------- */
+int asis_layernorm_gather(void* stream, int dtype, const float* x, int64_t ldx, const float* w, const float* b, float eps, void* y,
+                          int64_t ldy, const int32_t* tab, int K, int S, int64_t rows_c, int D);
+int asis_scaled_index_add(void* stream, const float* x, int64_t ldx, const float* res, int64_t ldres, float* out, int64_t ldo,
+                          const int32_t* tab, int K, int S, int64_t rows, int D);
+int asis_gather_cast_colsum(void* stream, int dtype, const float* x, int64_t ldx, void* out, int64_t ldo, float* partial,
+                            const int32_t* tab, int K, int S, int64_t rows_c, int D);
+int asis_layernorm_bwd_scatter(void* stream, const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w, float eps,
+                               const float* res, int64_t ldr, float* dx, int64_t lddx, float* partial, const int32_t* tab, int K, int S,
+                               int64_t rows, int64_t rows_c, int D);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-scale deformable attention core (backbones/ops/modules/ms_deform_attn.py:33-54 and the
  * location / softmax arithmetic of MSDeformAttn.forward :155-166), forward.
  * value: 16-bit [B, Lin, M*Dh] (output of value_proj; head m at columns m*Dh..)
