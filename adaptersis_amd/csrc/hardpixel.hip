@@ -23,18 +23,18 @@
 //            recomputed as in lovasz_dz_kernel: no [N][C] buffer), exactly 0 on unselected pixels (untouched with accumulate)
 //   finalize the tile sums in double in a fixed order -> loss
 //
-// Histograms: per workgroup in LDS, 256 counters, one digit per thread when they are flushed.  A wave finds the lanes that hold
-// the same digit with 8 ballots (match_digit of lovasz.hip) and its first lane adds the popcount: cross-entropy values crowd
-// into a few top bytes, this keeps the LDS atomics off one address.  The workgroup's counters are then added to the 256
+// Histograms: per workgroup in LDS, 256 counters, one digit per thread when they are flushed, filled by count_digit of
+// radix_routines.h (which also holds the scans, the reductions and the tile constants RX_*): cross-entropy values crowd into
+// a few top bytes, and it keeps the LDS atomics off one address.  The workgroup's counters are then added to the 256
 // global ones with integer atomics: integer sums do not depend on the order, so the result is bit-identical between calls.
 // Every floating-point sum has a fixed order (thread: items in order; wave: xor tree; workgroup: 4 waves; tiles: finalize).
 // Tile: 256 threads x 8 values = 2048, position = tile*2048 + item*256 + thread (coalesced, and ascending in (item, wave, lane)).
 #include "asis_common.h"
-#include "bilinear_tap.h"  // MAXC, sample_logits
+#include "bilinear_tap.h"  // MAXC, sample_logits_at, softmax_c, softmax_bwd_c
+#include "radix_routines.h"
 
 namespace {
 
-constexpr int HP_THREADS = 256, HP_WAVES = 4, HP_ITEMS = 8, HP_TILE = HP_THREADS * HP_ITEMS, HP_RADIX = 256;
 constexpr int HP_HIST_BLOCKS = 1024;  // workgroups of a histogram pass (each loops over tiles): bounds the global atomics
 
 struct HpCfg {
@@ -42,59 +42,11 @@ struct HpCfg {
   float gamma, smooth, o_hit, o_miss;  // the (clamped) one-hot row: o_hit at the label, o_miss elsewhere
 };
 
-// the softmax arithmetic of loss.hip's softmax_c / softmax_bwd_c (same operations in the same order)
-__device__ __forceinline__ void hp_softmax_c(float* z, int C) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) m = fmaxf(m, z[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) {
-      z[c] = __expf(z[c] - m);
-      s += z[c];
-    }
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) z[c] *= inv;
-}
-__device__ __forceinline__ void hp_softmax_bwd_c(float* g, const float* p, int C) {  // g <- p * (g - <g, p>)
-  float dot = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) dot += g[c] * p[c];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) g[c] = p[c] * (g[c] - dot);
-}
-
 // order-preserving map fp32 -> uint32 (larger value = larger key), -0 == +0
 __device__ __forceinline__ uint32_t hp_key(float v) {
   uint32_t b = __builtin_bit_cast(uint32_t, v);
   if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t hp_lanes_below(int lane) { return (1ull << lane) - 1ull; }
-// the valid lanes of the wave that hold digit d (all 64 lanes call it)
-__device__ __forceinline__ uint64_t hp_match_digit(int d, bool valid) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const bool bit = (d >> b) & 1;
-    const uint64_t bm = __ballot(bit);
-    m &= bit ? bm : ~bm;
-  }
-  return m;
-}
-__device__ __forceinline__ int hp_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
 }
 
 // v_i of pixel i; with `g` also d v_i / d z (through the clamped one-hot and, n_softmax = 1, the softmax transpose)
@@ -108,12 +60,8 @@ __device__ __forceinline__ float hp_pixel(const float* __restrict__ logits, cons
     }
     return 0.f;
   }
-  const int64_t hw = (int64_t)k.H * k.W;
-  const int b = (int)(i / hw);
-  const int p = (int)(i - (int64_t)b * hw);
-  const int y = p / k.W, x = p - y * k.W;
   float z[MAXC];
-  sample_logits(logits + (int64_t)b * k.h * k.w * k.C, k.h, k.w, k.C, y, x, (float)k.h / (float)k.H, (float)k.w / (float)k.W, z);
+  sample_logits_at(logits, k.h, k.w, k.H, k.W, k.C, i, z);
   const float wt = cw ? cw[t] : 1.f;
   if (k.kind == 0) {
     float m = -INFINITY, zt = 0.f;
@@ -128,13 +76,13 @@ __device__ __forceinline__ float hp_pixel(const float* __restrict__ logits, cons
     for (int c = 0; c < MAXC; ++c)
       if (c < k.C) se += expf(z[c] - m);
     if (g) {  // w (softmax(z) - onehot), the softmax as everywhere else in the loss kernels
-      hp_softmax_c(z, k.C);
+      softmax_c(z, k.C);
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) g[c] = c < k.C ? wt * (z[c] - (c == (int)t ? 1.f : 0.f)) : 0.f;
     }
     return wt * (logf(se) - (zt - m));
   }
-  if (k.n_softmax) hp_softmax_c(z, k.C);
+  if (k.n_softmax) softmax_c(z, k.C);
   float s = 0.f;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c)
@@ -149,31 +97,25 @@ __device__ __forceinline__ float hp_pixel(const float* __restrict__ logits, cons
     const float dpt = wt * (dpw * lg - pw / pt);
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) g[c] = c < k.C ? dpt * (c == (int)t ? k.o_hit : k.o_miss) : 0.f;
-    if (k.n_softmax) hp_softmax_bwd_c(g, z, k.C);
+    if (k.n_softmax) softmax_bwd_c(g, z, k.C);
   }
   return (-wt * pw) * lg;
 }
 
-// add the digits of up to 64 keys of one wave round into the workgroup's LDS histogram
-__device__ __forceinline__ void hp_count(int* hs, int d, bool valid, int lane) {
-  const uint64_t m = hp_match_digit(d, valid);
-  if (valid && (m & hp_lanes_below(lane)) == 0) atomicAdd(&hs[d], __popcll(m));  // integer: order-independent
-}
-
 // vals[i] = v_i (and `values`, optional); with `hist` the histogram of the top byte of the keys (pass 0 of the select)
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_values_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_values_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                                       const float* __restrict__ cw, HpCfg k, int64_t N, int nblk,
                                                                       float* __restrict__ vals, float* __restrict__ values,
                                                                       int* __restrict__ hist) {
-  __shared__ int hs[HP_RADIX];
+  __shared__ int hs[RX_RADIX];
   const int tid = threadIdx.x, lane = tid & 63;
   hs[tid] = 0;
   __syncthreads();
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int64_t base = (int64_t)blk * HP_TILE;
+    const int64_t base = (int64_t)blk * RX_TILE;
 #pragma unroll 1
-    for (int j = 0; j < HP_ITEMS; ++j) {
-      const int64_t i = base + j * HP_THREADS + tid;
+    for (int j = 0; j < RX_ITEMS; ++j) {
+      const int64_t i = base + j * RX_THREADS + tid;
       const bool valid = i < N;
       float v = 0.f;
       if (valid) {
@@ -181,7 +123,7 @@ __global__ __launch_bounds__(HP_THREADS) void hardpixel_values_kernel(const floa
         vals[i] = v;
         if (values) values[i] = v;
       }
-      if (hist) hp_count(hs, (int)(hp_key(v) >> 24), valid, lane);
+      if (hist) count_digit(hs, (int)(hp_key(v) >> 24), valid, lane);
     }
   }
   if (hist) {
@@ -191,116 +133,82 @@ __global__ __launch_bounds__(HP_THREADS) void hardpixel_values_kernel(const floa
 }
 
 // pass 1..3: histogram of byte (3 - pass) over the keys whose bytes above it equal the prefix in state[0]
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_hist_kernel(const float* __restrict__ vals, int64_t N, int nblk, int pass,
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_hist_kernel(const float* __restrict__ vals, int64_t N, int nblk, int pass,
                                                                     const uint32_t* __restrict__ state, int* __restrict__ hist) {
-  __shared__ int hs[HP_RADIX];
+  __shared__ int hs[RX_RADIX];
   const int tid = threadIdx.x, lane = tid & 63;
   hs[tid] = 0;
   __syncthreads();
   const int up = 32 - 8 * pass, shift = 24 - 8 * pass;
   const uint32_t prefix = state[0] >> up;
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int64_t base = (int64_t)blk * HP_TILE;
+    const int64_t base = (int64_t)blk * RX_TILE;
 #pragma unroll
-    for (int j = 0; j < HP_ITEMS; ++j) {
-      const int64_t i = base + j * HP_THREADS + tid;
+    for (int j = 0; j < RX_ITEMS; ++j) {
+      const int64_t i = base + j * RX_THREADS + tid;
       const uint32_t key = i < N ? hp_key(vals[i]) : 0u;
       const bool valid = i < N && (key >> up) == prefix;
-      hp_count(hs, (int)((key >> shift) & 255u), valid, lane);
+      count_digit(hs, (int)((key >> shift) & 255u), valid, lane);
     }
   }
   __syncthreads();
-  if (hs[tid]) atomicAdd(&hist[pass * HP_RADIX + tid], hs[tid]);
+  if (hs[tid]) atomicAdd(&hist[pass * RX_RADIX + tid], hs[tid]);
 }
 
 // one workgroup: among the keys counted in hist[pass] the rem-th largest lies in digit d: state[0] |= d << shift, state[1] = rem
 // minus the keys in larger digits.  rem is K before pass 0.  Thread i looks at digit 255 - i: the scan runs from the top.
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_pick_kernel(const int* __restrict__ hist, int pass, uint32_t K,
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_pick_kernel(const int* __restrict__ hist, int pass, uint32_t K,
                                                                     uint32_t* __restrict__ state) {
-  __shared__ int ws[HP_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, d = HP_RADIX - 1 - tid;
-  const int cnt = hist[pass * HP_RADIX + d];
+  __shared__ int ws[RX_WAVES];
+  const int d = RX_RADIX - 1 - threadIdx.x;
+  const int cnt = hist[pass * RX_RADIX + d];
   const uint32_t rem = pass == 0 ? K : state[1], prefix = pass == 0 ? 0u : state[0];
-  int incl = hp_wave_incl_scan(cnt, lane);
-  if (lane == 63) ws[wv] = incl;
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < HP_WAVES; ++q)
-    if (q < wv) incl += ws[q];
-  const uint32_t above = (uint32_t)(incl - cnt);  // keys in larger digits
-  if (above < rem && rem <= (uint32_t)incl) {     // exactly one thread: the counts sum to >= rem
+  const int incl = block_incl_scan(cnt, ws);
+  if (bin_holds_rank(incl, cnt, rem - 1)) {  // exactly one thread: the counts sum to >= rem
     state[0] = prefix | ((uint32_t)d << (24 - 8 * pass));
-    state[1] = rem - above;
+    state[1] = rem - (uint32_t)(incl - cnt);  // minus the keys in larger digits
   }
 }
 
 // bcnt[tile] = #(key == T) in the tile
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_ties_kernel(const float* __restrict__ vals, int64_t N,
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_ties_kernel(const float* __restrict__ vals, int64_t N,
                                                                     const uint32_t* __restrict__ state, int* __restrict__ bcnt) {
-  __shared__ int ws[HP_WAVES];
-  const int blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ int ws[RX_WAVES];
+  const int blk = blockIdx.x, tid = threadIdx.x;
   const uint32_t T = state[0];
-  const int64_t base = (int64_t)blk * HP_TILE;
-  int n = 0;
+  const int64_t base = (int64_t)blk * RX_TILE;
+  bool tie[RX_ITEMS];
 #pragma unroll
-  for (int j = 0; j < HP_ITEMS; ++j) {
-    const int64_t i = base + j * HP_THREADS + tid;
-    n += __popcll(__ballot(i < N && hp_key(vals[i]) == T));
+  for (int j = 0; j < RX_ITEMS; ++j) {
+    const int64_t i = base + j * RX_THREADS + tid;
+    tie[j] = i < N && hp_key(vals[i]) == T;
   }
-  if (lane == 0) ws[wv] = n;
-  __syncthreads();
-  if (tid == 0) bcnt[blk] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+  const int n = block_count(tie, ws);
+  if (tid == 0) bcnt[blk] = n;
 }
 
 // n ints, one workgroup: exclusive scan in place.  Any n.
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_scan_kernel(int* __restrict__ row, int n) {
-  __shared__ int ws[HP_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += HP_TILE) {
-    const int i0 = base + tid * HP_ITEMS;
-    int v[HP_ITEMS], s = 0;
-#pragma unroll
-    for (int j = 0; j < HP_ITEMS; ++j) {
-      v[j] = (i0 + j < n) ? row[i0 + j] : 0;
-      s += v[j];
-    }
-    const int incl = hp_wave_incl_scan(s, lane);
-    if (lane == 63) ws[wv] = incl;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < HP_WAVES; ++q) {
-      if (q < wv) before += ws[q];
-      tot += ws[q];
-    }
-    int run = carry + before + incl - s;
-#pragma unroll
-    for (int j = 0; j < HP_ITEMS; ++j) {
-      if (i0 + j < n) row[i0 + j] = run;
-      run += v[j];
-    }
-    carry += tot;
-    __syncthreads();
-  }
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_scan_kernel(int* __restrict__ row, int n) {
+  __shared__ int ws[RX_WAVES];
+  block_rowscan(row, n, ws);
 }
 
 // the selection, the tile's sum of the selected values, dz.  `state` == nullptr: every pixel is selected (K = N).
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_apply_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_apply_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                                      const float* __restrict__ cw, HpCfg k, int64_t N,
                                                                      const float* __restrict__ vals, const uint32_t* __restrict__ state,
                                                                      const int* __restrict__ bcnt, float inv_k, float grad_scale,
                                                                      int accumulate, double* __restrict__ part, float* __restrict__ dz,
                                                                      uint8_t* __restrict__ selected) {
-  __shared__ int wc[HP_ITEMS][HP_WAVES];
-  __shared__ double wd[HP_WAVES];
+  __shared__ int wc[RX_ITEMS][RX_WAVES];
+  __shared__ double wd[RX_WAVES];
   const int blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t base = (int64_t)blk * HP_TILE;
+  const int64_t base = (int64_t)blk * RX_TILE;
   const bool all = state == nullptr;
   const uint32_t T = all ? 0u : state[0], r = all ? 0u : state[1];
 #pragma unroll
-  for (int j = 0; j < HP_ITEMS; ++j) {
-    const int64_t i = base + j * HP_THREADS + tid;
+  for (int j = 0; j < RX_ITEMS; ++j) {
+    const int64_t i = base + j * RX_THREADS + tid;
     const uint64_t em = __ballot(!all && i < N && hp_key(vals[i]) == T);
     if (lane == 0) wc[j][wv] = __popcll(em);
   }
@@ -309,14 +217,14 @@ __global__ __launch_bounds__(HP_THREADS) void hardpixel_apply_kernel(const float
   double acc = 0.0;
   // one round at a time (the pixel function is large: not unrolled); the values come from the cache the second time
 #pragma unroll 1
-  for (int j = 0; j < HP_ITEMS; ++j) {
-    const int64_t i = base + j * HP_THREADS + tid;
+  for (int j = 0; j < RX_ITEMS; ++j) {
+    const int64_t i = base + j * RX_THREADS + tid;
     const float v = i < N ? vals[i] : 0.f;
     const uint32_t key = hp_key(v);
     const uint64_t em = __ballot(!all && i < N && key == T);
-    uint32_t rank = run + (uint32_t)__popcll(em & hp_lanes_below(lane));
+    uint32_t rank = run + (uint32_t)__popcll(em & lanes_below(lane));
 #pragma unroll
-    for (int q = 0; q < HP_WAVES; ++q) {
+    for (int q = 0; q < RX_WAVES; ++q) {
       if (q < wv) rank += (uint32_t)wc[j][q];
       run += (uint32_t)wc[j][q];
     }
@@ -340,52 +248,40 @@ __global__ __launch_bounds__(HP_THREADS) void hardpixel_apply_kernel(const float
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) wd[wv] = acc;
-  __syncthreads();
-  if (tid == 0) part[blk] = (wd[0] + wd[1]) + (wd[2] + wd[3]);
+  const double sum = block_sum(acc, wd);
+  if (tid == 0) part[blk] = sum;
 }
 
 // loss = sum of the tile partials (double, fixed order) * scale
-__global__ __launch_bounds__(HP_THREADS) void hardpixel_finalize_kernel(const double* __restrict__ part, int nblk, double scale,
+__global__ __launch_bounds__(RX_THREADS) void hardpixel_finalize_kernel(const double* __restrict__ part, int nblk, double scale,
                                                                         float* __restrict__ loss) {
-  __shared__ double red[HP_THREADS];
+  __shared__ double red[RX_THREADS];
   const int tid = threadIdx.x;
   double s = 0.0;
-  for (int i = tid; i < nblk; i += HP_THREADS) s += part[i];
-  red[tid] = s;
-  __syncthreads();
-  for (int o = HP_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  if (tid == 0) *loss = (float)(red[0] * scale);
+  for (int i = tid; i < nblk; i += RX_THREADS) s += part[i];
+  const double sum = tree_sum256(s, red);
+  if (tid == 0) *loss = (float)(sum * scale);
 }
-
-inline int64_t hp_align(int64_t b) { return (b + 255) / 256 * 256; }
-inline int64_t hp_nblk(int64_t N) { return (N + HP_TILE - 1) / HP_TILE; }
 
 struct HpScratch {
   int64_t vals, hist, state, bcnt, part, bytes;
 };
 inline HpScratch hp_layout(int64_t N) {
-  const int64_t nblk = hp_nblk(N);
+  const int64_t nblk = rx_nblk(N);
   HpScratch s;
-  int64_t o = 0;
-  auto take = [&](int64_t b) { const int64_t at = o; o += hp_align(b); return at; };
-  s.vals = take(4 * N);
-  s.hist = take(4 * 4 * HP_RADIX);  // hist and state are zeroed by one memset: keep them adjacent
-  s.state = take(16);
-  s.bcnt = take(4 * nblk);
-  s.part = take(8 * nblk);
-  s.bytes = o;
+  ScratchLayout l;
+  s.vals = l.take(4 * N);
+  s.hist = l.take(4 * 4 * RX_RADIX);  // hist and state are zeroed by one memset: keep them adjacent
+  s.state = l.take(16);
+  s.bcnt = l.take(4 * nblk);
+  s.part = l.take(8 * nblk);
+  s.bytes = l.bytes;
   return s;
 }
 
 }  // namespace
 
-extern "C" int asis_hardpixel_tile(void) { return HP_TILE; }
+extern "C" int asis_hardpixel_tile(void) { return RX_TILE; }
 
 extern "C" int64_t asis_hardpixel_scratch_bytes(int64_t N) {
   if (N < 1 || N >= ((int64_t)1 << 31)) {
@@ -422,8 +318,8 @@ extern "C" int asis_hardpixel_loss(void* stream, const float* logits, const int6
   uint32_t* state = reinterpret_cast<uint32_t*>(base + L.state);
   int* bcnt = reinterpret_cast<int*>(base + L.bcnt);
   double* part = reinterpret_cast<double*>(base + L.part);
-  const int nblk = (int)hp_nblk(N);
-  const dim3 blk(HP_THREADS), hgrid(nblk < HP_HIST_BLOCKS ? nblk : HP_HIST_BLOCKS);
+  const int nblk = (int)rx_nblk(N);
+  const dim3 blk(RX_THREADS), hgrid(nblk < HP_HIST_BLOCKS ? nblk : HP_HIST_BLOCKS);
 
   HpCfg k;
   k.h = h, k.w = w, k.H = H, k.W = W, k.C = C, k.kind = kind, k.n_softmax = n_softmax;

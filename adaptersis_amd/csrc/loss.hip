@@ -13,27 +13,9 @@
 // then softmax^T twice, written at (H, W); asis_resize_bilinear_bwd gathers it back to the
 // decoder's (h, w) grid as the 16-bit operand of the dgrad / wgrad GEMMs.
 #include "asis_common.h"
-#include "bilinear_tap.h"  // MAXC, Tap, tap_ac_false, sample_logits
+#include "bilinear_tap.h"  // MAXC, Tap, tap_ac_false, sample_logits, softmax_c, softmax_bwd_c
 
 namespace {
-
-__device__ __forceinline__ void softmax_c(float* z, int C) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) m = fmaxf(m, z[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) {
-      z[c] = __expf(z[c] - m);
-      s += z[c];
-    }
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) z[c] *= inv;
-}
 
 // One generalised pass for every loss of segloss/: with x0 = resized logits, x1 = softmax(x0), x2 = softmax(x1)
 //   region term on q = x_{n_region}:  per (b, c) sums I = sum q t, Sp = sum q, St = sum t   (tp = I, fp = Sp - I, fn = St - I)
@@ -179,16 +161,6 @@ __global__ void seg_loss_finalize_kernel(const float* __restrict__ partial, int 
     *loss = (float)l;
     coef[B * C * 2] = n_ce > 0 ? (float)((double)grad_scale / ce_tot[1]) : 0.f;
   }
-}
-
-__device__ __forceinline__ void softmax_bwd_c(float* g, const float* p, int C) {  // g <- p * (g - <g, p>)
-  float dot = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) dot += g[c] * p[c];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) g[c] = p[c] * (g[c] - dot);
 }
 
 // dz[b, y, x, c] = d loss / d (resized logits), fp32 at (H, W)

@@ -26,84 +26,31 @@
 //
 // Radix width and tile.  8 bits: 256 digits = one digit per thread of a 256-thread workgroup for the histogram / offset steps,
 // 4 passes, and 4 KiB of per-wave counters (4 waves x 256) — LDS never limits occupancy.  A wave ranks 64 keys of one round
-// with 8 wave64 ballots (one per digit bit: the lanes holding my digit), popcounts of that 64-bit mask below my lane give the
-// stable rank, and the first lane of each digit bumps the wave's counter: no LDS atomics on the scatter path and no
-// same-address serialisation when the digit is nearly constant (the top byte of probabilities).  11 bits would save one pass of
-// four but needs 2048 counters per wave and 11 ballots per round, and its histogram rows (one per digit and tile) would be
-// 8 times as large as the tile's keys are worth.  Tile: 256 threads x 8 keys = 2048 keys, wave-striped (wave w owns keys
-// w*512 .. w*512+511 of the tile, round j the 64 consecutive ones from j*64: coalesced 256-byte loads, and the order of the keys
-// is wave, round, lane).  8 keys per thread keep 24 live registers of keys / payloads / ranks: 8 workgroups per CU stay resident.
+// with match_digit (radix_routines.h, which also holds the scans, the reductions and the tile constants RX_*): popcounts of
+// that 64-bit mask below my lane give the stable rank, and the first lane of each digit bumps the wave's counter: no LDS
+// atomics on the scatter path and no same-address serialisation when the digit is nearly constant (the top byte of
+// probabilities).  11 bits would save one pass of four but needs 2048 counters per wave and 11 ballots per round, and its
+// histogram rows (one per digit and tile) would be 8 times as large as the tile's keys are worth.  Tile: 256 threads x 8 keys
+// = 2048 keys, wave-striped (wave w owns keys w*512 .. w*512+511 of the tile, round j the 64 consecutive ones from j*64:
+// coalesced 256-byte loads, and the order of the keys is wave, round, lane).  8 keys per thread keep 24 live registers of keys /
+// payloads / ranks: 8 workgroups per CU stay resident.
 #include "asis_common.h"
-#include "bilinear_tap.h"  // MAXC, sample_logits
+#include "bilinear_tap.h"  // MAXC, sample_logits_at, softmax_c, softmax_bwd_c
+#include "radix_routines.h"
 
 namespace {
 
-constexpr int LV_THREADS = 256, LV_WAVES = 4, LV_ITEMS = 8, LV_TILE = LV_THREADS * LV_ITEMS, LV_RADIX = 256;
-
-// the softmax arithmetic of loss.hip's softmax_c / softmax_bwd_c (same operations in the same order: same bits)
-__device__ __forceinline__ void lv_softmax_c(float* z, int C) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) m = fmaxf(m, z[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) {
-      z[c] = __expf(z[c] - m);
-      s += z[c];
-    }
-  const float inv = 1.f / s;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) z[c] *= inv;
-}
-__device__ __forceinline__ void lv_softmax_bwd_c(float* g, const float* p, int C) {  // g <- p * (g - <g, p>)
-  float dot = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) dot += g[c] * p[c];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-    if (c < C) g[c] = p[c] * (g[c] - dot);
-}
-
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
 // position of (wave, round, lane) in the tile that starts at `base`
-__device__ __forceinline__ int64_t tile_pos(int64_t base, int wv, int j, int lane) { return base + wv * (LV_ITEMS * 64) + j * 64 + lane; }
-// the valid lanes of the wave that hold digit d (all 64 lanes call it)
-__device__ __forceinline__ uint64_t match_digit(int d, bool valid) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const bool bit = (d >> b) & 1;
-    const uint64_t bm = __ballot(bit);
-    m &= bit ? bm : ~bm;
-  }
-  return m;
-}
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
+__device__ __forceinline__ int64_t tile_pos(int64_t base, int wv, int j, int lane) { return base + wv * (RX_ITEMS * 64) + j * 64 + lane; }
 
-__global__ __launch_bounds__(LV_THREADS) void lovasz_keys_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_keys_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                                  int h, int w, int H, int W, int C, int n_softmax, int64_t N,
                                                                  uint32_t* __restrict__ key, uint32_t* __restrict__ pay,
                                                                  float* __restrict__ dbg_keys) {
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  const int64_t hw = (int64_t)H * W;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-    const int b = (int)(i / hw);
-    const int p = (int)(i - (int64_t)b * hw);
-    const int y = p / W, x = p - y * W;
     float z[MAXC];
-    sample_logits(logits + (int64_t)b * h * w * C, h, w, C, y, x, sh, sw, z);
-    if (n_softmax) lv_softmax_c(z, C);
+    sample_logits_at(logits, h, w, H, W, C, i, z);
+    if (n_softmax) softmax_c(z, C);
     const int64_t t = target[i];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c)
@@ -118,91 +65,55 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_keys_kernel(const float* __
 }
 
 // hist[(c * 256 + digit) * nblk + tile] = number of keys of the tile with that digit
-__global__ __launch_bounds__(LV_THREADS) void lovasz_hist_kernel(const uint32_t* __restrict__ key, int64_t N, int nblk, int shift,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_hist_kernel(const uint32_t* __restrict__ key, int64_t N, int nblk, int shift,
                                                                  int* __restrict__ hist) {
-  __shared__ int hs[LV_RADIX];
+  __shared__ int hs[RX_RADIX];
   const int c = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   hs[tid] = 0;
   __syncthreads();
   const uint32_t* k = key + (int64_t)c * N;
-  const int64_t base = (int64_t)blk * LV_TILE;
+  const int64_t base = (int64_t)blk * RX_TILE;
 #pragma unroll
-  for (int j = 0; j < LV_ITEMS; ++j) {
+  for (int j = 0; j < RX_ITEMS; ++j) {
     const int64_t p = tile_pos(base, wv, j, lane);
     const bool valid = p < N;
-    const int d = valid ? (int)((~k[p] >> shift) & 255u) : 0;
-    const uint64_t m = match_digit(d, valid);
-    if (valid && (m & lanes_below(lane)) == 0) atomicAdd(&hs[d], __popcll(m));  // integer: order-independent
+    count_digit(hs, valid ? (int)((~k[p] >> shift) & 255u) : 0, valid, lane);
   }
   __syncthreads();
-  hist[((int64_t)c * LV_RADIX + tid) * nblk + blk] = hs[tid];
+  hist[((int64_t)c * RX_RADIX + tid) * nblk + blk] = hs[tid];
 }
 
 // rows of n ints, one workgroup per row: exclusive scan in place, the row's sum to totals[row].  Any n.
-__global__ __launch_bounds__(LV_THREADS) void lovasz_rowscan_kernel(int* __restrict__ data, int n, int* __restrict__ totals) {
-  __shared__ int ws[LV_WAVES];
-  int* row = data + (int64_t)blockIdx.x * n;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int carry = 0;
-  for (int base = 0; base < n; base += LV_TILE) {
-    const int i0 = base + tid * LV_ITEMS;
-    int v[LV_ITEMS], s = 0;
-#pragma unroll
-    for (int j = 0; j < LV_ITEMS; ++j) {
-      v[j] = (i0 + j < n) ? row[i0 + j] : 0;
-      s += v[j];
-    }
-    const int incl = wave_incl_scan(s, lane);
-    if (lane == 63) ws[wv] = incl;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < LV_WAVES; ++q) {
-      if (q < wv) before += ws[q];
-      tot += ws[q];
-    }
-    int run = carry + before + incl - s;
-#pragma unroll
-    for (int j = 0; j < LV_ITEMS; ++j) {
-      if (i0 + j < n) row[i0 + j] = run;
-      run += v[j];
-    }
-    carry += tot;
-    __syncthreads();
-  }
-  if (tid == 0) totals[blockIdx.x] = carry;
+__global__ __launch_bounds__(RX_THREADS) void lovasz_rowscan_kernel(int* __restrict__ data, int n, int* __restrict__ totals) {
+  __shared__ int ws[RX_WAVES];
+  const int total = block_rowscan(data + (int64_t)blockIdx.x * n, n, ws);
+  if (threadIdx.x == 0) totals[blockIdx.x] = total;
 }
 
 // stable scatter of one tile by the digit at `shift`: hist holds the row-scanned counts (exclusive over the tiles of one
 // digit), dtot the 256 digit totals of the class
-__global__ __launch_bounds__(LV_THREADS) void lovasz_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ pin,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ pin,
                                                                     uint32_t* __restrict__ kout, uint32_t* __restrict__ pout,
                                                                     int64_t N, int nblk, int shift, const int* __restrict__ hist,
                                                                     const int* __restrict__ dtot) {
-  __shared__ int cnt[LV_WAVES][LV_RADIX];
-  __shared__ int ws[LV_WAVES];
+  __shared__ int cnt[RX_WAVES][RX_RADIX];
+  __shared__ int ws[RX_WAVES];
   const int c = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // first output position of digit `tid` for this tile = keys of smaller digits + same digit in earlier tiles
-  const int tot = dtot[c * LV_RADIX + tid];
-  const int incl = wave_incl_scan(tot, lane);
-  if (lane == 63) ws[wv] = incl;
+  const int tot = dtot[c * RX_RADIX + tid];
 #pragma unroll
-  for (int q = 0; q < LV_WAVES; ++q) cnt[q][tid] = 0;
-  __syncthreads();
-  int dbase = incl - tot + hist[((int64_t)c * LV_RADIX + tid) * nblk + blk];
-#pragma unroll
-  for (int q = 0; q < LV_WAVES; ++q)
-    if (q < wv) dbase += ws[q];
+  for (int q = 0; q < RX_WAVES; ++q) cnt[q][tid] = 0;
+  const int dbase = block_incl_scan(tot, ws) - tot + hist[((int64_t)c * RX_RADIX + tid) * nblk + blk];  // its barrier: cnt too
 
   const uint32_t* ki = kin + (int64_t)c * N;
   const uint32_t* pi = pin + (int64_t)c * N;
-  const int64_t base = (int64_t)blk * LV_TILE;
-  uint32_t kk[LV_ITEMS], pp[LV_ITEMS];
-  int loc[LV_ITEMS];
+  const int64_t base = (int64_t)blk * RX_TILE;
+  uint32_t kk[RX_ITEMS], pp[RX_ITEMS];
+  int loc[RX_ITEMS];
   // rank inside the wave's 512 keys: the counters cnt[wv][*] are this wave's alone (LDS operations of one wave complete in
   // program order; the fences keep the compiler from moving them across the rounds)
 #pragma unroll
-  for (int j = 0; j < LV_ITEMS; ++j) {
+  for (int j = 0; j < RX_ITEMS; ++j) {
     const int64_t p = tile_pos(base, wv, j, lane);
     const bool valid = p < N;
     kk[j] = valid ? ki[p] : 0u;
@@ -221,7 +132,7 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_scatter_kernel(const uint32
   {  // cnt[wv][digit]: count -> first output position of the wave's keys of that digit
     int run = dbase;
 #pragma unroll
-    for (int q = 0; q < LV_WAVES; ++q) {
+    for (int q = 0; q < RX_WAVES; ++q) {
       const int t = cnt[q][tid];
       cnt[q][tid] = run;
       run += t;
@@ -231,7 +142,7 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_scatter_kernel(const uint32
   uint32_t* ko = kout + (int64_t)c * N;
   uint32_t* po = pout + (int64_t)c * N;
 #pragma unroll
-  for (int j = 0; j < LV_ITEMS; ++j) {
+  for (int j = 0; j < RX_ITEMS; ++j) {
     const int64_t p = tile_pos(base, wv, j, lane);
     if (p < N) {
       const int d = (int)((~kk[j] >> shift) & 255u);
@@ -243,40 +154,38 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_scatter_kernel(const uint32
 }
 
 // ftot[c * nblk + tile] = class pixels among the tile's sorted positions
-__global__ __launch_bounds__(LV_THREADS) void lovasz_flagtot_kernel(const uint32_t* __restrict__ pay, int64_t N, int nblk,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_flagtot_kernel(const uint32_t* __restrict__ pay, int64_t N, int nblk,
                                                                     int* __restrict__ ftot) {
-  __shared__ int ws[LV_WAVES];
+  __shared__ int ws[RX_WAVES];
   const int c = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t* pi = pay + (int64_t)c * N;
-  const int64_t base = (int64_t)blk * LV_TILE;
-  int n = 0;
+  const int64_t base = (int64_t)blk * RX_TILE;
+  bool f[RX_ITEMS];
 #pragma unroll
-  for (int j = 0; j < LV_ITEMS; ++j) {
+  for (int j = 0; j < RX_ITEMS; ++j) {
     const int64_t p = tile_pos(base, wv, j, lane);
-    const bool f = p < N && (pi[p] >> 31);
-    n += __popcll(__ballot(f));
+    f[j] = p < N && (pi[p] >> 31);
   }
-  if (lane == 0) ws[wv] = n;
-  __syncthreads();
-  if (tid == 0) ftot[(int64_t)c * nblk + blk] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+  const int n = block_count(f, ws);
+  if (tid == 0) ftot[(int64_t)c * nblk + blk] = n;
 }
 
 // per sorted position: f_k, g_k; grad[pixel * C + c] = s g_k; part[c * nblk + tile] = sum of e g over the tile (double)
-__global__ __launch_bounds__(LV_THREADS) void lovasz_grad_kernel(const uint32_t* __restrict__ key, const uint32_t* __restrict__ pay,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_grad_kernel(const uint32_t* __restrict__ key, const uint32_t* __restrict__ pay,
                                                                  int64_t N, int nblk, int C, const int* __restrict__ ftot,
                                                                  const int* __restrict__ gtot, float* __restrict__ grad,
                                                                  double* __restrict__ part, int32_t* __restrict__ dbg_order) {
-  __shared__ int ws[LV_WAVES];
-  __shared__ double wd[LV_WAVES];
+  __shared__ int ws[RX_WAVES];
+  __shared__ double wd[RX_WAVES];
   const int c = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t* ki = key + (int64_t)c * N;
   const uint32_t* pi = pay + (int64_t)c * N;
-  const int64_t base = (int64_t)blk * LV_TILE;
-  uint32_t kk[LV_ITEMS], pp[LV_ITEMS];
-  uint64_t fm[LV_ITEMS];
+  const int64_t base = (int64_t)blk * RX_TILE;
+  uint32_t kk[RX_ITEMS], pp[RX_ITEMS];
+  uint64_t fm[RX_ITEMS];
   int wt = 0;
 #pragma unroll
-  for (int j = 0; j < LV_ITEMS; ++j) {
+  for (int j = 0; j < RX_ITEMS; ++j) {
     const int64_t p = tile_pos(base, wv, j, lane);
     const bool valid = p < N;
     kk[j] = valid ? ki[p] : 0u;
@@ -288,13 +197,13 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_grad_kernel(const uint32_t*
   __syncthreads();
   int64_t run = ftot[(int64_t)c * nblk + blk];  // class pixels before this wave's first key
 #pragma unroll
-  for (int q = 0; q < LV_WAVES; ++q)
+  for (int q = 0; q < RX_WAVES; ++q)
     if (q < wv) run += ws[q];
   const int64_t G = gtot[c];
   const uint64_t upto = lanes_below(lane) | (1ull << lane);
   double acc = 0.0;
 #pragma unroll
-  for (int j = 0; j < LV_ITEMS; ++j) {
+  for (int j = 0; j < RX_ITEMS; ++j) {
     const int64_t k = tile_pos(base, wv, j, lane);
     if (k < N) {
       const bool f = pp[j] >> 31;
@@ -312,29 +221,21 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_grad_kernel(const uint32_t*
     }
     run += __popcll(fm[j]);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) wd[wv] = acc;
-  __syncthreads();
-  if (tid == 0) part[(int64_t)c * nblk + blk] = (wd[0] + wd[1]) + (wd[2] + wd[3]);
+  const double sum = block_sum(acc, wd);
+  if (tid == 0) part[(int64_t)c * nblk + blk] = sum;
 }
 
 // per_class[c] = sum of the class's tile partials (double, fixed order); loss = mean (reduction 0) or sum (1, 2) of them
-__global__ __launch_bounds__(LV_THREADS) void lovasz_finalize_kernel(const double* __restrict__ part, int nblk, int C, int reduction,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_finalize_kernel(const double* __restrict__ part, int nblk, int C, int reduction,
                                                                      float* __restrict__ per_class, float* __restrict__ loss) {
-  __shared__ double red[LV_THREADS];
+  __shared__ double red[RX_THREADS];
   __shared__ double cls[MAXC];
   const int tid = threadIdx.x;
   for (int c = 0; c < C; ++c) {
     double s = 0.0;
-    for (int i = tid; i < nblk; i += LV_THREADS) s += part[(int64_t)c * nblk + i];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = LV_THREADS / 2; o > 0; o >>= 1) {
-      if (tid < o) red[tid] += red[tid + o];
-      __syncthreads();
-    }
-    if (tid == 0) cls[c] = red[0];
+    for (int i = tid; i < nblk; i += RX_THREADS) s += part[(int64_t)c * nblk + i];
+    const double sum = tree_sum256(s, red);
+    if (tid == 0) cls[c] = sum;
     __syncthreads();
   }
   if (tid == 0) {
@@ -348,23 +249,18 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_finalize_kernel(const doubl
 }
 
 // dz[b, y, x, c] (=, or += with `accumulate`) grad_scale * d loss / d (resized logits)
-__global__ __launch_bounds__(LV_THREADS) void lovasz_dz_kernel(const float* __restrict__ logits, const float* __restrict__ grad, int h,
+__global__ __launch_bounds__(RX_THREADS) void lovasz_dz_kernel(const float* __restrict__ logits, const float* __restrict__ grad, int h,
                                                                int w, int H, int W, int C, int n_softmax, int64_t N, float rfac,
                                                                float grad_scale, int accumulate, float* __restrict__ dz) {
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  const int64_t hw = (int64_t)H * W;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
     float g[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) g[c] = c < C ? grad[i * C + c] * rfac : 0.f;
     if (n_softmax) {
-      const int b = (int)(i / hw);
-      const int p = (int)(i - (int64_t)b * hw);
-      const int y = p / W, x = p - y * W;
       float q[MAXC];
-      sample_logits(logits + (int64_t)b * h * w * C, h, w, C, y, x, sh, sw, q);
-      lv_softmax_c(q, C);
-      lv_softmax_bwd_c(g, q, C);
+      sample_logits_at(logits, h, w, H, W, C, i, q);
+      softmax_c(q, C);
+      softmax_bwd_c(g, q, C);
     }
 #pragma unroll
     for (int c = 0; c < MAXC; ++c)
@@ -375,34 +271,30 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_dz_kernel(const float* __re
   }
 }
 
-inline int64_t lv_align(int64_t b) { return (b + 255) / 256 * 256; }
-inline int64_t lv_nblk(int64_t N) { return (N + LV_TILE - 1) / LV_TILE; }
-
 struct LvScratch {
   int64_t key[2], pay[2], hist, dtot, ftot, gtot, part, grad, bytes;
 };
 inline LvScratch lv_layout(int64_t N, int C) {
-  const int64_t nblk = lv_nblk(N);
+  const int64_t nblk = rx_nblk(N);
   LvScratch s;
-  int64_t o = 0;
-  auto take = [&](int64_t b) { const int64_t at = o; o += lv_align(b); return at; };
-  s.key[0] = take(4 * N * C);
-  s.key[1] = take(4 * N * C);
-  s.pay[0] = take(4 * N * C);
-  s.pay[1] = take(4 * N * C);
-  s.hist = take(4 * (int64_t)C * LV_RADIX * nblk);
-  s.dtot = take(4 * (int64_t)C * LV_RADIX);
-  s.ftot = take(4 * (int64_t)C * nblk);
-  s.gtot = take(4 * (int64_t)C);
-  s.part = take(8 * (int64_t)C * nblk);
-  s.grad = take(4 * N * C);
-  s.bytes = o;
+  ScratchLayout l;
+  s.key[0] = l.take(4 * N * C);
+  s.key[1] = l.take(4 * N * C);
+  s.pay[0] = l.take(4 * N * C);
+  s.pay[1] = l.take(4 * N * C);
+  s.hist = l.take(4 * (int64_t)C * RX_RADIX * nblk);
+  s.dtot = l.take(4 * (int64_t)C * RX_RADIX);
+  s.ftot = l.take(4 * (int64_t)C * nblk);
+  s.gtot = l.take(4 * (int64_t)C);
+  s.part = l.take(8 * (int64_t)C * nblk);
+  s.grad = l.take(4 * N * C);
+  s.bytes = l.bytes;
   return s;
 }
 
 }  // namespace
 
-extern "C" int asis_lovasz_tile(void) { return LV_TILE; }
+extern "C" int asis_lovasz_tile(void) { return RX_TILE; }
 
 extern "C" int64_t asis_lovasz_scratch_bytes(int64_t N, int C) {
   if (N < 1 || N >= ((int64_t)1 << 31) || C < 1 || C > MAXC) {
@@ -435,15 +327,15 @@ extern "C" int asis_lovasz_softmax(void* stream, const float* logits, const int6
   int* gtot = reinterpret_cast<int*>(base + L.gtot);
   double* part = reinterpret_cast<double*>(base + L.part);
   float* grad = reinterpret_cast<float*>(base + L.grad);
-  const int nblk = (int)lv_nblk(N);
-  const dim3 tiles(nblk, C), blk(LV_THREADS);
-  const int pgrid = asis_grid(N, LV_THREADS, 8192);
+  const int nblk = (int)rx_nblk(N);
+  const dim3 tiles(nblk, C), blk(RX_THREADS);
+  const int pgrid = asis_grid(N, RX_THREADS, 8192);
 
   hipLaunchKernelGGL(lovasz_keys_kernel, dim3(pgrid), blk, 0, s, logits, target, h, w, H, W, C, n_softmax, N, key[0], pay[0], keys);
   for (int pass = 0; pass < 4; ++pass) {  // four passes: the sorted order ends in buffer 0
     const int in = pass & 1, out = in ^ 1, shift = 8 * pass;
     hipLaunchKernelGGL(lovasz_hist_kernel, tiles, blk, 0, s, key[in], N, nblk, shift, hist);
-    hipLaunchKernelGGL(lovasz_rowscan_kernel, dim3(C * LV_RADIX), blk, 0, s, hist, nblk, dtot);
+    hipLaunchKernelGGL(lovasz_rowscan_kernel, dim3(C * RX_RADIX), blk, 0, s, hist, nblk, dtot);
     hipLaunchKernelGGL(lovasz_scatter_kernel, tiles, blk, 0, s, key[in], pay[in], key[out], pay[out], N, nblk, shift, hist, dtot);
   }
   hipLaunchKernelGGL(lovasz_flagtot_kernel, tiles, blk, 0, s, pay[0], N, nblk, ftot);

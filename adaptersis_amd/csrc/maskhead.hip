@@ -12,12 +12,6 @@ namespace {
 
 constexpr int MAXC = 16;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // class rows: chat[b, k, :] = x[row] / ||x[row]||, inv_c[b*C + k] = 1 / ||x[row]||
 __global__ __launch_bounds__(256) void cls_l2norm_kernel(const float* __restrict__ x, float* __restrict__ chat,
                                                          float* __restrict__ inv_c, int B, int N, int C, int D) {

@@ -34,6 +34,7 @@
 // = 70.6 MB per frame at 1080 x 1920, C = 8 (847 MB for a batch of 12, 1.6 GiB at C = 16: hence the chunking, which keeps g
 // under 512 MiB whenever one class of one frame fits).
 #include "asis_common.h"
+#include "radix_routines.h"  // block_incl_scan, bin_holds_rank (pct_pick)
 
 namespace {
 
@@ -295,8 +296,8 @@ __global__ __launch_bounds__(256) void pct_fill_kernel(const uint8_t* __restrict
 __global__ __launch_bounds__(256) void pct_pick_kernel(const unsigned long long* __restrict__ ints, int C, int c0, int nc, int ncol,
                                                        int P, PctQ pq, int pass, const uint32_t* __restrict__ hist0,
                                                        uint32_t* __restrict__ hist, PctState* __restrict__ state) {
-  __shared__ uint32_t ws[4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ int ws[RX_WAVES];
+  const int tid = threadIdx.x;
   const int p = blockIdx.x / 3, set = blockIdx.x % 3, k = blockIdx.y, b = blockIdx.z;
   const int64_t slot = pct_slot(b, k, p, set, nc, P);
   uint32_t prefix = 0, rank, flags, cnt;
@@ -320,22 +321,12 @@ __global__ __launch_bounds__(256) void pct_pick_kernel(const unsigned long long*
     cnt = hist[slot * 256 + tid];
     hist[slot * 256 + tid] = 0;                             // for the next pass (only this block reads these bins)
   }
-  uint32_t incl = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += u;
-  }
-  if (lane == 63) ws[wv] = incl;
-  __syncthreads();                                          // also: every read of state[slot] is before the one write below
-#pragma unroll
-  for (int w = 0; w < 4; ++w)
-    if (w < wv) incl += ws[w];
-  const uint32_t below = incl - cnt;
-  if (below <= rank && rank < incl) {                       // exactly one thread: the bins hold more than `rank` keys
+  // a slot holds fewer than 2^30 keys: int.  Its barrier also puts every read of state[slot] before the one write below
+  const uint32_t incl = (uint32_t)block_incl_scan((int)cnt, ws);
+  if (bin_holds_rank(incl, cnt, rank)) {                    // exactly one thread: the bins hold more than `rank` keys
     PctState st;
     st.prefix = prefix | ((uint32_t)tid << (24 - 8 * pass));
-    st.k = rank - below;
+    st.k = rank - (incl - cnt);
     st.flags = flags;
     if (pass == 3 && st.k + ((flags & PCT_DHI) ? 1u : 0u) >= cnt) st.flags |= PCT_NEED;   // v[hi] lies above the ties of v[lo]
     st.above = PCT_NONE;

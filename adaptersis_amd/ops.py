@@ -1649,6 +1649,30 @@ def reduce_rows(partial: torch.Tensor, scale: float = 1.0, out: Optional[torch.T
 LOVASZ_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
 
 
+def _pixel_loss_args(op: str, logits: torch.Tensor, target: torch.Tensor, need, dz, scratch):
+    """The argument checks and buffers ``lovasz_softmax`` and ``hardpixel_loss`` share: logits NHWC against an int64 target,
+    the scratch (``need(N, C)`` bytes; checked, or a fresh one) and dz (checked and added into, or a fresh one).
+    -> (B, h, w, H, W, C, N, scratch, dz, accumulate)"""
+    if logits.dim() != 4 or target.dim() != 3:
+        raise ValueError(f"{op}: logits must be NHWC [B,h,w,C] and target [B,H,W]")
+    B, h, w, Cc = logits.shape
+    H, W = target.shape[-2:]
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] != B:
+        raise ValueError(f"{op}: target must be contiguous int64 [B,H,W]")
+    N = B * H * W
+    nbytes = need(N, Cc)
+    if scratch is None:
+        scratch = torch.empty((nbytes,), device=logits.device, dtype=torch.uint8)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < nbytes:
+        raise ValueError(f"{op}: scratch must be a contiguous uint8 buffer of at least {nbytes} bytes")
+    accumulate = dz is not None
+    if dz is None:
+        dz = torch.empty((B, H, W, Cc), device=logits.device, dtype=torch.float32)
+    elif tuple(dz.shape) != (B, H, W, Cc) or dz.dtype != torch.float32 or not dz.is_contiguous():
+        raise ValueError(f"{op}: dz must be contiguous float32 [B,H,W,C]")
+    return B, h, w, H, W, Cc, N, scratch, dz, accumulate
+
+
 def lovasz_scratch_bytes(n_pixels: int, num_classes: int) -> int:
     """bytes of caller-owned scratch ``asis_lovasz_softmax`` needs for ``n_pixels`` = B*H*W (needs no GPU)."""
     nb = lib().asis_lovasz_scratch_bytes(int(n_pixels), int(num_classes))
@@ -1667,32 +1691,17 @@ def lovasz_softmax(logits: torch.Tensor, target: torch.Tensor, n_softmax: int = 
     in pixel order) and order int32 [C,N] (pixel index at each sorted position: descending error, ties by ascending index).
     ``scratch``: a uint8 buffer of at least ``lovasz_scratch_bytes(B*H*W, C)`` to reuse between calls (default: a fresh one)."""
     _dev(logits, target, dz, scratch)
-    if logits.dim() != 4 or target.dim() != 3:
-        raise ValueError("lovasz_softmax: logits must be NHWC [B,h,w,C] and target [B,H,W]")
-    B, h, w, Cc = logits.shape
-    H, W = target.shape[-2:]
-    if target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] != B:
-        raise ValueError("lovasz_softmax: target must be contiguous int64 [B,H,W]")
     if reduction not in LOVASZ_REDUCTIONS:
         raise ValueError(f"lovasz_softmax: reduction must be one of {sorted(LOVASZ_REDUCTIONS)}")
-    N = B * H * W
-    need = lovasz_scratch_bytes(N, Cc)
-    if scratch is None:
-        scratch = torch.empty((need,), device=logits.device, dtype=torch.uint8)
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
-        raise ValueError(f"lovasz_softmax: scratch must be a contiguous uint8 buffer of at least {need} bytes")
-    accumulate = dz is not None
-    if dz is None:
-        dz = torch.empty((B, H, W, Cc), device=logits.device, dtype=torch.float32)
-    elif tuple(dz.shape) != (B, H, W, Cc):
-        raise ValueError("lovasz_softmax: dz must be float32 [B,H,W,C]")
+    B, h, w, H, W, Cc, N, scratch, dz, accumulate = _pixel_loss_args("lovasz_softmax", logits, target, lovasz_scratch_bytes, dz,
+                                                                     scratch)
     loss = torch.empty((1,), device=logits.device, dtype=torch.float32)
     per_class = torch.empty((Cc,), device=logits.device, dtype=torch.float32)
     keys = torch.empty((Cc, N), device=logits.device, dtype=torch.float32) if return_order else None
     order = torch.empty((Cc, N), device=logits.device, dtype=torch.int32) if return_order else None
     check(lib().asis_lovasz_softmax(_stream(), _f32c(logits).data_ptr(), target.data_ptr(), B, h, w, H, W, Cc, int(n_softmax),
                                     LOVASZ_REDUCTIONS[reduction], float(grad_scale), int(accumulate), scratch.data_ptr(),
-                                    loss.data_ptr(), per_class.data_ptr(), _f32c(dz).data_ptr(), _p(keys), _p(order)),
+                                    loss.data_ptr(), per_class.data_ptr(), dz.data_ptr(), _p(keys), _p(order)),
           "asis_lovasz_softmax")
     return (loss, per_class, dz, keys, order) if return_order else (loss, per_class, dz)
 
@@ -1721,27 +1730,12 @@ def hardpixel_loss(logits: torch.Tensor, target: torch.Tensor, kind: int, K: int
     to the lower pixel index.  ``scratch``: a uint8 buffer of at least ``hardpixel_scratch_bytes(B*H*W)`` to reuse between calls
     (default: a fresh one).  No host sync."""
     _dev(logits, target, class_weight, dz, scratch)
-    if logits.dim() != 4 or target.dim() != 3:
-        raise ValueError("hardpixel_loss: logits must be NHWC [B,h,w,C] and target [B,H,W]")
-    B, h, w, Cc = logits.shape
-    H, W = target.shape[-2:]
-    if target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] != B:
-        raise ValueError("hardpixel_loss: target must be contiguous int64 [B,H,W]")
+    B, h, w, H, W, Cc, N, scratch, dz, accumulate = _pixel_loss_args("hardpixel_loss", logits, target,
+                                                                     lambda n, c: hardpixel_scratch_bytes(n), dz, scratch)
     if class_weight is not None and (class_weight.numel() != Cc or class_weight.dtype != torch.float32):
         raise ValueError("hardpixel_loss: class_weight must be float32 [C]")
-    N = B * H * W
     if not 1 <= int(K) <= N:
         raise ValueError(f"hardpixel_loss: K={K} must be in 1..B*H*W={N}")
-    need = hardpixel_scratch_bytes(N)
-    if scratch is None:
-        scratch = torch.empty((need,), device=logits.device, dtype=torch.uint8)
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
-        raise ValueError(f"hardpixel_loss: scratch must be a contiguous uint8 buffer of at least {need} bytes")
-    accumulate = dz is not None
-    if dz is None:
-        dz = torch.empty((B, H, W, Cc), device=logits.device, dtype=torch.float32)
-    elif tuple(dz.shape) != (B, H, W, Cc) or dz.dtype != torch.float32 or not dz.is_contiguous():
-        raise ValueError("hardpixel_loss: dz must be contiguous float32 [B,H,W,C]")
     loss = torch.empty((1,), device=logits.device, dtype=torch.float32)
     values = torch.empty((N,), device=logits.device, dtype=torch.float32) if return_selection else None
     selected = torch.empty((N,), device=logits.device, dtype=torch.uint8) if return_selection else None

@@ -37,7 +37,8 @@ MEASURE lines: values 0.26 (cross entropy, identity resize), loss 0.47, dz 0.22 
 select.loss 0.43; golden losses 0.07 and gradients 0.22 (focal, where the reference's own float32 error Y is most of the bound),
 golden ops loss 0.004 / dz 0.03, k = 100 against CrossentropyND 0.000 (equal to the last bit here), engine loss 0.002 (the
 dc_and_topk bound is the worst-case chain of 224^2 float32 adds and far above what either side does).  All 70 exact selections hold
-(10 key sets x 7 values of K; high_byte: 122 distinct values over both signs).  46 cases, 2.3 s of pytest time."""
+(10 key sets x 7 values of K; high_byte: 122 distinct values over both signs).  46 cases, 2.3 s of pytest time.
+test_more_tiles_than_one_scan_pass (4.2 M pixels, 3 values of K, one CPU sort) came later: select.loss 0.21, about 1 s."""
 import json
 import math
 
@@ -237,6 +238,39 @@ def test_sizes_around_the_tile(dev, N, C):
     for K in sorted({1, max(1, N // 10), max(1, N - 1), N}):
         _check(("sizes", N, C, K), q, lab, FOCAL, K, dev, n_softmax=0, gamma=2.0, smooth=0.0)
         _check(("sizes.ce", N, C, K), q * 8.0, lab, CE, K, dev)
+
+
+def test_more_tiles_than_one_scan_pass(dev):
+    """WG + 2 tiles: the scan over the tiles' tie counts takes WG entries a pass (RX_TILE of csrc/radix_routines.h), so its carry
+    runs, and so does the stride loop of the histogram passes (more tiles than their 1024 workgroups).  1024 distinct crafted
+    values, about 4100 ties each, spread over all tiles; K puts the boundary among the ties of the value T at 10 %."""
+    H, Wd = WG + 3, WG - 1
+    N = H * Wd
+    assert -(-N // WG) == WG + 2
+    gen = torch.Generator().manual_seed(5)
+    keys = (torch.randint(0, 1024, (N,), generator=gen) + 32).float()
+    T = float(torch.sort(keys, descending=True).values[int(N * 10 / 100) - 1])
+    if int((keys[WG * WG:] == T).sum()) < 2:   # the last two ties must lie behind the scan's first pass
+        keys[-2:] = T
+    logits, labels, w = _crafted(keys, torch.zeros(N, dtype=torch.int64))
+    lg, tg, wd = logits.view(1, H, Wd, 3).to(dev), labels.view(1, H, Wd).to(dev), w.to(dev)
+    order = torch.sort(keys, descending=True, stable=True).indices   # R.stable_topk for every K below from one sort
+    above, ties = int((keys > T).sum()), int((keys == T).sum())
+    tie_at = (keys == T).nonzero().view(-1)
+    scratch = torch.empty(ops.hardpixel_scratch_bytes(N), device=dev, dtype=torch.uint8)
+    for K in (above + ties - 1, above + 1, above + ties // 2):
+        want = torch.zeros(N, dtype=torch.bool)
+        want[order[:K]] = True
+        if K == above + ties - 1:   # the last selected tie is in a tile of the second pass and one unselected tie follows it
+            assert bool(want[tie_at[:-1]].all()) and not bool(want[tie_at[-1]]) and int(tie_at[-2]) // WG >= WG
+        loss, dz, values, selected = ops.hardpixel_loss(lg, tg, CE, K, class_weight=wd, scratch=scratch, return_selection=True)
+        values, selected = values.cpu(), selected.cpu().bool()
+        assert torch.equal(values.view(torch.int32), keys.view(torch.int32)), K
+        nbad = int((selected != want).sum())
+        print(f"MEASURE select big K={K}: above {above} ties {ties} selected {int(selected.sum())} differing {nbad}")
+        assert int(selected.sum()) == K and nbad == 0, K
+        vs = values.double()[selected]
+        assert _measure("select.loss", ("big", K), abs(float(loss) - float(vs.sum()) / K), 2 * U * float(vs.abs().sum()) / K)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

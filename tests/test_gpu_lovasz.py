@@ -49,7 +49,7 @@ from tests.conftest import load_golden
 pytestmark = pytest.mark.gpu
 U = R.ULP24
 TILE = _lib.lib().asis_lovasz_tile()
-SCAN_CHUNK = TILE   # entries one pass of the row-scan workgroup handles (LV_TILE of csrc/lovasz.hip: 256 threads x 8)
+SCAN_CHUNK = TILE   # entries one pass of the row-scan workgroup handles (RX_TILE of csrc/radix_routines.h: 256 threads x 8)
 
 
 def _measure(name, case, err, bound):
