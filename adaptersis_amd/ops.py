@@ -2146,6 +2146,35 @@ def _predict_outputs(op: str, B: int, Cc: int, size, dev, encode, frames, palett
     return H, W, enc, mask, pal, alp, overlay, lut, counts
 
 
+def _predict_result(mask, conf, overlay, counts):
+    """-> mask, or (mask[, confidence][, overlay][, counts]): what was asked for."""
+    out = tuple(t for t in (mask, conf, overlay, counts) if t is not None)
+    return mask if len(out) == 1 else out
+
+
+def _predict_maps(op: str, noun: str, max_count: int, logits):
+    """The list of logit maps of ``predict_mask_views`` / ``predict_mask_tiles`` (``noun`` = "views" / "tiles", at most ``max_count``
+    of them), checked -> (K, B, C, device, ptrs, hs, ws): the last three are the ctypes arrays of the ABI."""
+    import ctypes
+    if torch.is_tensor(logits) or not isinstance(logits, (list, tuple)):
+        raise ValueError(f"{op}: logits must be a list of 1..{max_count} NHWC tensors, got {type(logits).__name__}")
+    K = len(logits)
+    if not 1 <= K <= max_count:
+        raise ValueError(f"{op}: logits holds {K} {noun}, supported 1..{max_count}")
+    for k, v in enumerate(logits):
+        if not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.float32 or not v.is_contiguous():
+            raise ValueError(f"{op}: logits[{k}] must be a contiguous float32 NHWC tensor [B,h,w,C]")
+        if v.shape[0] != logits[0].shape[0] or v.shape[3] != logits[0].shape[3]:
+            raise ValueError(f"{op}: logits[{k}] is {list(v.shape)}, logits[0] {list(logits[0].shape)}: every {noun[:-1]} has the same "
+                             "B and C")
+        if v.device != logits[0].device:
+            raise ValueError(f"{op}: logits[{k}] on {v.device}, logits[0] on {logits[0].device}")
+    ptrs = (ctypes.c_void_p * K)(*[v.data_ptr() for v in logits])
+    hs = (ctypes.c_int * K)(*[int(v.shape[1]) for v in logits])
+    ws = (ctypes.c_int * K)(*[int(v.shape[2]) for v in logits])
+    return K, int(logits[0].shape[0]), int(logits[0].shape[3]), logits[0].device, ptrs, hs, ws
+
+
 def predict_mask(logits: torch.Tensor, size, encode=None, *, frames: Optional[torch.Tensor] = None, palette=None, alpha=None,
                  target: Optional[torch.Tensor] = None, lut=None):
     """Native-size masks from the decoder's logits in one pass (csrc/predict.hip): fp32 NHWC [B,h,w,C] -> uint8 [B,H,W] =
@@ -2165,8 +2194,7 @@ def predict_mask(logits: torch.Tensor, size, encode=None, *, frames: Optional[to
                                                                        palette, alpha, target, lut)
     check(lib().asis_predict_mask(_stream(), logits.data_ptr(), B, h, w, Cc, H, W, enc.data_ptr(), mask.data_ptr(), _p(frames),
                                   _p(pal), _p(alp), _p(overlay), _p(target), _p(lut), _p(counts)), "asis_predict_mask")
-    out = (mask,) + ((overlay,) if overlay is not None else ()) + ((counts,) if counts is not None else ())
-    return mask if len(out) == 1 else out
+    return _predict_result(mask, None, overlay, counts)
 
 
 PREDICT_MAX_VIEWS = 8
@@ -2184,38 +2212,19 @@ def predict_mask_views(logits, size, encode=None, *, flips=None, confidence: boo
     -> mask, or (mask[, confidence][, overlay][, counts])."""
     import ctypes
     op = "predict_mask_views"
-    if torch.is_tensor(logits) or not isinstance(logits, (list, tuple)):
-        raise ValueError(f"{op}: logits must be a list of 1..{PREDICT_MAX_VIEWS} NHWC tensors, got {type(logits).__name__}")
-    K = len(logits)
-    if not 1 <= K <= PREDICT_MAX_VIEWS:
-        raise ValueError(f"{op}: logits holds {K} views, supported 1..{PREDICT_MAX_VIEWS}")
+    K, B, Cc, dev, ptrs, hs, ws = _predict_maps(op, "views", PREDICT_MAX_VIEWS, logits)
     flips = [False] * K if flips is None else [bool(f) for f in flips]
     if len(flips) != K:
         raise ValueError(f"{op}: flips has {len(flips)} entries for {K} views in logits")
-    for k, v in enumerate(logits):
-        if not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.float32 or not v.is_contiguous():
-            raise ValueError(f"{op}: logits[{k}] must be a contiguous float32 NHWC tensor [B,h,w,C]")
-        if v.shape[0] != logits[0].shape[0] or v.shape[3] != logits[0].shape[3]:
-            raise ValueError(f"{op}: logits[{k}] is {list(v.shape)}, logits[0] {list(logits[0].shape)}: every view has the same "
-                             "B and C")
-        if v.device != logits[0].device:
-            raise ValueError(f"{op}: logits[{k}] on {v.device}, logits[0] on {logits[0].device}")
     _dev(logits[0], frames, target)
-    B, Cc = int(logits[0].shape[0]), int(logits[0].shape[3])
-    dev = logits[0].device
     H, W, enc, mask, pal, alp, overlay, lut, counts = _predict_outputs(op, B, Cc, size, dev, encode, frames, palette, alpha, target,
                                                                        lut)
     conf = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if confidence else None
-    ptrs = (ctypes.c_void_p * K)(*[v.data_ptr() for v in logits])
-    hs = (ctypes.c_int * K)(*[int(v.shape[1]) for v in logits])
-    ws = (ctypes.c_int * K)(*[int(v.shape[2]) for v in logits])
     fl = (ctypes.c_int * K)(*[int(f) for f in flips])
     check(lib().asis_predict_mask_views(_stream(), ptrs, hs, ws, fl, K, B, Cc, H, W, enc.data_ptr(), mask.data_ptr(), _p(conf),
                                         _p(frames), _p(pal), _p(alp), _p(overlay), _p(target), _p(lut), _p(counts)),
           "asis_predict_mask_views")
-    out = ((mask,) + ((conf,) if conf is not None else ()) + ((overlay,) if overlay is not None else ())
-           + ((counts,) if counts is not None else ()))
-    return mask if len(out) == 1 else out
+    return _predict_result(mask, conf, overlay, counts)
 
 
 PREDICT_MAX_TILES = 32
@@ -2240,11 +2249,7 @@ def predict_mask_tiles(logits, tiles, work, size, encode=None, *, blend: str = "
     -> mask, or (mask[, confidence][, overlay][, counts])."""
     import ctypes
     op = "predict_mask_tiles"
-    if torch.is_tensor(logits) or not isinstance(logits, (list, tuple)):
-        raise ValueError(f"{op}: logits must be a list of 1..{PREDICT_MAX_TILES} NHWC tensors, got {type(logits).__name__}")
-    K = len(logits)
-    if not 1 <= K <= PREDICT_MAX_TILES:
-        raise ValueError(f"{op}: logits holds {K} tiles, supported 1..{PREDICT_MAX_TILES}")
+    K, B, Cc, dev, ptrs, hs, ws = _predict_maps(op, "tiles", PREDICT_MAX_TILES, logits)
     tiles = list(tiles)
     if len(tiles) != K:
         raise ValueError(f"{op}: tiles has {len(tiles)} entries for {K} maps in logits")
@@ -2277,31 +2282,16 @@ def predict_mask_tiles(logits, tiles, work, size, encode=None, *, blend: str = "
     ramp = float(ramp)
     if not ramp >= 1.0:
         raise ValueError(f"{op}: ramp must be at least 1 working pixel, got {ramp!r}")
-    for k, v in enumerate(logits):
-        if not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.float32 or not v.is_contiguous():
-            raise ValueError(f"{op}: logits[{k}] must be a contiguous float32 NHWC tensor [B,h,w,C]")
-        if v.shape[0] != logits[0].shape[0] or v.shape[3] != logits[0].shape[3]:
-            raise ValueError(f"{op}: logits[{k}] is {list(v.shape)}, logits[0] {list(logits[0].shape)}: every tile has the same "
-                             "B and C")
-        if v.device != logits[0].device:
-            raise ValueError(f"{op}: logits[{k}] on {v.device}, logits[0] on {logits[0].device}")
     _dev(logits[0], frames, target)
-    B, Cc = int(logits[0].shape[0]), int(logits[0].shape[3])
-    dev = logits[0].device
     H, W, enc, mask, pal, alp, overlay, lut, counts = _predict_outputs(op, B, Cc, size, dev, encode, frames, palette, alpha, target,
                                                                        lut)
     conf = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if confidence else None
-    ptrs = (ctypes.c_void_p * K)(*[v.data_ptr() for v in logits])
-    hs = (ctypes.c_int * K)(*[int(v.shape[1]) for v in logits])
-    ws = (ctypes.c_int * K)(*[int(v.shape[2]) for v in logits])
     rc = (ctypes.c_int * (4 * K))(*rects)
     fl = (ctypes.c_int * K)(*[int(f) for f in flips])
     check(lib().asis_predict_mask_tiles(_stream(), ptrs, hs, ws, rc, fl, K, Lh, Lw, PREDICT_BLENDS.index(blend), ramp, B, Cc, H, W,
                                         enc.data_ptr(), mask.data_ptr(), _p(conf), _p(frames), _p(pal), _p(alp), _p(overlay),
                                         _p(target), _p(lut), _p(counts)), "asis_predict_mask_tiles")
-    out = ((mask,) + ((conf,) if conf is not None else ()) + ((overlay,) if overlay is not None else ())
-           + ((counts,) if counts is not None else ()))
-    return mask if len(out) == 1 else out
+    return _predict_result(mask, conf, overlay, counts)
 
 
 SURFACE_MAX_TOLERANCES = 8

@@ -118,7 +118,7 @@ def _case(name, C, blend):
 # ---- 1. against float64 on the CPU ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("blend", BLENDS)
 @pytest.mark.parametrize("name", sorted(CASES))
-@pytest.mark.parametrize("C", [2, 3, 8, 11, 16])
+@pytest.mark.parametrize("C", [2, 3, 8, 10, 11, 16])
 def test_mask_and_confidence_vs_float64(dev, C, name, blend):
     """Pixels whose float64 top-2 margin of the blended probability is below TAU are left out; every other pixel must agree and
     the confidence is within one level of round(255 * max) everywhere.  At most 1 % may be left out; the float64 reference alone
@@ -276,6 +276,27 @@ def test_tails_and_unaligned_rows(dev, W):
             a = ops.predict_mask_tiles([aligned[k] for k in order], two, work, (40, W), confidence=True)
             b = ops.predict_mask_tiles([(odd, aligned[1])[k] for k in order], two, work, (40, W), confidence=True)
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("off", [0, 1, 2])
+@pytest.mark.parametrize("C", range(1, 17))
+def test_every_load_width_and_class_bucket(dev, C, off):
+    """Every instance of the kernel: the class bucket follows C (4, 8, 16), the load width C and the maps' addresses.  The first
+    map starts ``off`` floats into a 16-byte aligned buffer (16-byte loads when C % 4 == 0 and off == 0, 8-byte loads when C is
+    even and off is, dword loads otherwise); mask and confidence must equal those of its 16-byte aligned copy bit for bit, under
+    both blends."""
+    B, n = 2, 2 * 5 * 7 * C
+    two = [(0, 0, 16, 10, False), (0, 6, 16, 10, True)]
+    src = _maps(C, B, [(5, 7), (6, 4)], seed=100 * C + off)
+    aligned = [s.to(dev) for s in src]
+    flat = torch.zeros(n + 4, device=dev)
+    assert flat.data_ptr() % 16 == 0 and aligned[0].data_ptr() % 16 == 0 and aligned[1].data_ptr() % 16 == 0
+    odd = flat[off:off + n].view(B, 5, 7, C)
+    odd.copy_(src[0])
+    for blend in BLENDS:
+        a = ops.predict_mask_tiles(aligned, two, (16, 16), (9, 13), blend=blend, confidence=True)
+        b = ops.predict_mask_tiles([odd, aligned[1]], two, (16, 16), (9, 13), blend=blend, confidence=True)
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
 # ---- 6. overlay and counts --------------------------------------------------------------------------------------------------

@@ -61,7 +61,7 @@ def _views(C, B, shapes, seed, scale=3.0):
 
 # ---- 1. against float64 on the CPU ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(CASES))
-@pytest.mark.parametrize("C", [2, 3, 8, 11, 16])
+@pytest.mark.parametrize("C", [2, 3, 8, 10, 11, 16])
 def test_mask_and_confidence_vs_float64(dev, C, name):
     """Pixels whose float64 top-2 margin of the mean probability is below tau = 2e-4 are left out (torch's own fp32 evaluation of
     the formula differs from float64 by at most 1.0e-5 in probability on these inputs; 20 x that for two classes moving in
@@ -146,6 +146,24 @@ def test_tails_and_unaligned_rows(dev, W):
             a = ops.predict_mask_views([aligned[k] for k in order], (40, W), flips=[True, False], confidence=True)
             b = ops.predict_mask_views([(odd, aligned[1])[k] for k in order], (40, W), flips=[True, False], confidence=True)
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("off", [0, 1, 2])
+@pytest.mark.parametrize("C", range(1, 17))
+def test_every_load_width_and_class_bucket(dev, C, off):
+    """Every instance of the kernel: the class bucket follows C (4, 8, 16), the load width C and the maps' addresses.  The first
+    map starts ``off`` floats into a 16-byte aligned buffer (16-byte loads when C % 4 == 0 and off == 0, 8-byte loads when C is
+    even and off is, dword loads otherwise); mask and confidence must equal those of its 16-byte aligned copy bit for bit."""
+    B, n = 2, 2 * 5 * 7 * C
+    src = _views(C, B, [(5, 7), (6, 4)], seed=100 * C + off)
+    aligned = [s.to(dev) for s in src]
+    flat = torch.zeros(n + 4, device=dev)
+    assert flat.data_ptr() % 16 == 0 and aligned[0].data_ptr() % 16 == 0 and aligned[1].data_ptr() % 16 == 0
+    odd = flat[off:off + n].view(B, 5, 7, C)
+    odd.copy_(src[0])
+    a = ops.predict_mask_views(aligned, (9, 13), flips=[False, True], confidence=True)
+    b = ops.predict_mask_views([odd, aligned[1]], (9, 13), flips=[False, True], confidence=True)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
 # ---- 4. overlay and counts --------------------------------------------------------------------------------------------------
