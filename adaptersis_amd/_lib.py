@@ -206,6 +206,9 @@ SIGNATURES = {
     "asis_wgrad": [_vp, C.POINTER(WgradDesc)],
     "asis_conv3x3_wgrad_halo_nblk": [_i, _i, _i, _i, _i],
     "asis_conv3x3_wgrad_halo": [_vp, _i, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i],
+    "asis_lora_down": [_vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _i64],
+    "asis_lora_wgrad_nblk": [_i64, _i],
+    "asis_lora_wgrad": [_vp, _i, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i64],
     "asis_sgd_momentum": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i],
     "asis_augment": [_vp] * 13 + [_i, _i],
     "asis_augment_geo_u8": [_vp] * 12 + [_i, _i],

@@ -17,6 +17,7 @@ Everything is a HIP kernel from libasis_hip.so; torch provides device memory, st
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -25,6 +26,7 @@ import torch.distributed as dist
 from torch import nn
 
 from .. import config, ops
+from .. import lora as lora_mod
 from ..dinov2.layers.blocks import _Packed, _pack, run_blocks
 from ..droppath import DropPathSampler
 from ..optim import SGD, AdamW, FlatBucket
@@ -141,7 +143,7 @@ class SegEngine(nn.Module):
                  blocks_per_bucket: int = 4, grad_compress: Optional[str] = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
                  layer_decay: Optional[float] = None, topk_percent: float = 10.0, focal_gamma: float = 2.0,
-                 drop_path_seed: int = 0):
+                 drop_path_seed: int = 0, lora_rank: Optional[int] = None, lora_alpha: Optional[float] = None):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -167,7 +169,14 @@ class SegEngine(nn.Module):
         ``focal_gamma``: the ``gamma`` of ``FocalLoss`` for "focal".
 
         ``drop_path_seed``: seed of the stochastic-depth draws of a model built with ``drop_path_rate`` > 0 (droppath.py); they
-        act in the training forward of ``train_backbone`` only, and every rank draws its own."""
+        act in the training forward of ``train_backbone`` only, and every rank draws its own.
+
+        ``lora_rank`` (4 | 8 | 16 | 32, with mode="train_adapters" and ``train_backbone``; ``lora_alpha`` defaults to the rank):
+        low-rank adaptation of the q and v projections of every block (lora.py).  The step is the ``train_backbone`` step with the
+        backbone weights frozen: both ViT passes run the training forward on the K-augmented qkv GEMM, the backward produces
+        input gradients plus the three LoRA gradients per block, no backbone gradient bucket exists, a small LoRA bucket is
+        all-reduced once (after block 0's backward) and joins the optimizer; ``eval_logits`` (validation, prediction) runs the
+        frozen forward on the merged weights.  Not with ``optimize_backbone``, ``layer_decay``, stochastic depth or the MLA flow."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -251,7 +260,20 @@ class SegEngine(nn.Module):
         self.precise_parts = config.precise_parts_policy if config.precise_parts_policy is not None else \
             (frozenset(("proj", "fc1")) if (config.precise_level_policy is None and self.precise_level == 2) else all_parts)
         self.vit_bucket = None
-        if train_backbone:
+        self.lora = self.lora_bucket = None
+        if lora_rank is None and lora_alpha is not None:
+            raise ValueError("lora_alpha needs lora_rank")
+        if lora_rank is not None:
+            lora_mod.check_engine_args(mode=mode, train_backbone=train_backbone, optimize_backbone=optimize_backbone,
+                                       layer_decay=layer_decay, is_mla=self.is_mla, model=model, rank=lora_rank)
+            # the backbone weights stay frozen (requires_grad False, above): no ViT bucket; the LoRA parameters live in a small
+            # bucket of their own whose one exchange fires when block 0 (the last of the reverse walk) has written its gradients
+            self.lora = lora_mod.LoRA(model, lora_rank, lora_alpha)
+            self.lora_bucket = FlatBucket(list(self.lora.named_parameters()))
+            self.vit_reducer = StageReducer(self.lora_bucket.grad, [(0, self.lora_bucket.numel)], process_group)
+            self._fire_at = [0]
+            buckets.append(self.lora_bucket)
+        elif train_backbone:
             if mode != "train_adapters":
                 raise ValueError("train_backbone needs mode='train_adapters' (the unfrozen variant of the adapter flow)")
             self.vit_bucket, self.vit_reducer, self._fire_at = make_vit_bucket(model, blocks_per_bucket, process_group,
@@ -713,9 +735,10 @@ class SegEngine(nn.Module):
         nb, nl = len(m.blocks), self.n_last_blocks
         Ra, Rb = B * (N + 1), B * N
         dev = dcat.device
-        ab, vg = self.adapter_bucket, self.vit_bucket.views
+        lora = self.lora is not None      # frozen backbone weights: the blocks write their LoRA gradients, nothing else of the ViT
+        ab, vg = self.adapter_bucket, (self.lora_bucket if lora else self.vit_bucket).views
         slabs = ops.zeros((nl, ab.numel), dev)
-        nslab = ops.zeros((nl, 2 * D), dev)
+        nslab = None if lora else ops.zeros((nl, 2 * D), dev)
         nw = m.norm.weight.detach().float().contiguous()
         dcat2 = dcat.view(B * N, D3)
         G = ops.zeros((Ra + Rb, D), dev)
@@ -733,7 +756,8 @@ class SegEngine(nn.Module):
                 ops.add_f32(dyA[:, 1:], dvit.view(B, N, D), out=dyA[:, 1:])
             Gn = torch.empty((Ra + Rb, D), device=dev, dtype=torch.float32)
             _, part = ops.layernorm_bwd(dyA.view(Ra, D), fin[s][:Ra], nw, m.norm.eps, res=G[:Ra], out=Gn[:Ra])
-            ops.reduce_rows(part.view(part.shape[0], 2 * D), inv, nslab[s])
+            if not lora:
+                ops.reduce_rows(part.view(part.shape[0], 2 * D), inv, nslab[s])
             dx = G[Ra:]
             dc_in = None
             if dc_next is not None:
@@ -746,8 +770,9 @@ class SegEngine(nn.Module):
             dc_next = dc_cv
             ops.copy_channels(dx_in, Gn[Ra:])
             if s == 0:   # every use of model.norm / CAViT / CACNN has contributed: finish their gradients, start the exchanges
-                red = ops.reduce_rows(nslab, 1.0)
-                vg["norm.weight"].copy_(red[:D]); vg["norm.bias"].copy_(red[D:])
+                if not lora:
+                    red = ops.reduce_rows(nslab, 1.0)
+                    vg["norm.weight"].copy_(red[:D]); vg["norm.bias"].copy_(red[D:])
                 self._block_done(nb)
                 ops.reduce_rows(slabs, 1.0, ab.grad)
                 self.adapter_reducer.stage_done()
@@ -762,7 +787,8 @@ class SegEngine(nn.Module):
             G = m.blocks[i].backward(bsaves[i], G, inv, vg, f"blocks.{i}")
             bsaves[i] = None
             self._block_done(i)
-        m.embed_backward(a16, G[:Ra].view(B, N + 1, D), G[Ra:], H, W, inv, vg)
+        if not lora:
+            m.embed_backward(a16, G[:Ra].view(B, N + 1, D), G[Ra:], H, W, inv, vg)
         self._block_done(-1)
 
     def _adapter_backward(self, asaves, dcat: torch.Tensor, inv: float) -> None:
@@ -858,11 +884,13 @@ class SegEngine(nn.Module):
 
     @torch.no_grad()
     def eval_logits(self, inp: torch.Tensor) -> torch.Tensor:
-        """Decoder logits, NHWC fp32, with the decoder's BatchNorm in its current train/eval mode."""
-        if self.is_mla:
-            logits, _ = self.seg_decoder._forward_core(self.features_mla(inp), save=False)
-        else:
-            logits, _ = self.seg_decoder._forward_core(*self.features(inp), save=False)
+        """Decoder logits, NHWC fp32, with the decoder's BatchNorm in its current train/eval mode.  With LoRA the frozen forward
+        runs on the merged weights W + s B A (``LoRA.merged``)."""
+        with (self.lora.merged(self.model) if self.lora is not None else contextlib.nullcontext()):
+            if self.is_mla:
+                logits, _ = self.seg_decoder._forward_core(self.features_mla(inp), save=False)
+            else:
+                logits, _ = self.seg_decoder._forward_core(*self.features(inp), save=False)
         return logits
 
     @torch.no_grad()
@@ -1018,8 +1046,10 @@ class EndToEndEngine(nn.Module):
     def __init__(self, model, seg_decoder, *, lr: float = 0.01, momentum: float = 0.9, weight_decay: float = 0.0,
                  loss: str = "ce_dc", process_group=None, blocks_per_bucket: int = 4, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
-                 drop_path_seed: int = 0):
+                 drop_path_seed: int = 0, lora_rank: Optional[int] = None):
         super().__init__()
+        if lora_rank is not None:
+            raise ValueError("EndToEndEngine trains every backbone weight: LoRA (lora_rank) is built for SegEngine's adapter flow")
         self.drop_path = make_drop_path_sampler(model, drop_path_seed, process_group)   # stochastic depth of ``train_step``
         if loss not in SegEngine.LOSSES:
             raise ValueError(f"loss must be one of {sorted(SegEngine.LOSSES)}")

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from ... import config, droppath, ops
+from ... import lora as _lora_mod
 
 
 _VT_STREAMS = {}
@@ -77,9 +78,10 @@ class _Packed(nn.Module):
         return _pack(self._cache, key, param, lambda p: p.float().contiguous())
 
     # ---- backward helpers shared by the ViT blocks and the adapter modules --------------------------------------
-    def _pack2(self, key: str, w: torch.Tensor, gamma: Optional[torch.Tensor], fn):
-        """cache of a 16-bit operand derived from a weight and (optionally) a LayerScale vector"""
-        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in (w, gamma) if t is not None) + \
+    def _pack2(self, key: str, w: torch.Tensor, gamma: Optional[torch.Tensor], fn, extra=()):
+        """cache of a 16-bit operand derived from a weight and (optionally) a LayerScale vector (``extra``: further tensors it is
+        derived from — the LoRA matrices of an augmented pack)"""
+        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in (w, gamma, *extra) if t is not None) + \
             (config.operand_dtype,)
         hit = self._cache.get(key)
         if hit is None or hit[0] != tag:
@@ -238,6 +240,33 @@ class Attention(_Packed):
         self.scale = (dim // num_heads) ** -0.5
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.proj = nn.Linear(dim, dim, bias=proj_bias)
+
+    # ---- LoRA on the q and v thirds of qkv (lora.py): a handle attached by ``lora.LoRA``, never a submodule or a parameter ----
+    _lora = None
+
+    def _lora_packs_fwd(self):
+        """(Wf [3D, D + 64] = [W_qkv | s B placed], its rounding residual | None, Wd [64, D] = A padded) as 16-bit operands"""
+        lo, w = self._lora, self.qkv.weight
+        dt = config.operand_dtype
+        f = lambda t: t.detach().float()
+        wf32 = lambda: _lora_mod.pack_wf(f(w), f(lo.Bq), f(lo.Bv), lo.scale).contiguous()
+        wf = self._pack2("qkv.lora.wf", w, None, lambda: ops.cast_pad(wf32(), dtype=dt), extra=(lo.Bq, lo.Bv))
+        wf_lo = None
+        if config.precise_attention:   # the lo plane ``_w16lo`` supplies for the plain weight, of the whole augmented matrix
+            wf_lo = self._pack2("qkv.lora.wf.lo", w, None, lambda: ops.cast_pad(wf32(), dtype=dt, part=1), extra=(lo.Bq, lo.Bv))
+        wd = self._pack2("qkv.lora.wd", lo.A, None, lambda: ops.cast_pad(_lora_mod.pack_wd_fwd(f(lo.A)).contiguous(), dtype=dt))
+        return wf, wf_lo, wd
+
+    def _lora_packs_bwd(self):
+        """(WbT [D, 3D + 64] = [W_qkv^T | A^T | 0], Wd [64, 2D] = [s B_q^T | 0 ; 0 | s B_v^T]) as 16-bit operands"""
+        lo, w = self._lora, self.qkv.weight
+        dt = config.operand_dtype
+        f = lambda t: t.detach().float()
+        wbt = self._pack2("qkv.lora.wbt", w, None, lambda: ops.cast_pad(_lora_mod.pack_wbt(f(w), f(lo.A)).contiguous(), dtype=dt),
+                          extra=(lo.A,))
+        wd = self._pack2("qkv.lora.wdb", lo.Bq, None,
+                         lambda: ops.cast_pad(_lora_mod.pack_wd_bwd(f(lo.Bq), f(lo.Bv), lo.scale).contiguous(), dtype=dt), extra=(lo.Bv,))
+        return wbt, wd
 
     def _qkv_folded(self):
         """(16-bit qkv weight, fp32 bias, rounding residual | None) with the q rows multiplied by scale * log2(e) in fp32
@@ -701,7 +730,18 @@ class Block(_Packed):
         dt = config.operand_dtype
         D = xn.shape[1]
         a = self.attn
-        qkv = ops.gemm(xn, a._w16("qkv", a.qkv.weight), bias_n=a._f32("qkv_b", a.qkv.bias), b_lo=a._w16lo("qkv", a.qkv.weight))
+        if a._lora is not None:
+            # LoRA: ``xn`` is the first D columns of abuf [R, D + 64]; u = xn A^T goes into the last 64 (all of them written: the
+            # pad columns meet zero columns of Wf, and NaN * 0 = NaN) and the ONE qkv GEMM runs over K = D + 64
+            P = ops.LORA_PAD
+            if xn.stride(0) != D + P or xn.stride(1) != 1:
+                raise ValueError("_attn_train with LoRA: xn must be the first D columns of a 16-bit [R, D + 64] buffer")
+            abuf = xn.as_strided((xn.shape[0], D + P), (D + P, 1))
+            wf, wf_lo, wd = a._lora_packs_fwd()
+            ops.lora_down(abuf, [(0, D)], wd, out=abuf[:, D:])
+            qkv = ops.gemm(abuf, wf, bias_n=a._f32("qkv_b", a.qkv.bias), b_lo=wf_lo)
+        else:
+            qkv = ops.gemm(xn, a._w16("qkv", a.qkv.weight), bias_n=a._f32("qkv_b", a.qkv.bias), b_lo=a._w16lo("qkv", a.qkv.weight))
         o = torch.empty((xn.shape[0], D), device=xn.device, dtype=dt)
         o_lo = torch.empty_like(o) if config.split_attn_out else None
         if sum(B * N for B, N in segs) != xn.shape[0]:
@@ -743,8 +783,15 @@ class Block(_Packed):
             raise ValueError("forward_train_rows: segments do not cover the rows")
         ka, kf = droppath.as_branch_keeps(keep, segs, x2.device)
         n1w, n1b = self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias)
+        lora_on = a._lora is not None
+        if lora_on and keep is not None:
+            raise ValueError("forward_train_rows: LoRA and stochastic depth exclude each other (the gathered LayerNorm has no strided output)")
         if ka is None:
-            xn = ops.layernorm(x2, n1w, n1b, self.norm1.eps, dt)
+            if lora_on:     # LayerNorm writes the first D columns of [xn | u] (row stride D + 64): see ``_attn_train``
+                xn = torch.empty((x2.shape[0], D + ops.LORA_PAD), device=x2.device, dtype=dt)[:, :D]
+                ops.layernorm(x2, n1w, n1b, self.norm1.eps, dt, out=xn)
+            else:
+                xn = ops.layernorm(x2, n1w, n1b, self.norm1.eps, dt)
             qkv, o, o_lo, lse = self._attn_train(xn, segs)
             x1 = ops.gemm(o, a._w16("proj", a.proj.weight), out_f32=True, bias_n=a._f32("proj_b", a.proj.bias), scale_n=g1,
                           res=x2, a_lo=o_lo, b_lo=a._w16lo("proj", a.proj.weight))
@@ -776,6 +823,8 @@ class Block(_Packed):
         if kf is not None:
             x3 = ops.scaled_index_add(x1, x3, kf)
         saved = (x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, segs)
+        if lora_on:          # saved[:10] as ever (MaskTransformer shares ``backward``); xn carries u behind it
+            return x3, saved + ((None, None), "lora")
         return x3, (saved if keep is None else saved + ((ka, kf),))
 
     def backward(self, saved, dres: torch.Tensor, inv_scale: float, grads: Optional[dict] = None, prefix: str = "") -> torch.Tensor:
@@ -784,12 +833,20 @@ class Block(_Packed):
         without it only the input gradient is produced (frozen backbone, adapters training)."""
         x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, segs = saved[:10]
         ka, kf = saved[10] if len(saved) > 10 else (None, None)     # stochastic depth: the kept samples of the two branches
+        lora_on = len(saved) > 11 and saved[11] == "lora"           # the forward took the rank-r route (lora.py)
         dt = config.operand_dtype
         D = x2.shape[1]
         a, m = self.attn, self.mlp
         ls1 = self.ls1.gamma if isinstance(self.ls1, LayerScale) else None
         ls2 = self.ls2.gamma if isinstance(self.ls2, LayerScale) else None
         pre = prefix + "." if prefix else ""
+        # a ``grads`` dict that holds the block's LoRA names: those three gradients are written and every dense weight gradient,
+        # the norm gradients and the column sums are skipped (``grads`` = None from here on)
+        lgrads = None
+        if lora_on and grads is not None and pre + "attn.qkv.lora_A" in grads:
+            lgrads, grads = grads, None
+        elif lora_on and grads is not None:
+            raise ValueError("Block.backward: behind a LoRA forward ``grads`` holds the block's LoRA names (or is None)")
         # per-branch power-of-two scales of the LayerScale'd gradients (see ``_ls_pow2``): dh / dO and everything computed from
         # them inside the branch carry 2^k; the factor leaves through inv_scale (weight / bias / norm gradients) and through the
         # LayerNorm backward's weight (input gradient)
@@ -838,7 +895,11 @@ class Block(_Packed):
             d16, cs = ops.cast_colsum(dx1, dt) if grads is not None else (ops.cast_pad(dx1, D, dt), None)
         self._linear_bwd(pre + "attn.proj", a.proj, ls1, pre + "ls1.gamma", d16, cs, o, inv_scale, grads)
         dO = ops.gemm(d16, self._wT16("projT", a.proj.weight, ls1, k1))            # 16-bit [R, D], times 2^k1
-        dqkv = torch.empty((d16.shape[0], 3 * D), device=x2.device, dtype=dt)
+        if lora_on:         # [dQ | dK | dV | du]: the attention backward writes the first 3D columns (row stride 3D + 64)
+            dbuf = torch.empty((d16.shape[0], 3 * D + ops.LORA_PAD), device=x2.device, dtype=dt)
+            dqkv = dbuf[:, :3 * D]
+        else:
+            dqkv = torch.empty((d16.shape[0], 3 * D), device=x2.device, dtype=dt)
         if isinstance(lse, (list, tuple)):   # per-batch [B, H, N] tensors (the MaskTransformer block's forward)
             lse = torch.cat([l.reshape(-1) for l in lse])
         q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
@@ -850,7 +911,23 @@ class Block(_Packed):
                                    part, a.num_heads, a.scale, dqkv=dqkv[r0:r1])
         self._linear_bwd(pre + "attn.qkv", a.qkv, None, None, dqkv, ops.colsum(dqkv) if grads is not None else None, xn,
                          inv1, grads)
-        dln = ops.gemm(dqkv, self._wT16("qkvT", a.qkv.weight), out_f32=True)
+        if lora_on:
+            # du = s (dQ B_q | dV B_v) behind dqkv, then ONE input-gradient GEMM over K = 3D + 64: dqkv W + du A
+            lo, P = a._lora, ops.LORA_PAD
+            wbt, wdb = a._lora_packs_bwd()
+            du = dbuf[:, 3 * D:]
+            ops.lora_down(dbuf, [(0, D), (2 * D, D)], wdb, out=du)
+            if lgrads is not None:
+                r = lo.rank
+                abuf = xn.as_strided((xn.shape[0], D + P), (D + P, 1))
+                dA = ops.lora_wgrad(du, abuf, [(0, D)], inv1)                                        # [64, D], rows 0..2r valid
+                Gb = ops.lora_wgrad(abuf[:, D:], dbuf, [(0, D), (2 * D, D)], lo.scale * inv1)       # [64, 2D]: the diagonal blocks
+                lgrads[pre + "attn.qkv.lora_A"].copy_(dA[:2 * r])
+                lgrads[pre + "attn.qkv.lora_B_q"].copy_(Gb[:r, :D].t())
+                lgrads[pre + "attn.qkv.lora_B_v"].copy_(Gb[r:2 * r, D:].t())
+            dln = ops.gemm(dbuf, wbt, out_f32=True)
+        else:
+            dln = ops.gemm(dqkv, self._wT16("qkvT", a.qkv.weight), out_f32=True)
         if ka is not None:
             dx, part = ops.layernorm_bwd_scatter(dln, x2, self._nw_pow2("n1w", self.norm1.weight, -k1), self.norm1.eps, dx1, ka)
         else:

@@ -1868,6 +1868,73 @@ def wgrad(dy: torch.Tensor, x_nhwc: torch.Tensor, Cout: int, KH: int, KW: int, s
     return out
 
 
+LORA_PAD = 64   # padded width of the stacked rank dimension (q | v): 2 r <= 64 (csrc/lora.hip)
+
+
+def _lora_args(op: str, x: torch.Tensor, segs, u: torch.Tensor):
+    """checks shared by ``lora_down`` / ``lora_wgrad`` -> (col0a, lena, col0b, lenb, R)"""
+    segs = [(int(c), int(n)) for c, n in segs]
+    if len(segs) not in (1, 2):
+        raise ValueError(f"{op}: one or two column segments (col0, len)")
+    if x.dim() != 2 or u.dim() != 2 or x.dtype != u.dtype or x.stride(1) != 1 or u.stride(1) != 1:
+        raise ValueError(f"{op}: x and u must be 2-D 16-bit matrices of one dtype with contiguous rows")
+    _dt(x.dtype)
+    (c0a, lena), (c0b, lenb) = segs[0], (segs[1] if len(segs) == 2 else (0, 0))
+    if any(n < 64 or n % 64 for _, n in segs) or any(c < 0 or c % 8 for c, _ in segs) or (len(segs) == 2 and c0b < c0a + lena):
+        raise ValueError(f"{op}: segments must have len % 64 == 0 and col0 % 8 == 0, in order and not overlapping: {segs}")
+    if segs[-1][0] + segs[-1][1] > x.shape[1]:
+        raise ValueError(f"{op}: segments {segs} reach past the {x.shape[1]} columns of x")
+    R = x.shape[0]
+    if R < 1 or u.shape[0] < R or u.shape[1] != LORA_PAD:
+        raise ValueError(f"{op}: u must be a [>= {R}, {LORA_PAD}] view, got {tuple(u.shape)}")
+    if x.stride(0) % 8 or u.stride(0) % 8 or x.data_ptr() % 16 or u.data_ptr() % 16:
+        raise ValueError(f"{op}: x and u must be 16-byte aligned with row strides that are multiples of 8")
+    return c0a, lena, c0b, lenb, R
+
+
+def lora_down(x: torch.Tensor, segs, wd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[R, 0:64] = round16(x_seg @ wd.T)``: x 16-bit [R, C] (any row stride), ``segs`` = [(col0, len)] or two of them (the
+    columns in between are never read), wd 16-bit [64, sum(len)] contiguous.  ``out``: a 16-bit [R, 64] view (e.g. the last 64
+    columns of a wider buffer); all 64 columns are written, nothing else is touched."""
+    _dev(x, wd, out)
+    if out is None:
+        out = torch.empty((x.shape[0], LORA_PAD), device=x.device, dtype=x.dtype)
+    c0a, lena, c0b, lenb, R = _lora_args("lora_down", x, segs, out)
+    if wd.dtype != x.dtype or tuple(wd.shape) != (LORA_PAD, lena + lenb) or not wd.is_contiguous() or wd.data_ptr() % 16:
+        raise ValueError(f"lora_down: wd must be a contiguous 16-byte aligned [{LORA_PAD}, {lena + lenb}] matrix of x's dtype")
+    Kt = lena + lenb
+    check(_launch_timed("lora_down", 2.0 * R * LORA_PAD * Kt,
+                        lambda: lib().asis_lora_down(_stream(), _dt(x.dtype), x.data_ptr(), x.stride(0), c0a, lena, c0b, lenb,
+                                                     wd.data_ptr(), out.data_ptr(), out.stride(0), R),
+                        2.0 * (R * Kt + LORA_PAD * Kt + R * LORA_PAD)), "asis_lora_down")
+    return out
+
+
+def lora_wgrad_nblk(R: int, Nt: int) -> int:
+    return lib().asis_lora_wgrad_nblk(int(R), int(Nt))
+
+
+def lora_wgrad(u: torch.Tensor, x: torch.Tensor, segs, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> fp32 [64, Nt] = scale * u[:R].T @ x_seg, R = rows of x: u 16-bit [>= R, 64] and x 16-bit [R, C], both row-strided,
+    ``segs`` as in ``lora_down`` (Nt = sum(len)).  Per-row-block fp32 slabs summed by ``reduce_rows`` in a fixed order: two runs
+    are bit-identical."""
+    _dev(u, x, out)
+    c0a, lena, c0b, lenb, R = _lora_args("lora_wgrad", x, segs, u)
+    Nt = lena + lenb
+    if out is None:
+        out = torch.empty((LORA_PAD, Nt), device=x.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (LORA_PAD, Nt) or not out.is_contiguous():
+        raise ValueError(f"lora_wgrad: out must be a contiguous float32 [{LORA_PAD}, {Nt}] tensor")
+    nblk = lora_wgrad_nblk(R, Nt)
+    slabs = torch.empty((nblk, LORA_PAD * Nt), device=x.device, dtype=torch.float32)
+    check(_launch_timed("lora_wgrad", 2.0 * R * LORA_PAD * Nt,
+                        lambda: lib().asis_lora_wgrad(_stream(), _dt(x.dtype), u.data_ptr(), u.stride(0), x.data_ptr(), x.stride(0),
+                                                      c0a, lena, c0b, lenb, slabs.data_ptr(), nblk, R),
+                        2.0 * R * (Nt + LORA_PAD) + 4.0 * nblk * LORA_PAD * Nt), "asis_lora_wgrad")
+    reduce_rows(slabs, scale, out.view(-1))
+    return out
+
+
 def grad_guard(g: torch.Tensor, guard: torch.Tensor, reset: bool) -> None:
     """guard int32[2]: guard[0] |= any non-finite element of ``g`` (cleared first when ``reset``)."""
     _dev(g, guard)

@@ -63,6 +63,7 @@ import torch
 
 from . import train as _t
 from .backbones.engines import SegEngine
+from .lora import LoRA
 from .tools import frame_resize as _fr
 
 IMAGE_EXT = (".png", ".jpg", ".bmp")
@@ -384,6 +385,8 @@ def build_engine(args) -> SegEngine:
     # "backbone": the ViT of a run with --optimize_backbone (absent from any other checkpoint: the pretrained weights stay)
     load_checkpoint(path, dec, {"cross_vit": cv, "cross_cnn": cn, "backbone_encoder": enc, "backbone": model},
                     hint=f" (--head {args.head} --num_classes {args.num_classes})", ck=ck)
+    if "lora" in ck:    # a run with --lora_rank: every forward of the engine goes through the merged weights (SegEngine.eval_logits)
+        eng.lora = LoRA.from_state(model, ck["lora"])
     print(f"loaded {path} (epoch {ck.get('epoch')}, entries {sorted(k for k in ck if isinstance(ck[k], dict))})")
     return eng
 

@@ -173,6 +173,9 @@ def _backbone_args(args) -> dict:
         out["optimize_backbone"] = True
     if getattr(args, "drop_path_seed", 0):
         out["drop_path_seed"] = int(args.drop_path_seed)
+    if getattr(args, "lora_rank", None) is not None:      # LoRA on q / v (lora.py); the engine rejects what it excludes
+        out["lora_rank"] = int(args.lora_rank)
+        out["lora_alpha"] = getattr(args, "lora_alpha", None)
     return out
 
 
@@ -187,6 +190,15 @@ def check_backbone_args(args) -> Optional[str]:
         return "--drop_path must be in [0, 1)"
     if r > 0.0 and not getattr(args, "train_backbone", False):
         return "--drop_path drops samples in the training forward of the ViT blocks: it needs --train_backbone"
+    if getattr(args, "lora_alpha", None) is not None and getattr(args, "lora_rank", None) is None:
+        return "--lora_alpha needs --lora_rank"
+    if getattr(args, "lora_rank", None) is not None:
+        if not (getattr(args, "train_adapters", False) and getattr(args, "train_backbone", False)):
+            return "--lora_rank needs --train_adapters --train_backbone (LoRA runs the backbone's training forward)"
+        if getattr(args, "optimize_backbone", False):
+            return "--lora_rank and --optimize_backbone exclude each other (with LoRA the backbone weights stay frozen)"
+        if r > 0.0:
+            return "--lora_rank needs --drop_path 0"
     return None
 
 
@@ -306,8 +318,10 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
             extra["backbone_encoder"] = backbone_encoder
         if getattr(args, "optimize_backbone", False):   # a fine-tuned ViT is part of the trained model: saved and restored
             extra["backbone"] = model
+    lora = getattr(engine, "lora", None)       # --lora_rank: the checkpoint gains a "lora" entry (parameters, rank, alpha)
     utils.restart_from_checkpoint(os.path.join(args.output_dir, "checkpoint.pth.tar"), run_variables=to_restore,
-                                  state_dict=seg_decoder, **extra, optimizer=optimizer, scheduler=scheduler)
+                                  state_dict=seg_decoder, **extra, **({} if lora is None else {"lora": lora}), optimizer=optimizer,
+                                  scheduler=scheduler)
     start_epoch, best_acc = to_restore["epoch"], to_restore["best_acc"]
     if args.evaluate:
         stats = validate(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_decoder,
@@ -337,6 +351,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                     "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(), "best_acc": best_acc}
             for k, mod in extra.items():
                 ckpt[k] = {"module." + n: v for n, v in mod.state_dict().items()}
+            if lora is not None:
+                ckpt["lora"] = lora.state_dict()
             torch.save(ckpt, os.path.join(args.output_dir, "checkpoint.pth.tar"))
     print("Training of the supervised linear classifier on frozen features completed.\n"
           "Top-1 test accuracy: {acc:.1f}".format(acc=best_acc))
@@ -478,6 +494,10 @@ def get_args_parser():
                    help="with --train_adapters: both ViT passes run with saved activations and the backward reaches every block")
     p.add_argument("--optimize_backbone", action="store_true",
                    help="with --train_backbone: the optimizer also steps the ViT; the checkpoint gains a 'backbone' entry")
+    p.add_argument("--lora_rank", default=None, type=int, choices=(4, 8, 16, 32), metavar="R",
+                   help="with --train_adapters --train_backbone: low-rank adaptation of the q and v projections of every ViT block "
+                        "instead of full backbone gradients (4 | 8 | 16 | 32); the checkpoint gains a 'lora' entry")
+    p.add_argument("--lora_alpha", default=None, type=float, help="LoRA scale numerator: the update is (alpha / rank) B A (default: the rank)")
     p.add_argument("--drop_path", default=0.0, type=float, metavar="R",
                    help="stochastic depth rate of the ViT (DINOv2's drop_path_rate; needs --train_backbone): block i gets "
                         "linspace(0, R, depth)[i]; above 0.1 a branch runs on a random subset of the batch only")

@@ -794,6 +794,21 @@ int asis_conv3x3_wgrad_halo_nblk(int B, int H, int W, int Cin, int Cout);
 int asis_conv3x3_wgrad_halo(void* stream, int dtype, const void* dy, int64_t ld_dy, const void* x, float* slabs, int nblk, int B,
                             int H, int W, int Cin, int Cout);
 
+/* Low-rank (LoRA) updates of the attention q / v projections (csrc/lora.hip; adaptersis_amd/lora.py).  X_seg = one or two column
+ * segments (col0a, lena), (col0b, lenb) of a 16-bit matrix x with row stride ldx (elements): len % 64 == 0 (lenb = 0: one segment),
+ * col0 % 8 == 0, segment b behind segment a; the columns between them are never read.  Kt = Nt = lena + lenb.
+ * asis_lora_down:  u[R, 0:64] (16-bit, row stride ldu >= 64) = round16(X_seg[R, Kt] wd^T), wd 16-bit [64, Kt] contiguous, fp32
+ *   accumulation.  All 64 columns are written (a zero row of wd gives an exact zero); nothing outside [R, 64] is touched.
+ * asis_lora_wgrad: slabs fp32 [nblk, 64, Nt], slab[b][p][n] = sum over the rows of block b of u[row, p] * X_seg[row, n]; rows >= R
+ *   are never used.  nblk = asis_lora_wgrad_nblk(R, Nt) (host only; 0 for a bad shape); sum the slabs with asis_reduce_rows
+ *   (fixed order, no atomics: deterministic).
+ * x, u, wd, slabs 16-byte aligned; ldx, ldu % 8 == 0; R >= 1. */
+int asis_lora_down(void* stream, int dtype, const void* x, int64_t ldx, int col0a, int lena, int col0b, int lenb, const void* wd,
+                   void* u, int64_t ldu, int64_t R);
+int asis_lora_wgrad_nblk(int64_t R, int Nt);
+int asis_lora_wgrad(void* stream, int dtype, const void* u, int64_t ldu, const void* x, int64_t ldx, int col0a, int lena, int col0b,
+                    int lenb, float* slabs, int nblk, int64_t R);
+
 /* torch.optim.SGD step (train.py:178-191: momentum, weight decay, dampening 0, no Nesterov) on a flat
  * fp32 parameter buffer; g is multiplied by inv_scale (1/loss_scale) first. */
 int asis_sgd_momentum(void* stream, float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
