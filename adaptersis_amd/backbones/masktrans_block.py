@@ -84,7 +84,7 @@ class Block(L.Block):
         H = a.num_heads
         xn32 = ops.layernorm(x2, self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias), self.norm1.eps, torch.float32)
         xn, xn_lo = ops.cast_pad(xn32, D, dt), ops.cast_pad(xn32, D, dt, part=1)
-        qkv32 = self._split_linear(xn, xn_lo, a._w16("qkv", a.qkv.weight), self._lo(a, "qkv", a.qkv.weight), a._f32("qkv_b", a.qkv.bias))
+        qkv32 = self._split_linear(xn, xn_lo, a._w16("qkv", a.qkv.weight), a._w16("qkv", a.qkv.weight, part=1), a._f32("qkv_b", a.qkv.bias))
         qkv = ops.cast_pad(qkv32, 3 * D, dt)
         o = torch.empty((R, D), device=x2.device, dtype=dt)
         if len(segs) != 1:
@@ -103,16 +103,16 @@ class Block(L.Block):
         for h in range(H):
             ops.gemm(Pd4[h], vt[:, h * 64:(h + 1) * 64, :], out=o3[:, :, h * 64:(h + 1) * 64])
         y = ops.gemm(o, a._w16("proj", a.proj.weight), out_f32=True, bias_n=a._f32("proj_b", a.proj.bias),
-                     b_lo=self._lo(a, "proj", a.proj.weight))
+                     b_lo=a._w16("proj", a.proj.weight, part=1))
         x1 = ops.dropout_f32(y, seed, site0 + self.SITE_PROJ, p, res=x2)
         xn2_32 = ops.layernorm(x1, self._f32("n2w", self.norm2.weight), self._f32("n2b", self.norm2.bias), self.norm2.eps, torch.float32)
         xn2, xn2_lo = ops.cast_pad(xn2_32, D, dt), ops.cast_pad(xn2_32, D, dt, part=1)
-        hpre32 = self._split_linear(xn2, xn2_lo, m._w16("fc1", m.fc1.weight), self._lo(m, "fc1", m.fc1.weight), m._f32("fc1_b", m.fc1.bias))
+        hpre32 = self._split_linear(xn2, xn2_lo, m._w16("fc1", m.fc1.weight), m._w16("fc1", m.fc1.weight, part=1), m._f32("fc1_b", m.fc1.bias))
         hpost, hpost_lo = ops.gelu_split(hpre32, dt)
         hsaved = ops.dropout_t16(hpost.clone(), seed, site0 + self.SITE_GELU, p, rescale=True)      # drop(gelu) as fc2's weight gradient sees it
         # the operand pair of fc2 is only ZEROED (hi + lo stays exact); its 1 / (1 - p) and the bias go into the next kernel
         ops.dropout_t16(hpost, seed, site0 + self.SITE_GELU, p, x_lo=hpost_lo, rescale=False)
-        f2 = self._split_linear(hpost, hpost_lo, m._w16("fc2", m.fc2.weight), self._lo(m, "fc2", m.fc2.weight), None)
+        f2 = self._split_linear(hpost, hpost_lo, m._w16("fc2", m.fc2.weight), m._w16("fc2", m.fc2.weight, part=1), None)
         x3 = ops.dropout_f32(f2, seed, site0 + self.SITE_FC2, p, res=x1, alpha=1.0 / (1.0 - p), bias_n=m._f32("fc2_b", m.fc2.bias))
         hpre = ops.cast_pad(hpre32, hpre32.shape[1], dt)
         return x3, dict(x2=x2, xn=xn, qkv=qkv, o=o, P=P, Pd=Pd, x1=x1, xn2=xn2, hpre=hpre, hpost=hsaved, segs=list(segs),
@@ -184,10 +184,6 @@ class Block(L.Block):
     # split-precision operands too (LayerNorm / GELU outputs as hi + lo pairs, weights as hi + lo pairs); only the fused
     # attention keeps 16-bit q, k, v, P and its 16-bit output.  Two layers of d_model: 3x the GEMM passes of a head that is a
     # few per cent of the backbone.  The saved activations keep the 16-bit layout ``Block.backward`` expects.
-    def _lo(self, owner, key: str, w: torch.Tensor):
-        return _pack(owner._cache, key + ".lo2", w,
-                     lambda q: ops.cast_pad(q.reshape(q.shape[0], -1).contiguous().float(), dtype=config.operand_dtype, part=1))
-
     @staticmethod
     def _split_linear(a_hi, a_lo, w_hi, w_lo, bias, res=None):
         out = torch.empty((a_hi.shape[0], w_hi.shape[0]), device=a_hi.device, dtype=torch.float32)
@@ -203,7 +199,7 @@ class Block(L.Block):
         a, m = self.attn, self.mlp
         xn32 = ops.layernorm(x2, self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias), self.norm1.eps, torch.float32)
         xn, xn_lo = ops.cast_pad(xn32, D, dt), ops.cast_pad(xn32, D, dt, part=1)
-        qkv32 = self._split_linear(xn, xn_lo, a._w16("qkv", a.qkv.weight), self._lo(a, "qkv", a.qkv.weight), a._f32("qkv_b", a.qkv.bias))
+        qkv32 = self._split_linear(xn, xn_lo, a._w16("qkv", a.qkv.weight), a._w16("qkv", a.qkv.weight, part=1), a._f32("qkv_b", a.qkv.bias))
         qkv = ops.cast_pad(qkv32, 3 * D, dt)
         o = torch.empty((R, D), device=x2.device, dtype=dt)
         lse = []
@@ -218,12 +214,12 @@ class Block(L.Block):
         if r0 != R:
             raise ValueError("masktrans Block: segments do not cover the rows")
         x1 = ops.gemm(o, a._w16("proj", a.proj.weight), out_f32=True, bias_n=a._f32("proj_b", a.proj.bias), res=x2,
-                      b_lo=self._lo(a, "proj", a.proj.weight))
+                      b_lo=a._w16("proj", a.proj.weight, part=1))
         xn2_32 = ops.layernorm(x1, self._f32("n2w", self.norm2.weight), self._f32("n2b", self.norm2.bias), self.norm2.eps, torch.float32)
         xn2, xn2_lo = ops.cast_pad(xn2_32, D, dt), ops.cast_pad(xn2_32, D, dt, part=1)
-        hpre32 = self._split_linear(xn2, xn2_lo, m._w16("fc1", m.fc1.weight), self._lo(m, "fc1", m.fc1.weight), m._f32("fc1_b", m.fc1.bias))
+        hpre32 = self._split_linear(xn2, xn2_lo, m._w16("fc1", m.fc1.weight), m._w16("fc1", m.fc1.weight, part=1), m._f32("fc1_b", m.fc1.bias))
         hpost, hpost_lo = ops.gelu_split(hpre32, dt)
-        x3 = self._split_linear(hpost, hpost_lo, m._w16("fc2", m.fc2.weight), self._lo(m, "fc2", m.fc2.weight),
+        x3 = self._split_linear(hpost, hpost_lo, m._w16("fc2", m.fc2.weight), m._w16("fc2", m.fc2.weight, part=1),
                                 m._f32("fc2_b", m.fc2.bias), res=x1)
         if not save:
             return x3, None
@@ -317,10 +313,6 @@ class MaskTransformer(_Packed):
         return _pack(self._cache, key, p,
                      lambda q: ops.cast_pad((q.float().t() if transpose else q.float()).contiguous(), dtype=dt, part=part))
 
-    def _lo(self, key: str, w: torch.Tensor):
-        return _pack(self._cache, key, w,
-                     lambda q: ops.cast_pad(q.reshape(q.shape[0], -1).contiguous().float(), dtype=config.operand_dtype, part=1))
-
     def _forward_core(self, tok: torch.Tensor, save: bool):
         """tok fp32 [B, N, d_encoder] -> masks fp32 NHWC [B, GS, GS, n_cls] (GS = sqrt(N)), saved state."""
         dt = config.operand_dtype
@@ -344,7 +336,7 @@ class MaskTransformer(_Packed):
         x = torch.empty((R, D), device=tok.device, dtype=torch.float32)
         if sp:
             ops.gemm_split(a16, ops.cast_pad(t_all.view(R, De), De, dt, part=1), self._w16("pd", pd.weight),
-                           self._lo("pd_lo", pd.weight), out=x, bias_n=self._f32("pd_b", pd.bias))
+                           self._w16("pd", pd.weight, part=1), out=x, bias_n=self._f32("pd_b", pd.bias))
         else:
             ops.gemm(a16, self._w16("pd", pd.weight), out=x, bias_n=self._f32("pd_b", pd.bias))
         x.view(B, RB, D)[:, N:] = self.cls_emb.detach().float()           # the class tokens behind every image's patches

@@ -18,7 +18,7 @@ from torch import nn
 from torch.nn.init import constant_, xavier_uniform_
 
 from .... import config, ops
-from ....dinov2.layers.blocks import _Packed, _pack
+from ....dinov2.layers.blocks import _Packed, derived
 
 
 def _is_power_of_2(n):
@@ -69,57 +69,38 @@ class MSDeformAttn(_Packed):
         constant_(self.output_proj.bias.data, 0.0)
 
     # ---- fused path used by CAViT / CACNN: 16-bit, already-normalised inputs ------------------
+    def _oa_packs(self, lo: bool):
+        """offsets and attention logits come from ONE GEMM: -> (w_oa 16-bit [M*L*P*3, D], b_oa fp32, rounding residual of w_oa | None)"""
+        so, aw = self.sampling_offsets, self.attention_weights
+        dt = config.operand_dtype
+        w32 = lambda: torch.cat([so.weight.detach(), aw.weight.detach()], 0).float().contiguous()
+        w_oa = derived(self._cache, "w_oa", (so.weight, aw.weight), lambda: ops.cast_pad(w32(), dtype=dt))
+        b_oa = derived(self._cache, "b_oa", (so.bias, aw.bias), lambda: torch.cat([so.bias.detach(), aw.bias.detach()]).float().contiguous())
+        w_lo = derived(self._cache, "w_oa.lo", (so.weight, aw.weight), lambda: ops.cast_pad(w32(), dtype=dt, part=1)) if lo else None
+        return w_oa, b_oa, w_lo
+
     def forward16(self, q16, feat16, ref, shapes_i32, starts_i32, B, Lq, Lin, *, res=None, scale_n=None):
         """q16 [B*Lq, D], feat16 [B*Lin, D] (16-bit) -> fp32 [B*Lq, D] = res + scale_n * output_proj(msda)."""
-        dt = config.operand_dtype
         M, L, P = self.n_heads, self.n_levels, self.n_points
-
-        srcs = (self.sampling_offsets.weight, self.attention_weights.weight, self.sampling_offsets.bias,
-                self.attention_weights.bias)
-        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in srcs) + (dt,)
-        if self._cache.get("oa_tag") != tag:  # offsets and attention logits come from ONE GEMM: [M*L*P*3, D]
-            with torch.no_grad():
-                w = torch.cat([srcs[0].detach(), srcs[1].detach()], 0).float().contiguous()
-                self._cache["w_oa"] = ops.cast_pad(w, dtype=dt)
-                self._cache["b_oa"] = torch.cat([srcs[2].detach(), srcs[3].detach()]).float().contiguous()
-            self._cache["oa_tag"] = tag
-        w_oa = self._cache["w_oa"]
         if config.precise_adapters_on():
             # 16 significant bits where tests/precision_probe.py puts the adapters' error in bf16 (weights 9.2e-4 and the sampled
             # rows 6.2e-4 of 1.43e-3 on the logits): the three weights as hi + lo halves, the sampled rows as a split A operand
-            if self._cache.get("oa_lo_tag") != tag:
-                with torch.no_grad():
-                    w = torch.cat([srcs[0].detach(), srcs[1].detach()], 0).float().contiguous()
-                    self._cache["w_oa_lo"] = ops.cast_pad(w, dtype=dt, part=1)
-                self._cache["oa_lo_tag"] = tag
-            lo = lambda key, p_: _pack(self._cache, key + ".lo", p_, lambda t: ops.cast_pad(t.reshape(t.shape[0], -1).contiguous().float(), dtype=dt, part=1))
+            w_oa, b_oa, w_oa_lo = self._oa_packs(True)
             value = ops.gemm(feat16, self._w16("wv", self.value_proj.weight), bias_n=self._f32("bv", self.value_proj.bias),
-                             b_lo=lo("wv", self.value_proj.weight))
-            offaw = ops.gemm(q16, w_oa, out_f32=True, bias_n=self._cache["b_oa"], b_lo=self._cache["w_oa_lo"])
+                             b_lo=self._w16("wv", self.value_proj.weight, part=1))
+            offaw = ops.gemm(q16, w_oa, out_f32=True, bias_n=b_oa, b_lo=w_oa_lo)
             samp, samp_lo = ops.msda_fwd(value.view(B, Lin, self.d_model), offaw, ref, shapes_i32, starts_i32, B, Lq, M, L, P, split=True)
             return ops.gemm(samp, self._w16("wo", self.output_proj.weight), out_f32=True, bias_n=self._f32("bo", self.output_proj.bias),
-                            scale_n=scale_n, res=res, a_lo=samp_lo, b_lo=lo("wo", self.output_proj.weight))
-        value = ops.gemm(feat16, self._w16("wv", self.value_proj.weight), bias_n=self._f32("bv", self.value_proj.bias))
-        offaw = ops.gemm(q16, w_oa, out_f32=True, bias_n=self._cache["b_oa"])
-        samp = ops.msda_fwd(value.view(B, Lin, self.d_model), offaw, ref, shapes_i32, starts_i32, B, Lq, M, L, P)
-        return ops.gemm(samp, self._w16("wo", self.output_proj.weight), out_f32=True,
-                        bias_n=self._f32("bo", self.output_proj.bias), scale_n=scale_n, res=res)
+                            scale_n=scale_n, res=res, a_lo=samp_lo, b_lo=self._w16("wo", self.output_proj.weight, part=1))
+        return self.forward16_train(q16, feat16, ref, shapes_i32, starts_i32, B, Lq, Lin, res=res, scale_n=scale_n)[0]
 
     # ---- training path (`train_adapters` mode): forward that keeps what the backward needs ------------------------
     def forward16_train(self, q16, feat16, ref, shapes_i32, starts_i32, B, Lq, Lin, *, res=None, scale_n=None):
-        """Same arithmetic as ``forward16`` -> (out fp32 [B*Lq, D], saved)."""
+        """The single-precision arithmetic of ``forward16`` -> (out fp32 [B*Lq, D], saved)."""
         M, L, P = self.n_heads, self.n_levels, self.n_points
-        srcs = (self.sampling_offsets.weight, self.attention_weights.weight, self.sampling_offsets.bias,
-                self.attention_weights.bias)
-        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in srcs) + (config.operand_dtype,)
-        if self._cache.get("oa_tag") != tag:
-            with torch.no_grad():
-                w = torch.cat([srcs[0].detach(), srcs[1].detach()], 0).float().contiguous()
-                self._cache["w_oa"] = ops.cast_pad(w, dtype=config.operand_dtype)
-                self._cache["b_oa"] = torch.cat([srcs[2].detach(), srcs[3].detach()]).float().contiguous()
-            self._cache["oa_tag"] = tag
+        w_oa, b_oa, _ = self._oa_packs(False)
         value = ops.gemm(feat16, self._w16("wv", self.value_proj.weight), bias_n=self._f32("bv", self.value_proj.bias))
-        offaw = ops.gemm(q16, self._cache["w_oa"], out_f32=True, bias_n=self._cache["b_oa"])
+        offaw = ops.gemm(q16, w_oa, out_f32=True, bias_n=b_oa)
         samp = ops.msda_fwd(value.view(B, Lin, self.d_model), offaw, ref, shapes_i32, starts_i32, B, Lq, M, L, P)
         out = ops.gemm(samp, self._w16("wo", self.output_proj.weight), out_f32=True,
                        bias_n=self._f32("bo", self.output_proj.bias), scale_n=scale_n, res=res)
@@ -150,7 +131,7 @@ class MSDeformAttn(_Packed):
         grads[pre + "sampling_offsets.weight"].copy_(G[:n_off]); grads[pre + "attention_weights.weight"].copy_(G[n_off:])
         cso = ops.reduce_rows(cs_oa, inv_scale)
         grads[pre + "sampling_offsets.bias"].copy_(cso[:n_off]); grads[pre + "attention_weights.bias"].copy_(cso[n_off:])
-        w_oaT = self._pack2("w_oaT", self.sampling_offsets.weight, self.attention_weights.weight, lambda: ops.cast_pad(
+        w_oaT = derived(self._cache, "w_oaT", (self.sampling_offsets.weight, self.attention_weights.weight), lambda: ops.cast_pad(
             torch.cat([self.sampling_offsets.weight.detach(), self.attention_weights.weight.detach()], 0).float().t().contiguous(),
             dtype=dt))
         dq = ops.gemm(doa16, w_oaT, out_f32=True)

@@ -23,6 +23,7 @@ from torch import nn
 
 from ... import config, droppath, ops
 from ... import lora as _lora_mod
+from ...packs import derived, tag_of  # noqa: F401  (re-exported: the modules that borrow ``_Packed`` take them from here)
 
 
 _VT_STREAMS = {}
@@ -43,12 +44,7 @@ _LS_POW2_REFRESH = 64   # Block._ls_pow2: parameter changes between two reads of
 
 def _pack(cache: dict, key: str, param: torch.Tensor, fn: Callable[[torch.Tensor], torch.Tensor]):
     """Cache a derived (16-bit / re-laid-out) copy of a parameter until the parameter changes."""
-    tag = (param.data_ptr(), param._version, getattr(param, "_asis_gen", 0), config.operand_dtype, param.device)
-    hit = cache.get(key)
-    if hit is None or hit[0] != tag:
-        with torch.no_grad():
-            cache[key] = (tag, fn(param.detach()))
-    return cache[key][1]
+    return derived(cache, key, (param,), lambda: fn(param.detach()))
 
 
 class _Packed(nn.Module):
@@ -56,39 +52,44 @@ class _Packed(nn.Module):
         super().__init__()
         self._cache = {}
 
-    def _w16(self, key: str, param: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """16-bit [out_features, K] operand of a weight; ``rows``: its rows in that order (the SwiGLU epilogue's interleave),
-        cached under ``key`` + ".sg" """
+    def _w16(self, key: str, param: torch.Tensor, rows: Optional[torch.Tensor] = None, part: int = 0) -> torch.Tensor:
+        """16-bit [out_features, K] operand of a weight (``part`` 1: the rounding residual of part 0, same layout); ``rows``: its
+        rows in that order (the SwiGLU epilogue's interleave).  Cached under ``key`` [+ ".sg"] [+ ".lo"]."""
         if rows is not None:
-            return _pack(self._cache, key + ".sg", param,
-                         lambda p: ops.cast_pad(p.reshape(p.shape[0], -1).float()[rows].contiguous(), dtype=config.operand_dtype))
-        return _pack(self._cache, key, param,
-                     lambda p: ops.cast_pad(p.reshape(p.shape[0], -1).contiguous().float(), dtype=config.operand_dtype))
+            key += ".sg"
+        if part:
+            key += ".lo"
+
+        def make(p):
+            w = p.reshape(p.shape[0], -1)
+            w = w.contiguous().float() if rows is None else w.float()[rows].contiguous()
+            return ops.cast_pad(w, dtype=config.operand_dtype, part=part)
+        return _pack(self._cache, key, param, make)
 
     def _w16lo(self, key: str, param: torch.Tensor) -> Optional[torch.Tensor]:
         """rounding residual of ``_w16`` (same layout) when ``config.precise_attention`` is on, else None"""
-        if not config.precise_attention:
-            return None
-        return _pack(self._cache, key + ".lo", param,
-                     lambda p: ops.cast_pad(p.reshape(p.shape[0], -1).contiguous().float(), dtype=config.operand_dtype, part=1))
+        return self._w16(key, param, part=1) if config.precise_attention else None
 
     def _f32(self, key: str, param: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         if param is None:
             return None
         return _pack(self._cache, key, param, lambda p: p.float().contiguous())
 
-    # ---- backward helpers shared by the ViT blocks and the adapter modules --------------------------------------
-    def _pack2(self, key: str, w: torch.Tensor, gamma: Optional[torch.Tensor], fn, extra=()):
-        """cache of a 16-bit operand derived from a weight and (optionally) a LayerScale vector (``extra``: further tensors it is
-        derived from — the LoRA matrices of an augmented pack)"""
-        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in (w, gamma, *extra) if t is not None) + \
-            (config.operand_dtype,)
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                self._cache[key] = (tag, fn())
-        return self._cache[key][1]
+    def _lin_ln_folded(self, key: str, lin: nn.Linear, norm: nn.LayerNorm, q_rows: int = 0, q_scale: float = 1.0):
+        """A linear layer behind a LayerNorm, for the LayerNorm-fold chain (config.ln_fold): -> (W' = W diag(norm.weight) as 16
+        bits, b' fp32 = b + W norm.bias, cs fp32 = row sums of the ROUNDED W' — what the MFMA really multiplies the mean with).
+        The first ``q_rows`` rows of W and b carry ``q_scale`` (the q rows' scale * log2(e) under config.fold_attn_scale)."""
+        def make():
+            w = lin.weight.detach().float().clone()
+            w[:q_rows] *= q_scale
+            b = lin.bias.detach().float().clone() if lin.bias is not None else torch.zeros(w.shape[0], device=w.device)
+            b[:q_rows] *= q_scale
+            b = b + w @ norm.bias.detach().float()
+            w16 = ops.cast_pad((w * norm.weight.detach().float()[None, :]).contiguous(), dtype=config.operand_dtype)
+            return w16, b.contiguous(), w16.float().sum(1).contiguous()
+        return derived(self._cache, key, (lin.weight, lin.bias, norm.weight, norm.bias), make, (q_scale,))
 
+    # ---- backward helpers shared by the ViT blocks and the adapter modules --------------------------------------
     def _wT16(self, key: str, w: torch.Tensor, gamma: Optional[torch.Tensor] = None, pow2: int = 0) -> torch.Tensor:
         """B operand of an input-gradient GEMM: (2^pow2 diag(gamma) W)^T as 16-bit [in_features, out_features]"""
         def make():
@@ -96,7 +97,7 @@ class _Packed(nn.Module):
             if gamma is not None:
                 wf = wf * (gamma.detach().float() * (2.0 ** pow2))[:, None]
             return ops.cast_pad(wf.t().contiguous(), dtype=config.operand_dtype)
-        return self._pack2(key + (f"@{pow2}" if pow2 else ""), w, gamma, make)
+        return derived(self._cache, key + (f"@{pow2}" if pow2 else ""), (w, gamma), make)
 
     def _ls_pow2(self, key: str, gamma: Optional[torch.Tensor]) -> int:
         """k with max|gamma| 2^k in [1, 2): the power-of-two scale a LayerScale'd branch gradient carries through its 16-bit
@@ -123,7 +124,8 @@ class _Packed(nn.Module):
         m = float(gamma.detach().abs().max())
         k = 0 if not (m > 0.0 and m < float("inf")) else -int(math.floor(math.log2(m)))
         if ent is not None and ent[0] == tag and ent[1][0] != k:
-            for stale in [c for c in self._cache if c.endswith(f"@{ent[1][0]}") or c.endswith(f"@{-ent[1][0]}")]:
+            old = (str(ent[1][0]), str(-ent[1][0]))      # compared with the whole suffix behind the last "@"
+            for stale in [c for c in self._cache if "@" in c and c.rsplit("@", 1)[-1] in old]:
                 del self._cache[stale]        # the 2^k-scaled weight packs of the old k
         self._cache[key] = (tag, [k, ver, gen, 0])
         return k
@@ -250,11 +252,11 @@ class Attention(_Packed):
         dt = config.operand_dtype
         f = lambda t: t.detach().float()
         wf32 = lambda: _lora_mod.pack_wf(f(w), f(lo.Bq), f(lo.Bv), lo.scale).contiguous()
-        wf = self._pack2("qkv.lora.wf", w, None, lambda: ops.cast_pad(wf32(), dtype=dt), extra=(lo.Bq, lo.Bv))
+        wf = derived(self._cache, "qkv.lora.wf", (w, lo.Bq, lo.Bv), lambda: ops.cast_pad(wf32(), dtype=dt))
         wf_lo = None
         if config.precise_attention:   # the lo plane ``_w16lo`` supplies for the plain weight, of the whole augmented matrix
-            wf_lo = self._pack2("qkv.lora.wf.lo", w, None, lambda: ops.cast_pad(wf32(), dtype=dt, part=1), extra=(lo.Bq, lo.Bv))
-        wd = self._pack2("qkv.lora.wd", lo.A, None, lambda: ops.cast_pad(_lora_mod.pack_wd_fwd(f(lo.A)).contiguous(), dtype=dt))
+            wf_lo = derived(self._cache, "qkv.lora.wf.lo", (w, lo.Bq, lo.Bv), lambda: ops.cast_pad(wf32(), dtype=dt, part=1))
+        wd = derived(self._cache, "qkv.lora.wd", (lo.A,), lambda: ops.cast_pad(_lora_mod.pack_wd_fwd(f(lo.A)).contiguous(), dtype=dt))
         return wf, wf_lo, wd
 
     def _lora_packs_bwd(self):
@@ -262,10 +264,9 @@ class Attention(_Packed):
         lo, w = self._lora, self.qkv.weight
         dt = config.operand_dtype
         f = lambda t: t.detach().float()
-        wbt = self._pack2("qkv.lora.wbt", w, None, lambda: ops.cast_pad(_lora_mod.pack_wbt(f(w), f(lo.A)).contiguous(), dtype=dt),
-                          extra=(lo.A,))
-        wd = self._pack2("qkv.lora.wdb", lo.Bq, None,
-                         lambda: ops.cast_pad(_lora_mod.pack_wd_bwd(f(lo.Bq), f(lo.Bv), lo.scale).contiguous(), dtype=dt), extra=(lo.Bv,))
+        wbt = derived(self._cache, "qkv.lora.wbt", (w, lo.A), lambda: ops.cast_pad(_lora_mod.pack_wbt(f(w), f(lo.A)).contiguous(), dtype=dt))
+        wd = derived(self._cache, "qkv.lora.wdb", (lo.Bq, lo.Bv),
+                     lambda: ops.cast_pad(_lora_mod.pack_wd_bwd(f(lo.Bq), f(lo.Bv), lo.scale).contiguous(), dtype=dt))
         return wbt, wd
 
     def _qkv_folded(self):
@@ -289,26 +290,6 @@ class Attention(_Packed):
             bias = _pack(self._cache, "qkv_b.fold", self.qkv.bias, lambda p: scaled(p).reshape(-1))
         return w, bias, wlo
 
-    def _qkv_ln_folded(self, norm: nn.LayerNorm):
-        """qkv weight with diag(norm.weight) folded in (and the q rows' scale * log2(e) when config.fold_attn_scale), for the
-        LayerNorm-fold chain (config.ln_fold): -> (W' 16-bit [3D, D], b' fp32 [3D] = b + W norm.bias, cs fp32 [3D] = row sums
-        of the ROUNDED W' — what the MFMA really multiplies the mean with)."""
-        c = self.scale * 1.4426950408889634 if config.fold_attn_scale else 1.0
-        D = self.qkv.weight.shape[1]
-        ps = [p for p in (self.qkv.weight, self.qkv.bias, norm.weight, norm.bias) if p is not None]
-        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in ps) + (config.operand_dtype, c)
-        hit = self._cache.get("qkv.lnfold")
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                w = self.qkv.weight.detach().float().clone()
-                w[:D] *= c
-                b = self.qkv.bias.detach().float().clone() if self.qkv.bias is not None else torch.zeros(3 * D, device=w.device)
-                b[:D] *= c
-                b = b + w @ norm.bias.detach().float()
-                w16 = ops.cast_pad((w * norm.weight.detach().float()[None, :]).contiguous(), dtype=config.operand_dtype)
-                self._cache["qkv.lnfold"] = (tag, (w16, b.contiguous(), w16.float().sum(1).contiguous()))
-        return self._cache["qkv.lnfold"][1]
-
     def attend(self, xn: torch.Tensor, B: int, N: int) -> torch.Tensor:
         """xn: 16-bit [B*N, D] (already normalised) -> 16-bit attention output [B*N, D] (before proj)."""
         return self.attend_rows(xn, [(B, N)])[0]
@@ -320,58 +301,35 @@ class Attention(_Packed):
         ``ln`` = (norm1, mr): ``xn`` is the hi plane of the UN-normalised stream and mr its per-row (mean, rstd): the
         LayerNorm is folded into the projection weights and undone in the GEMM epilogues (config.ln_fold)."""
         D = xn.shape[1]
-        if ln is not None:
+        # the two forms differ in the operands of the q|k and V^T GEMMs, in the column granule of the V^T epilogue (and in what
+        # happens when the spare rows behind ``xn`` do not cover it) and in whether V^T is always one stacked buffer
+        fold = ln is not None
+        if fold:
             norm, mr = ln
-            w, bias, cs = self._qkv_ln_folded(norm)
+            c = self.scale * 1.4426950408889634 if config.fold_attn_scale else 1.0
+            w, bias, cs = self._lin_ln_folded("qkv.lnfold", self.qkv, norm, D, c)
             scale = None if config.fold_attn_scale else self.scale
-            o = torch.empty((xn.shape[0], D), device=xn.device, dtype=xn.dtype)
-            o_lo = torch.empty_like(o) if config.split_attn_out else None
-            one_launch = len(segs) == 2
-            ldv_all = (max(n for _, n in segs) + 63) // 64 * 64
-            vt_all = torch.empty((sum(b for b, _ in segs), D, ldv_all), device=xn.device, dtype=xn.dtype)
-            spare = xn.untyped_storage().nbytes() // xn.element_size() - (xn.storage_offset() + xn.shape[0] * D)
-            side = None
-            if one_launch and config.vt_stream:
-                main = torch.cuda.current_stream()
-                side = _vt_side_stream(xn.device)
-                side.wait_stream(main)
-            else:
-                qk = ops.gemm(xn, w[: 2 * D], bias_n=bias[: 2 * D], ln=(mr, cs[: 2 * D], False))
-            r0 = b0 = 0
-            for B, N in segs:
-                r1 = r0 + B * N
-                vt = vt_all[b0:b0 + B]
-                N4 = (N + 7) // 8 * 8      # the 16-bit epilogue that undoes the LayerNorm stores 8 columns per lane
-                if spare < (N4 - N) * D:
-                    raise ValueError("attend_rows(ln=...): the hi plane needs 8 spare rows behind it")
-                with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                    ops.gemm(w[2 * D:], xn[r0:r1].as_strided((B, N4, D), (N * D, D, 1)),
-                             out=vt.as_strided((B, D, N4), (D * ldv_all, ldv_all, 1)), bias_m=bias[2 * D:], ln=(mr[r0:], cs[2 * D:], True))
-                if not one_launch:
-                    ops.attention_fwd(qk[r0:r1, :D], qk[r0:r1, D:], vt, B, self.num_heads, N, scale, out=o[r0:r1],
-                                      out_lo=None if o_lo is None else o_lo[r0:r1])
-                r0, b0 = r1, b0 + B
-            if side is not None:
-                qk = ops.gemm(xn, w[: 2 * D], bias_n=bias[: 2 * D], ln=(mr, cs[: 2 * D], False))
-                main.wait_stream(side)
-                mr.record_stream(side)
-            if one_launch:
-                (B1, N1), (B2, N2) = segs
-                ops.attention_fwd_seg(qk[:, :D], qk[:, D:], vt_all, B1, N1, B2, N2, self.num_heads, scale, out=o, out_lo=o_lo)
-            if r0 != xn.shape[0]:
-                raise ValueError("attend_rows: segments do not cover the rows")
-            return o, o_lo
-        if config.fold_attn_scale:
-            w, bias, wlo = self._qkv_folded()       # q rows carry scale * log2(e): asis_attention_fwd_prescaled
-            scale = None
+            qk_kw = dict(bias_n=bias[: 2 * D], ln=(mr, cs[: 2 * D], False))
+            vt_kw = lambda r0: dict(bias_m=bias[2 * D:], ln=(mr[r0:], cs[2 * D:], True))
+            granule, strict = 8, True     # the 16-bit epilogue that undoes the LayerNorm stores 8 columns per lane: no fallback
         else:
-            w = self._w16("qkv", self.qkv.weight)  # [3D, D] rows q | k | v
-            bias = self._f32("qkv_b", self.qkv.bias)
-            wlo = self._w16lo("qkv", self.qkv.weight)
-            scale = self.scale
+            if config.fold_attn_scale:
+                w, bias, wlo = self._qkv_folded()       # q rows carry scale * log2(e): asis_attention_fwd_prescaled
+                scale = None
+            else:
+                w = self._w16("qkv", self.qkv.weight)  # [3D, D] rows q | k | v
+                bias = self._f32("qkv_b", self.qkv.bias)
+                wlo = self._w16lo("qkv", self.qkv.weight)
+                scale = self.scale
+            qk_kw = dict(bias_n=None if bias is None else bias[: 2 * D], b_lo=None if wlo is None else wlo[: 2 * D])
+            vt_kw = lambda r0: dict(bias_m=None if bias is None else bias[2 * D:], a_lo=None if wlo is None else wlo[2 * D:])
+            # N rounded up to 4 keeps the vector epilogue (N = 1765 fell to the scalar one: 101 vs 69 us); the extra
+            # columns land in V^T's pad region, which the attention kernel zeroes in registers, and their operand rows
+            # are the first tokens of the next image (the last image reads the spare rows behind ``xn``)
+            granule, strict = 4, False
         o = torch.empty((xn.shape[0], D), device=xn.device, dtype=xn.dtype)
         o_lo = torch.empty_like(o) if config.split_attn_out else None   # rounding residual of o: proj's split A operand
-        if config.fused_qkv and len(segs) <= 2:
+        if not fold and config.fused_qkv and len(segs) <= 2:
             # `attention.py:58`: one qkv GEMM; the attention kernel reads V row-major out of it (asis_attention_fwd_qkv)
             if sum(b * n for b, n in segs) != xn.shape[0]:
                 raise ValueError("attend_rows: segments do not cover the rows")
@@ -380,36 +338,39 @@ class Attention(_Packed):
             return o, o_lo
         one_launch = len(segs) == 2
         ldv_all = (max(n for _, n in segs) + 63) // 64 * 64
-        vt_all = torch.empty((sum(b for b, _ in segs), D, ldv_all), device=xn.device, dtype=xn.dtype) if one_launch else None
+        stacked = one_launch or fold        # V^T of all segments in one buffer; else one per segment with its own ldvt
+        vt_all = torch.empty((sum(b for b, _ in segs), D, ldv_all), device=xn.device, dtype=xn.dtype) if stacked else None
         spare = xn.untyped_storage().nbytes() // xn.element_size() - (xn.storage_offset() + xn.shape[0] * D)
         # stacked form: the V^T GEMMs go to a side stream, the q|k GEMM stays on the compute stream (config.vt_stream)
         side = None
-        if one_launch and config.vt_stream and xn.is_cuda:
+        if one_launch and config.vt_stream and (fold or xn.is_cuda):
             main = torch.cuda.current_stream()
             side = _vt_side_stream(xn.device)
             side.wait_stream(main)      # xn, and whatever read the recycled blocks of vt_all
         else:
-            qk = ops.gemm(xn, w[: 2 * D], bias_n=None if bias is None else bias[: 2 * D], b_lo=None if wlo is None else wlo[: 2 * D])
+            qk = ops.gemm(xn, w[: 2 * D], **qk_kw)
         r0 = b0 = 0
         for B, N in segs:
             r1 = r0 + B * N
-            ldvt = ldv_all if one_launch else (N + 63) // 64 * 64
-            vt = vt_all[b0:b0 + B] if one_launch else torch.empty((B, D, ldvt), device=xn.device, dtype=xn.dtype)
-            # N rounded up to 4 keeps the vector epilogue (N = 1765 fell to the scalar one: 101 vs 69 us); the extra
-            # columns land in V^T's pad region, which the attention kernel zeroes in registers, and their operand rows
-            # are the first tokens of the next image (the last image reads the spare rows behind ``xn``)
-            N4 = (N + 3) // 4 * 4 if spare >= 4 * D else N
+            ldvt = ldv_all if stacked else (N + 63) // 64 * 64
+            vt = vt_all[b0:b0 + B] if stacked else torch.empty((B, D, ldvt), device=xn.device, dtype=xn.dtype)
+            N4 = (N + granule - 1) // granule * granule
+            if strict and spare < (N4 - N) * D:
+                raise ValueError("attend_rows(ln=...): the hi plane needs 8 spare rows behind it")
+            if not strict and spare < 4 * D:
+                N4 = N
             with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
                 ops.gemm(w[2 * D:], xn[r0:r1].as_strided((B, N4, D), (N * D, D, 1)),
-                         out=vt.as_strided((B, D, N4), (D * ldvt, ldvt, 1)), bias_m=None if bias is None else bias[2 * D:],
-                         a_lo=None if wlo is None else wlo[2 * D:])
+                         out=vt.as_strided((B, D, N4), (D * ldvt, ldvt, 1)), **vt_kw(r0))
             if not one_launch:
                 ops.attention_fwd(qk[r0:r1, :D], qk[r0:r1, D:], vt, B, self.num_heads, N, scale, out=o[r0:r1],
                                   out_lo=None if o_lo is None else o_lo[r0:r1])
             r0, b0 = r1, b0 + B
         if side is not None:
-            qk = ops.gemm(xn, w[: 2 * D], bias_n=None if bias is None else bias[: 2 * D], b_lo=None if wlo is None else wlo[: 2 * D])
+            qk = ops.gemm(xn, w[: 2 * D], **qk_kw)
             main.wait_stream(side)
+            if fold:
+                mr.record_stream(side)
         if one_launch:  # both token batches in one launch (fewer partial rounds of workgroups)
             (B1, N1), (B2, N2) = segs
             ops.attention_fwd_seg(qk[:, :D], qk[:, D:], vt_all, B1, N1, B2, N2, self.num_heads, scale, out=o, out_lo=o_lo)
@@ -495,16 +456,21 @@ class Block(_Packed):
             x2 = x2.float().contiguous()
         return self.forward_rows(x2, [(B, N)]).view(B, N, D)
 
-    def _w16lo_any(self, owner, key: str, w: torch.Tensor, rows: Optional[torch.Tensor] = None):
-        """rounding residual of ``owner._w16(key, w, rows)`` (same layout), whatever config.precise_attention says (precise_level 2)"""
-        sel = (lambda t: t) if rows is None else (lambda t: t[rows])
-        return _pack(owner._cache, key + (".sg" if rows is not None else "") + ".lo_any", w,
-                     lambda p: ops.cast_pad(sel(p.reshape(p.shape[0], -1).float()).contiguous(), dtype=config.operand_dtype, part=1))
+    def _gammas(self, raw: bool = False):
+        """(ls1.gamma, ls2.gamma) as fp32 epilogue operands (``raw``: the parameters themselves); None where there is no LayerScale"""
+        g1 = self.ls1.gamma if isinstance(self.ls1, LayerScale) else None
+        g2 = self.ls2.gamma if isinstance(self.ls2, LayerScale) else None
+        return (g1, g2) if raw else (self._f32("g1", g1), self._f32("g2", g2))
+
+    def _ffn(self):
+        """(lin_in, key_in, lin_out, key_out) of the Mlp (fc1, fc2) or the SwiGLU FFN (w12, w3): keys as in ``state_dict``"""
+        m = self.mlp
+        return (m.fc1, "fc1", m.fc2, "fc2") if isinstance(m, Mlp) else (m.w12, "w12", m.w3, "w3")
 
     def _w16mx_any(self, owner, key: str, w: torch.Tensor, rows: Optional[torch.Tensor] = None):
         """(MX plane of the weight's (hi, lo) pair — weight side: (lo8, hi8) per element —, its absolute maximum [1])"""
         return _pack(owner._cache, key + (".sg" if rows is not None else "") + ".mx_any", w,
-                     lambda p: ops.mx_from_pair(owner._w16(key, w, rows), self._w16lo_any(owner, key, w, rows), wside=True))
+                     lambda p: ops.mx_from_pair(owner._w16(key, w, rows), owner._w16(key, w, rows, part=1), wside=True))
 
     def _mx_ok(self, owner, key: str, lin: nn.Linear, M: int) -> bool:
         N, K = lin.weight.shape
@@ -520,7 +486,7 @@ class Block(_Packed):
             a_pl, amax_a = a_mx if a_mx is not None else ops.mx_from_pair(a_hi, a_lo)
             w_mx, amax_w = self._w16mx_any(owner, key, lin.weight, rows)
             return ops.gemm(a_hi, w, a_lo=a_pl, b_lo=w_mx, mx=(amax_a, amax_w), **kw)
-        return ops.gemm(a_hi, w, a_lo=a_lo, b_lo=self._w16lo_any(owner, key, lin.weight, rows), **kw)
+        return ops.gemm(a_hi, w, a_lo=a_lo, b_lo=owner._w16(key, lin.weight, rows, part=1), **kw)
 
     def _ln_split(self, key: str, norm: nn.LayerNorm, x2: torch.Tensor, mx: bool):
         """LayerNorm output as a split-precision A operand: (hi, lo, None), or (hi, None, (MX plane, amax bound)) in ONE pass"""
@@ -528,8 +494,8 @@ class Block(_Packed):
         w, b = self._f32(key + "w", norm.weight), self._f32(key + "b", norm.bias)
         if mx:
             # |LN(x)_i| <= sqrt(D - 1) |w_i| + |b_i|: a bound, not the maximum (asis_layernorm_mx: costs nothing at e4m3's range)
-            amax = _pack(self._cache, key + ".amax", norm.weight,
-                         lambda p: ((x2.shape[1] - 1) ** 0.5 * p.float().abs().max() + norm.bias.detach().float().abs().max()).reshape(1).contiguous())
+            amax = derived(self._cache, key + ".amax", (norm.weight, norm.bias), lambda: (
+                (x2.shape[1] - 1) ** 0.5 * norm.weight.detach().float().abs().max() + norm.bias.detach().float().abs().max()).reshape(1).contiguous())
             hi, pl = ops.layernorm_mx(x2, w, b, norm.eps, dt, amax)
             return hi, None, (pl, amax)
         xn32 = ops.layernorm(x2, w, b, norm.eps, torch.float32)
@@ -543,8 +509,7 @@ class Block(_Packed):
         R = x2.shape[0]
         dt = config.operand_dtype
         a, m = self.attn, self.mlp
-        g1 = self._f32("g1", self.ls1.gamma) if isinstance(self.ls1, LayerScale) else None
-        g2 = self._f32("g2", self.ls2.gamma) if isinstance(self.ls2, LayerScale) else None
+        g1, g2 = self._gammas()
         parts = config.precise_parts      # which of the four linear layers run split (default: all)
         n1w, n1b = self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias)
         fold_q = config.fold_attn_scale and "qkv" not in parts and _PRECISE_FOLD_Q
@@ -582,8 +547,7 @@ class Block(_Packed):
         else:
             x1 = self._split_lin(a, "proj", a.proj, o, o_lo, **pkw) if o_lo is not None else ops.gemm(o, a._w16("proj", a.proj.weight), **pkw)
         n2w, n2b = self._f32("n2w", self.norm2.weight), self._f32("n2b", self.norm2.bias)
-        lin_in, k_in = (m.fc1, "fc1") if isinstance(m, Mlp) else (m.w12, "w12")
-        lin_out, k_out = (m.fc2, "fc2") if isinstance(m, Mlp) else (m.w3, "w3")
+        lin_in, k_in, lin_out, k_out = self._ffn()
         ikw = dict(out_f32=True, bias_n=m._f32(k_in + "_b", lin_in.bias))
         split_out = "fc2" in parts
         mx_in = "fc1" in parts and self._mx_ok(m, k_in, lin_in, R)
@@ -614,19 +578,6 @@ class Block(_Packed):
             return self._split_lin(m, k_out, lin_out, h, h_lo, **okw)
         return ops.gemm(h, m._w16(k_out, lin_out.weight), **okw)
 
-    def _lin_ln_folded(self, key: str, lin: nn.Linear, norm: nn.LayerNorm):
-        """(W diag(norm.weight) as 16 bits, b + W norm.bias, row sums of the rounded W') of a linear layer behind a LayerNorm"""
-        ps = [p for p in (lin.weight, lin.bias, norm.weight, norm.bias) if p is not None]
-        tag = tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in ps) + (config.operand_dtype,)
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                w = lin.weight.detach().float()
-                b = (lin.bias.detach().float() if lin.bias is not None else torch.zeros(w.shape[0], device=w.device)) + w @ norm.bias.detach().float()
-                w16 = ops.cast_pad((w * norm.weight.detach().float()[None, :]).contiguous(), dtype=config.operand_dtype)
-                self._cache[key] = (tag, (w16, b.contiguous(), w16.float().sum(1).contiguous()))
-        return self._cache[key][1]
-
     def fold_ok(self, R: int, segs) -> bool:
         """the LayerNorm-fold chain (config.ln_fold) applies to this block on ``R`` stacked rows: every GEMM involved lands on
         a kernel that implements the epilogue fields (ops.ln_fold_supported)"""
@@ -647,7 +598,7 @@ class Block(_Packed):
         statistics for the NEXT block's norm1: same eps, `vision_transformer.py:89`)."""
         dt = config.operand_dtype
         a, m = self.attn, self.mlp
-        g1, g2 = self._f32("g1", self.ls1.gamma), self._f32("g2", self.ls2.gamma)
+        g1, g2 = self._gammas()
         if isinstance(xin, tuple):
             hi, lo, mr = xin
             R, D = hi.shape
@@ -666,9 +617,10 @@ class Block(_Packed):
         ops.gemm(o, a._w16("proj", a.proj.weight), out=x1h, out_lo=x1l, rowstats=st, bias_n=a._f32("proj_b", a.proj.bias), scale_n=g1,
                  a_lo=o_lo, **res_kw)
         mr1 = ops.ln_stats_finalize(st, D, self.norm2.eps)
-        w1, b1, cs1 = self._lin_ln_folded("fc1.lnfold", m.fc1, self.norm2)
+        lin_in, k_in, lin_out, k_out = self._ffn()      # fold_ok: the Mlp
+        w1, b1, cs1 = self._lin_ln_folded(k_in + ".lnfold", lin_in, self.norm2)
         h = ops.gemm(x1h, w1, bias_n=b1, act=ops.ACT_GELU, ln=(mr1, cs1, False))
-        w2, b2 = m._w16("fc2", m.fc2.weight), m._f32("fc2_b", m.fc2.bias)
+        w2, b2 = m._w16(k_out, lin_out.weight), m._f32(k_out + "_b", lin_out.bias)
         if not planes_out:
             return ops.gemm(h, w2, out_f32=True, bias_n=b2, scale_n=g2, res16=(x1h, x1l))
         x3h = torch.empty((R + 8, D), device=o.device, dtype=dt)[:R]      # spare rows: the next block's V^T GEMM reads past the end
@@ -687,8 +639,7 @@ class Block(_Packed):
             return self._forward_rows_precise(x2, segs)
         D = x2.shape[1]
         dt = config.operand_dtype
-        g1 = self._f32("g1", self.ls1.gamma) if isinstance(self.ls1, LayerScale) else None
-        g2 = self._f32("g2", self.ls2.gamma) if isinstance(self.ls2, LayerScale) else None
+        g1, g2 = self._gammas()
         xn = torch.empty((x2.shape[0] + 8, D), device=x2.device, dtype=dt)[: x2.shape[0]]   # 8 spare rows: see attend_rows
         ops.layernorm(x2, self._f32("n1w", self.norm1.weight), self._f32("n1b", self.norm1.bias), self.norm1.eps, dt, out=xn)
         o, o_lo = self.attn.attend_rows(xn, segs)
@@ -698,19 +649,15 @@ class Block(_Packed):
         xn2 = ops.layernorm(x1, self._f32("n2w", self.norm2.weight), self._f32("n2b", self.norm2.bias),
                             self.norm2.eps, dt)
         m = self.mlp
+        lin_in, k_in, lin_out, k_out = self._ffn()
         if isinstance(m, Mlp):
-            h = ops.gemm(xn2, m._w16("fc1", m.fc1.weight), bias_n=m._f32("fc1_b", m.fc1.bias), act=ops.ACT_GELU)
-            x3 = ops.gemm(h, m._w16("fc2", m.fc2.weight), out_f32=True, bias_n=m._f32("fc2_b", m.fc2.bias),
-                          scale_n=g2, res=x1)
+            h = ops.gemm(xn2, m._w16(k_in, lin_in.weight), bias_n=m._f32(k_in + "_b", lin_in.bias), act=ops.ACT_GELU)
+        elif ops.swiglu_fused_ok(xn2.shape[0], lin_in.out_features // 2, lin_in.in_features, False, False):
+            h = ops.gemm(xn2, m._w16(k_in, lin_in.weight, m.sg_rows()), bias_n=m.sg_bias(), act=ops.ACT_SILU_MUL)
         else:
-            if ops.swiglu_fused_ok(xn2.shape[0], m.w12.out_features // 2, m.w12.in_features, False, False):
-                h = ops.gemm(xn2, m._w16("w12", m.w12.weight, m.sg_rows()), bias_n=m.sg_bias(), act=ops.ACT_SILU_MUL)
-            else:
-                h12 = ops.gemm(xn2, m._w16("w12", m.w12.weight), out_f32=True, bias_n=m._f32("w12_b", m.w12.bias))
-                h = ops.swiglu(h12, dt)
-            x3 = ops.gemm(h, m._w16("w3", m.w3.weight), out_f32=True, bias_n=m._f32("w3_b", m.w3.bias),
-                          scale_n=g2, res=x1)
-        return x3
+            h12 = ops.gemm(xn2, m._w16(k_in, lin_in.weight), out_f32=True, bias_n=m._f32(k_in + "_b", lin_in.bias))
+            h = ops.swiglu(h12, dt)
+        return ops.gemm(h, m._w16(k_out, lin_out.weight), out_f32=True, bias_n=m._f32(k_out + "_b", lin_out.bias), scale_n=g2, res=x1)
 
     # ---- training path (block.py:89-114 under autograd; BASELINE config 4 / north_star "forward/backward") ----------
     def forward_train(self, x: torch.Tensor, keep=None):
@@ -775,8 +722,7 @@ class Block(_Packed):
         dt = config.operand_dtype
         D = x2.shape[1]
         m = self.mlp
-        g1 = self._f32("g1", self.ls1.gamma) if isinstance(self.ls1, LayerScale) else None
-        g2 = self._f32("g2", self.ls2.gamma) if isinstance(self.ls2, LayerScale) else None
+        g1, g2 = self._gammas()
         a = self.attn
         segs = list(segs)
         if sum(B * N for B, N in segs) != x2.shape[0]:
@@ -812,14 +758,14 @@ class Block(_Packed):
         okw = dict(out_f32=True, scale_n=g2)
         if kf is None:
             okw["res"] = x1
+        lin_in, k_in, lin_out, k_out = self._ffn()
         if isinstance(m, Mlp):
-            hpre = ops.gemm(xn2, m._w16("fc1", m.fc1.weight), bias_n=m._f32("fc1_b", m.fc1.bias))
+            hpre = ops.gemm(xn2, m._w16(k_in, lin_in.weight), bias_n=m._f32(k_in + "_b", lin_in.bias))
             hpost = ops.gelu16(hpre)
-            x3 = ops.gemm(hpost, m._w16("fc2", m.fc2.weight), bias_n=m._f32("fc2_b", m.fc2.bias), **okw)
         else:  # SwiGLU (ViT-g): hpre = the fp32 [x1 | x2] of w12, hpost = silu(x1) * x2
-            hpre = ops.gemm(xn2, m._w16("w12", m.w12.weight), out_f32=True, bias_n=m._f32("w12_b", m.w12.bias))
+            hpre = ops.gemm(xn2, m._w16(k_in, lin_in.weight), out_f32=True, bias_n=m._f32(k_in + "_b", lin_in.bias))
             hpost = ops.swiglu(hpre, dt)
-            x3 = ops.gemm(hpost, m._w16("w3", m.w3.weight), bias_n=m._f32("w3_b", m.w3.bias), **okw)
+        x3 = ops.gemm(hpost, m._w16(k_out, lin_out.weight), bias_n=m._f32(k_out + "_b", lin_out.bias), **okw)
         if kf is not None:
             x3 = ops.scaled_index_add(x1, x3, kf)
         saved = (x2, xn, qkv, o, lse, x1, xn2, hpre, hpost, segs)
@@ -837,8 +783,7 @@ class Block(_Packed):
         dt = config.operand_dtype
         D = x2.shape[1]
         a, m = self.attn, self.mlp
-        ls1 = self.ls1.gamma if isinstance(self.ls1, LayerScale) else None
-        ls2 = self.ls2.gamma if isinstance(self.ls2, LayerScale) else None
+        ls1, ls2 = self._gammas(raw=True)
         pre = prefix + "." if prefix else ""
         # a ``grads`` dict that holds the block's LoRA names: those three gradients are written and every dense weight gradient,
         # the norm gradients and the column sums are skipped (``grads`` = None from here on)
@@ -853,10 +798,9 @@ class Block(_Packed):
         k1, k2 = self._ls_pow2("ls1.k", ls1), self._ls_pow2("ls2.k", ls2)
         inv1, inv2 = inv_scale * 2.0 ** -k1, inv_scale * 2.0 ** -k2
         # ---- MLP branch: out = x1 + ls2 * fc2(gelu(fc1(LN2(x1)))) ----
-        if isinstance(m, Mlp):
-            lin_out, lin_in, n_out, n_in, act_bwd = m.fc2, m.fc1, "mlp.fc2", "mlp.fc1", ops.gelu16
-        else:
-            lin_out, lin_in, n_out, n_in, act_bwd = m.w3, m.w12, "mlp.w3", "mlp.w12", ops.swiglu_bwd
+        lin_in, k_in, lin_out, k_out = self._ffn()
+        n_in, n_out = "mlp." + k_in, "mlp." + k_out
+        act_bwd = ops.gelu16 if isinstance(m, Mlp) else ops.swiglu_bwd
         if kf is not None and kf.empty:      # the branch saw no sample: no parameter gradient, the stream gradient passes
             dx1 = dres
             self._zero_grads(grads, [pre + n_out, pre + n_in, pre + "norm2"], pre + "ls2.gamma")

@@ -24,6 +24,8 @@ from typing import Dict, Iterator, List, Optional, Tuple
 import torch
 from torch import nn
 
+from .packs import tag_of
+
 RANKS = (4, 8, 16, 32)
 PAD = 64                    # ops.LORA_PAD: padded width of the stacked rank dimension
 
@@ -75,7 +77,7 @@ def merged_weight(W: torch.Tensor, A: torch.Tensor, Bq: torch.Tensor, Bv: torch.
 
 
 def _tag(*ts) -> tuple:
-    return tuple((t.data_ptr(), t._version, getattr(t, "_asis_gen", 0)) for t in ts)
+    return tag_of(ts)
 
 
 class LoRAHandle:
@@ -190,7 +192,7 @@ class LoRA:
                 attn = blk.attn
                 w = attn.qkv.weight
                 base = w.data
-                tag = _tag(w, h.A, h.Bq, h.Bv) + (base.device,)
+                tag = _tag(w, h.A, h.Bq, h.Bv)
                 if h.merged_w is None or h.merged_tag != tag:
                     with torch.no_grad():
                         m = merged_weight(base.detach().float(), h.A.detach().float(), h.Bq.detach().float(), h.Bv.detach().float(),
@@ -200,7 +202,7 @@ class LoRA:
                         else:
                             h.merged_w.copy_(m)
                     w._asis_gen = getattr(w, "_asis_gen", 0) + 1
-                    h.merged_tag = _tag(w, h.A, h.Bq, h.Bv) + (base.device,)
+                    h.merged_tag = _tag(w, h.A, h.Bq, h.Bv)
                 undo.append((attn, w, base, attn._cache, attn.__dict__.get("_lora")))
                 w.data = h.merged_w
                 attn._cache = h.merged_cache
