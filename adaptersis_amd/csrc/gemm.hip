@@ -272,15 +272,38 @@ const char* const kFormNames[F_COUNT] = {ASIS_GEMM_FORMS(X)};
 struct GemmPlan {
   int form, grid_x, grid_y, block;
   int group_m;   // second kernel argument of the large-tile forms: GemmOpts::group_m | 0x10000 (fp32 slab epilogue, lab)
+  const char* why;   // of a refusal that has a message of its own (the vector-epilogue requirement), else null
 };
+// The first property that keeps batch entry / K part bz off the vector epilogue (gemm_big.h: gemm_big_vec_epilogue is the
+// predicate; this only words its refusal).
+const char* vec_epilogue_misfit(const asis_gemm_desc& d, int bz) {
+  auto off16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
+  if (d.N % 4 || d.ldc % 4) return "N and ldc must be multiples of 4";
+  if (off16(d.C)) return "C must be 16-byte aligned";
+  if (bz > 0 && d.strideC % 4) return "strideC must be a multiple of 4";
+  if (d.res && d.ldr % 4) return "ldr must be a multiple of 4";
+  if (d.res && off16(d.res + (int64_t)bz * d.strideR)) return "res must be 16-byte aligned in every batch entry (strideR a multiple of 4)";
+  if (d.bias_n && off16(d.bias_n)) return "bias_n must be 16-byte aligned";
+  if (d.scale_n && off16(d.scale_n)) return "scale_n must be 16-byte aligned";
+  return "an operand is off its 16-byte boundary";
+}
 
-// Which form a validated descriptor runs on, and its launch geometry; ASIS_EINVAL when no form takes it.  Pure: no HIP call,
-// pointers are only tested for null and alignment.  The order of the cascade is behaviour.
+// Which form a validated descriptor runs on, and its launch geometry; ASIS_EINVAL when no form takes it (p->why: a refusal with
+// a message of its own).  Pure: no HIP call, pointers are only tested for null and alignment.  The order of the cascade is behaviour.
 int gemm_plan(const asis_gemm_desc& d, const GemmOpts& o, GemmPlan* p) {
   auto al = [](const void* q, int a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
   auto tiles = [&](int bm, int bn) { return (int64_t)((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn); };
   auto take = [&](GemmForm f, int64_t gx, int gy, int block = 512, int flags = 0) {
-    *p = GemmPlan{f, (int)gx, gy, block, o.group_m | flags};
+    *p = GemmPlan{f, (int)gx, gy, block, o.group_m | flags, nullptr};
+    // the large-tile kernel (every form but these four) chooses its epilogue at run time (gemm_big_vec_epilogue): statistics,
+    // GELU' and K parts exist in the vector epilogue only
+    const bool big_kernel = f != F_GENERIC && f != F_GENERIC_CONV && f != F_P8 && f != F_P8_LN;
+    if (big_kernel && (d.stats || d.act == ASIS_ACT_GELU_GRAD || d.ksplit > 1))
+      for (int bz = 0; bz < (gy > 1 ? 2 : 1); ++bz)
+        if (!gemm_big_vec_epilogue(d, (int64_t)bz * d.strideC, d.res ? d.res + (int64_t)bz * d.strideR : nullptr)) {
+          p->why = vec_epilogue_misfit(d, bz);
+          return (int)ASIS_EINVAL;
+        }
     return (int)ASIS_OK;
   };
   const bool vec_ok = (d.N % 4 == 0) && (d.ldc % 4 == 0);
@@ -467,7 +490,11 @@ int gemm_prepare(const asis_gemm_desc* dp, asis_gemm_desc* out, GemmPlan* p) {
   ASIS_REQUIRE(tiles < (1ll << 31), "asis_gemm: too many tiles");
   ASIS_REQUIRE(!d.conv || (d.A_lo == nullptr) == (d.B_lo == nullptr), "asis_gemm: a split convolution needs both A_lo and B_lo");
   ASIS_REQUIRE((!d.A_lo || asis_aligned16(d.A_lo)) && (!d.B_lo || asis_aligned16(d.B_lo)), "asis_gemm: split halves must be 16-byte aligned");
+  p->why = nullptr;
   const int rc = gemm_plan(d, gemm_opts(), p);  // nonzero = no kernel form takes this descriptor
+  if (rc != 0 && p->why)
+    ASIS_FAIL(ASIS_EINVAL, "asis_gemm: stats / ASIS_ACT_GELU_GRAD / ksplit run in the vector epilogue of the large-tile kernels only: %s "
+                           "(include/asis_hip.h)", p->why);
   if (rc != 0 && d.act == ASIS_ACT_SILU_MUL)
     ASIS_FAIL(ASIS_EINVAL, "asis_gemm: ASIS_ACT_SILU_MUL needs a dense 16-bit-output launch on the 8-phase form (include/asis_hip.h: K %% 64 == 0, "
                            "M >= 256, N >= 256, N %% 32 == 0, ldc %% 8 == 0, plain or MX split operands, bias only)");

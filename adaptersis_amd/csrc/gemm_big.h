@@ -20,6 +20,17 @@ namespace {
 // 16 zero bytes: the LDS-DMA source of implicit-im2col lanes that fall into the conv padding
 __device__ __attribute__((aligned(16))) uint4 g_zero_page[1];
 
+// Which epilogue gemm_big_kernel runs for a batch entry / K part (cbase, res: its output offset and its residual): true = the
+// vector epilogue (16-byte accesses of C, bias_n, scale_n and res, four columns per lane), false = the scalar fallback.  ONE
+// predicate for the kernel and for gemm_plan (gemm.hip): the fallback writes no statistics, applies no GELU' and knows no K
+// parts, so the plan refuses such launches instead of letting the kernel drop them.
+__host__ __device__ __forceinline__ bool gemm_big_vec_epilogue(const asis_gemm_desc& d, int64_t cbase, const float* res) {
+  return ((d.N & 3) == 0) && ((d.ldc & 3) == 0) && ((cbase & 3) == 0) && (!res || (d.ldr & 3) == 0) &&
+         ((reinterpret_cast<uintptr_t>(d.C) & 15) == 0) && (!res || (reinterpret_cast<uintptr_t>(res) & 15) == 0) &&
+         (!d.bias_n || (reinterpret_cast<uintptr_t>(d.bias_n) & 15) == 0) &&
+         (!d.scale_n || (reinterpret_cast<uintptr_t>(d.scale_n) & 15) == 0);
+}
+
 template <typename T, int WM, int WN, int TM, int TN, int NS, int DBG = 0, bool CONV = false, bool SPLIT = false, int BKT = 64,
           int OCC = 2, bool PH8 = false, bool M16 = false, int LNF = 0, bool MXC = false>
 __global__ __launch_bounds__(WM * WN * 64, OCC) void gemm_big_kernel(const asis_gemm_desc d, const int GROUP_M_FLAGS) {
@@ -609,10 +620,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void gemm_big_kernel(const asis_
   // and 8- or 16-byte stores instead of 2-byte ones (the 2-byte form cost as much as the whole K loop).
   const int64_t cbase = (int64_t)bz * d.strideC;
   const float* __restrict__ res = d.res ? d.res + (int64_t)bz * d.strideR : nullptr;
-  const bool vec = ((d.N & 3) == 0) && ((d.ldc & 3) == 0) && ((cbase & 3) == 0) && (!res || (d.ldr & 3) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(d.C) & 15) == 0) && (!res || (reinterpret_cast<uintptr_t>(res) & 15) == 0) &&
-                   (!d.bias_n || (reinterpret_cast<uintptr_t>(d.bias_n) & 15) == 0) &&
-                   (!d.scale_n || (reinterpret_cast<uintptr_t>(d.scale_n) & 15) == 0);
+  const bool vec = gemm_big_vec_epilogue(d, cbase, res);
   if constexpr (M16 && PH8) {
     // 16-bit outputs without residual / statistics (q|k, fc1 + GELU): bias and activation are applied in the accumulator
     // layout (a lane owns 4 consecutive columns of one row), the result is converted to 16 bits BEFORE the LDS transposition

@@ -230,15 +230,12 @@ def gemm_set_option(name: str, value: int) -> None:
     _shape_plan.cache_clear()
 
 
-def conv_gemm(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, stride: int, pad: int, *,
-              out: Optional[torch.Tensor] = None, out_f32: bool = True, bias_n: Optional[torch.Tensor] = None,
-              act: int = ACT_NONE, stats: Optional[torch.Tensor] = None, accumulate: bool = False,
-              x_lo: Optional[torch.Tensor] = None, w_lo: Optional[torch.Tensor] = None, ksplit: int = 1, mx=None) -> torch.Tensor:
-    """Implicit-GEMM convolution: x [B,H,W,Cin] (16-bit NHWC), w_packed [Cout, KH*KW*Cin] ->
-    out [B,OH,OW,Cout] (fp32 by default: BatchNorm statistics are taken on it).
-    ``ksplit`` > 1: the reduction runs as that many side-by-side parts (fp32 partial maps summed in a fixed order, then the
-    caller takes the
-    BatchNorm statistics from the sum with ``colstats``) — for layers whose tile count fills only part of the machine."""
+def _conv_desc(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, stride: int, pad: int, *,
+               out: Optional[torch.Tensor] = None, out_f32: bool = True, bias_n: Optional[torch.Tensor] = None,
+               act: int = ACT_NONE, stats: Optional[torch.Tensor] = None, accumulate: bool = False,
+               x_lo: Optional[torch.Tensor] = None, w_lo: Optional[torch.Tensor] = None, ksplit: int = 1, mx=None):
+    """-> (filled GemmDesc, the tensor the launch writes, algorithmic flops) of one ``conv_gemm`` call (see ``conv_gemm``); with
+    ``ksplit`` > 1 the written tensor is the [ksplit, B, OH, OW, Cout] stack of partial maps."""
     _dev(x_nhwc, w_packed, out, bias_n, stats)
     if not x_nhwc.is_contiguous():
         raise ValueError("conv_gemm: x must be contiguous NHWC")
@@ -250,8 +247,7 @@ def conv_gemm(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, st
         if out is not None or accumulate or not out_f32 or act != ACT_NONE or stats is not None:
             raise ValueError("conv_gemm: ksplit needs a fresh fp32 output without activation; take the BatchNorm "
                              "statistics from the sum with colstats()")
-        parts = torch.empty((ksplit, Bn, OH, OW, Cout), device=x_nhwc.device, dtype=torch.float32)
-        out = parts
+        out = torch.empty((ksplit, Bn, OH, OW, Cout), device=x_nhwc.device, dtype=torch.float32)
     if out is None:
         out = torch.empty((Bn, OH, OW, Cout), device=x_nhwc.device, dtype=torch.float32 if out_f32 else x_nhwc.dtype)
     d = GemmDesc()
@@ -274,10 +270,20 @@ def conv_gemm(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, st
         d.A_lo, d.B_lo = x_lo.data_ptr(), w_lo.data_ptr()
     if mx is not None:     # x_lo / w_lo are in the MX form; mx = (amax of x, amax of w) device floats
         d.mx_amax_a, d.mx_amax_b = _f32c(mx[0]).data_ptr(), _f32c(mx[1]).data_ptr()
+    return d, out, flops
+
+
+def conv_gemm(x_nhwc: torch.Tensor, w_packed: torch.Tensor, KH: int, KW: int, stride: int, pad: int, **kw) -> torch.Tensor:
+    """Implicit-GEMM convolution: x [B,H,W,Cin] (16-bit NHWC), w_packed [Cout, KH*KW*Cin] ->
+    out [B,OH,OW,Cout] (fp32 by default: BatchNorm statistics are taken on it).
+    ``ksplit`` > 1: the reduction runs as that many side-by-side parts (fp32 partial maps summed in a fixed order, then the
+    caller takes the
+    BatchNorm statistics from the sum with ``colstats``) — for layers whose tile count fills only part of the machine."""
+    d, out, flops = _conv_desc(x_nhwc, w_packed, KH, KW, stride, pad, **kw)
     check(_launch_timed("conv", flops, lambda: lib().asis_gemm(_stream(), C.byref(d))), "asis_gemm(conv)")
-    if ksplit > 1:
-        out = torch.empty((Bn, OH, OW, Cout), device=x_nhwc.device, dtype=torch.float32)
-        reduce_rows(parts.view(ksplit, -1), 1.0, out.view(-1))
+    if d.ksplit > 1:
+        parts, out = out, torch.empty(out.shape[1:], device=out.device, dtype=torch.float32)
+        reduce_rows(parts.view(d.ksplit, -1), 1.0, out.view(-1))
     return out
 
 

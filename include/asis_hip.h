@@ -111,6 +111,12 @@ typedef struct asis_gemm_desc {
                                         partial map at C + p * strideC, group 0 adds bias_n; `stats` and `res` must be null.
                                         Sum the parts with asis_reduce_rows, take BatchNorm statistics with asis_colstats.
                                         For layers whose tile count fills only part of the machine (EINVAL elsewhere). */
+  /* The vector-epilogue requirement.  The large-tile kernels (every form but generic, generic_conv, p8 and p8_ln) write four
+   * columns per lane with 16-byte accesses when N % 4 == 0, ldc % 4 == 0, C is 16-byte aligned, and bias_n, scale_n and res
+   * (where present) are 16-byte aligned, with ldr % 4 == 0, and strideC / strideR multiples of 4 when batch > 1 or ksplit > 1;
+   * any other launch leaves through a scalar epilogue, which implements bias_n, bias_m, GELU / ReLU, scale_n and res only.
+   * `stats`, ASIS_ACT_GELU_GRAD and ksplit > 1 therefore NEED the requirement on those forms: asis_gemm and asis_gemm_plan
+   * return ASIS_EINVAL, naming the operand, when it does not hold (a bias that is a view 4 bytes into its allocation). */
   /* ---- LayerNorm folded into the linear layers around it (block.py:89-114: x + ls * f(LN(x)); norm1 / norm2) -------------
    * The residual stream between two linear layers travels as TWO 16-bit planes, x ~= hi + lo (the same 4 bytes per element as
    * fp32), with per-row (mean, rstd); the layer that consumes LN(x) takes the hi plane as its A operand directly, with

@@ -4,6 +4,8 @@ with or without a GPU), and the Python shape predicates that ask the plan instea
 EXPECTED was recorded from the dispatcher as it stood BEFORE it was split into plan + launch switch: that file compiled for the
 host with the launch macro redefined to note the kernel instantiation and the grid, run over ROWS.  It is the reference; it was
 not produced by ``asis_gemm_plan``.  A form name stands for one template instantiation (csrc/gemm.hip: launch).
+The rows on the vector-epilogue requirement (include/asis_hip.h; ``*_bytes_in``, ``conv_stats_bias_aligned``) came later and
+state the rule itself: the dispatcher before the split launched them and the kernel dropped the statistics, GELU' or K-part bias.
 
 Shapes: the ViT-L/14 trunk of the default step (R = 42348 stacked token rows, D = 1024, hidden 4096; V^T GEMMs of 6 images with
 3529 -> 3536 tokens), its SwiGLU / adapter / patch-embedding relatives, and the FeatureDecoder convolutions (12 images, 42^2 ..
@@ -123,10 +125,19 @@ ROWS = {
     "refuse_conv_ksplit2": (1, mk(21168, 512, 9 * 1024, SPLIT, conv=3, ksplit=2, strideC=21168 * 512)),
     "refuse_conv_ksplit_stats": (1, mk(21168, 512, 9 * 1024, ("stats",), conv=3, ksplit=3, strideC=21168 * 512)),
     "refuse_generic_conv_ksplit": (1, mk(21168, 512, 9 * 8, conv=3, ksplit=3, strideC=21168 * 512)),
+    # statistics, GELU' and K parts live in the vector epilogue of the large-tile kernels, which the kernel leaves at run time for
+    # an operand off its 16-byte boundary (tests/gemm_ref.py: MISALIGNED holds the same four launches for the GPU)
+    "refuse_conv_stats_bias_4_bytes_in": (1, mk(312, 136, 9 * 64, ("stats",), conv=3, bias_n=PTR + 4)),
+    "refuse_conv_ksplit_bias_4_bytes_in": (1, mk(312, 136, 9 * 64, conv=3, ksplit=3, strideC=312 * 136, bias_n=PTR + 4)),
+    "refuse_gelu_grad_bias_4_bytes_in": (1, mk(300, 136, 96, ("aux",), act=ACT_GELU_GRAD, bias_n=PTR + 4)),
+    "refuse_gelu_grad_res_8_bytes_in": (1, mk(300, 136, 96, ("aux", "scale_n"), act=ACT_GELU_GRAD, out_f32=1, res=PTR + 8)),
+    "conv_stats_bias_aligned": (1, mk(312, 136, 9 * 64, ("stats", "bias_n"), conv=3)),
+    "plain_bias_4_bytes_in_scalar_epilogue": (1, mk(300, 136, 96, bias_n=PTR + 4)),
 }
 # the two messages of "no kernel form takes this descriptor"
 NO_FORM = ("asis_gemm: split-precision operands / ASIS_ACT_GELU_GRAD / ksplit need the large-tile path (K % 64 == 0 (GELU_GRAD: 32), "
            "M >= 256, N >= 32 (128), N and ldc multiples of 4, fp32 output for split; conv: Cin % 64 == 0)")
+NOT_VEC = "asis_gemm: stats / ASIS_ACT_GELU_GRAD / ksplit run in the vector epilogue of the large-tile kernels only: %s (include/asis_hip.h)"
 NO_SWIGLU_FORM = ("asis_gemm: ASIS_ACT_SILU_MUL needs a dense 16-bit-output launch on the 8-phase form (include/asis_hip.h: K % 64 == 0, "
                   "M >= 256, N >= 256, N % 32 == 0, ldc % 8 == 0, plain or MX split operands, bias only)")
 # (form, grid_x, grid_y, block), or the message of the ASIS_EINVAL refusal
@@ -203,6 +214,12 @@ EXPECTED = {
     "refuse_conv_ksplit2": NO_FORM,
     "refuse_conv_ksplit_stats": NO_FORM,
     "refuse_generic_conv_ksplit": NO_FORM,
+    "refuse_conv_stats_bias_4_bytes_in": NOT_VEC % "bias_n must be 16-byte aligned",
+    "refuse_conv_ksplit_bias_4_bytes_in": NOT_VEC % "bias_n must be 16-byte aligned",
+    "refuse_gelu_grad_bias_4_bytes_in": NOT_VEC % "bias_n must be 16-byte aligned",
+    "refuse_gelu_grad_res_8_bytes_in": NOT_VEC % "res must be 16-byte aligned in every batch entry (strideR a multiple of 4)",
+    "conv_stats_bias_aligned": ("conv_256x128", 4, 1, 512),
+    "plain_bias_4_bytes_in_scalar_epilogue": ("big_256x128_m16", 4, 1, 512),
 }
 # switch in the child's environment -> label -> expectation (recorded the same way, with the switch set)
 ENV_ROWS = {
