@@ -32,8 +32,15 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (ROCm toolchain required to build adaptersis_amd)")
 
 
+# Libraries beside libasis_hip.so: file name -> its sources.  The training step loads libasis_hip.so alone, whose source list and
+# link line do not change when an optional op arrives; such an op lives in a library of its own, loaded on first use
+# (adaptersis_amd/_lib_distill.py), linked against libasis_hip.so for the error plumbing (asis_set_error_ / asis_last_error).
+SIDE_LIBS = {"libasis_distill.so": ("distill.hip",)}
+
+
 def sources():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+    side = {f for fs in SIDE_LIBS.values() for f in fs}
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip") and f not in side)
 
 
 def _deps_mtime() -> float:
@@ -94,7 +101,24 @@ def _build_locked(force: bool, verbose: bool) -> str:
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    for name, files in SIDE_LIBS.items():
+        _build_side(os.path.join(LIBDIR, name), [os.path.join(CSRC, f) for f in files], dep_t, force, verbose)
     return LIB
+
+
+def _build_side(out: str, srcs, dep_t: float, force: bool, verbose: bool) -> None:
+    objs = [os.path.join(OBJ, os.path.basename(s)[:-4] + ".o") for s in srcs]
+    todo = [s for s, o in zip(srcs, objs) if force or not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), dep_t)]
+    for s in todo:
+        _compile(s, verbose)
+    if todo or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(LIB):
+        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, *objs, f"-L{LIBDIR}", "-l:libasis_hip.so",
+               "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link of {out} failed:\n{r.stdout}\n{r.stderr}")
 
 
 def main():

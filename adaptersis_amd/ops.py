@@ -1665,6 +1665,12 @@ def _pixel_loss_args(op: str, logits: torch.Tensor, target: torch.Tensor, need, 
     H, W = target.shape[-2:]
     if target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] != B:
         raise ValueError(f"{op}: target must be contiguous int64 [B,H,W]")
+    return (B, h, w, H, W, Cc) + _pixel_loss_buffers(op, logits, H, W, need, dz, scratch)
+
+
+def _pixel_loss_buffers(op: str, logits: torch.Tensor, H: int, W: int, need, dz, scratch):
+    """The scratch / dz convention of the per-pixel losses for logits NHWC [B,h,w,C] evaluated at H x W -> (N, scratch, dz, accumulate)"""
+    B, Cc = logits.shape[0], logits.shape[3]
     N = B * H * W
     nbytes = need(N, Cc)
     if scratch is None:
@@ -1676,7 +1682,7 @@ def _pixel_loss_args(op: str, logits: torch.Tensor, target: torch.Tensor, need, 
         dz = torch.empty((B, H, W, Cc), device=logits.device, dtype=torch.float32)
     elif tuple(dz.shape) != (B, H, W, Cc) or dz.dtype != torch.float32 or not dz.is_contiguous():
         raise ValueError(f"{op}: dz must be contiguous float32 [B,H,W,C]")
-    return B, h, w, H, W, Cc, N, scratch, dz, accumulate
+    return N, scratch, dz, accumulate
 
 
 def lovasz_scratch_bytes(n_pixels: int, num_classes: int) -> int:
@@ -1750,6 +1756,61 @@ def hardpixel_loss(logits: torch.Tensor, target: torch.Tensor, kind: int, K: int
                                     float(grad_scale), int(accumulate), scratch.data_ptr(), loss.data_ptr(), dz.data_ptr(),
                                     _p(values), _p(selected)), "asis_hardpixel_loss")
     return (loss, dz, values, selected) if return_selection else (loss, dz)
+
+
+DISTILL_MAX_VIEWS = 8
+
+
+def distill_scratch_bytes(n_pixels: int) -> int:
+    """bytes of caller-owned scratch ``asis_distill_loss`` needs for ``n_pixels`` = B*H*W: one double per workgroup (needs no GPU)."""
+    from . import _lib_distill     # its library is loaded on first use, beside libasis_hip.so
+    nb = _lib_distill.lib().asis_distill_nblk(int(n_pixels))
+    if nb < 0:
+        check(int(nb), "asis_distill_nblk")
+    return 8 * int(nb)
+
+
+def distill_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,
+                 grad_scale: float = 1.0, dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """Knowledge distillation in one pass (csrc/distill.hip, libasis_distill.so): the KL divergence of the student from the mean distribution of a
+    teacher's views, forward and gradient.  ``logits`` fp32 NHWC [B,h,w,C] (the student); ``teacher_logits`` a tensor or a list of
+    1..8 contiguous fp32 NHWC maps [B,h_k,w_k,C], each of its own size; ``flips[k]`` true = map k was predicted from the mirrored
+    frame and is read through mirrored columns (bit for bit the un-mirrored map ``v.flip(2)``, as in ``predict_mask_views``; None =
+    no map is).  ``size_or_target``: (H, W), an int, or a tensor whose last two dimensions are H, W (the target of the hard loss).
+    Per native pixel: p = softmax(resize(logits) / T), q = mean_k softmax(resize(teacher_k) / T), T = ``temperature``;
+    -> (loss [1] = T^2 mean_pixels KL(q || p), dz fp32 [B,H,W,C] = grad_scale (T / N) (p - q) = grad_scale * d loss / d resized
+    logits); a given ``dz`` is added into (and returned).  Nothing else of size [B,H,W,C] is written however many maps there are.
+    ``scratch``: a uint8 buffer of at least ``distill_scratch_bytes(B*H*W)`` to reuse between calls (default: a fresh one).
+    No host sync; bit-identical from call to call."""
+    import ctypes
+    from . import _lib_distill
+    op = "distill_loss"
+    maps = [teacher_logits] if torch.is_tensor(teacher_logits) else teacher_logits
+    V, B, Cc, dev, ptrs, hs, ws = _predict_maps(op, "views", DISTILL_MAX_VIEWS, maps)
+    flips = [False] * V if flips is None else [bool(f) for f in flips]
+    if len(flips) != V:
+        raise ValueError(f"{op}: flips has {len(flips)} entries for {V} teacher maps")
+    if not torch.is_tensor(logits) or logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(f"{op}: logits must be a contiguous float32 NHWC tensor [B,h,w,C]")
+    if logits.shape[0] != B or logits.shape[3] != Cc or logits.device != dev:
+        raise ValueError(f"{op}: logits are {list(logits.shape)} on {logits.device}, the teacher maps have B={B}, C={Cc} on {dev}")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"{op}: temperature={temperature} must be > 0")
+    if torch.is_tensor(size_or_target):
+        size = tuple(size_or_target.shape[-2:])
+    else:
+        size = (size_or_target, size_or_target) if isinstance(size_or_target, int) else tuple(size_or_target)
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError(f"{op}: size must be a positive int, (H, W) or a tensor [..., H, W], got {size_or_target!r}")
+    _dev(logits, maps[0], dz, scratch)
+    h, w, H, W = int(logits.shape[1]), int(logits.shape[2]), int(size[0]), int(size[1])
+    N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: distill_scratch_bytes(n), dz, scratch)
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    fl = (ctypes.c_int * V)(*[int(f) for f in flips])
+    check(_lib_distill.lib().asis_distill_loss(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature),
+                                  float(grad_scale), int(accumulate), scratch.data_ptr(), loss.data_ptr(), dz.data_ptr()),
+          "asis_distill_loss")
+    return loss, dz
 
 
 # --------------------------------------------------------------------------------------------
