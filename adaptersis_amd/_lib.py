@@ -233,6 +233,8 @@ SIGNATURES = {
     "asis_grad_sumsq": [_vp, _vp, _i64, _vp],
     "asis_adamw_prepare": [_vp, _vp, _i, _vp, _vp, _f, _f, _d, _d],
     "asis_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _d, _d, _d, _d, _f, _vp, _vp],
+    "asis_ema_prepare": [_vp, _vp, _vp, _vp, _d, _i],
+    "asis_ema_update": [_vp, _vp, _vp, _i64, _vp],
     "asis_scale_f32": [_vp, _vp, _i64, _f],
     "asis_zero": [_vp, _vp, _i64],
     "asis_grad_pack_bf16": [_vp, _vp, _i64, _vp],

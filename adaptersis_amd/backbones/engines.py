@@ -29,7 +29,7 @@ from .. import config, ops
 from .. import lora as lora_mod
 from ..dinov2.layers.blocks import _Packed, _pack, run_blocks
 from ..droppath import DropPathSampler
-from ..optim import SGD, AdamW, FlatBucket
+from ..optim import EMA, SGD, AdamW, FlatBucket
 from ..parallel import StageReducer, world_size
 from .adapter_blocks import CACNN, CAViT, deform_inputs
 
@@ -105,6 +105,42 @@ def loss_and_dz(engine, logits: torch.Tensor, target: torch.Tensor, S: float):
     return (loss if ce is None else ce.add_(loss)), dz
 
 
+def make_ema(optimizer, ema_decay: Optional[float], ema_warmup: bool) -> Optional[EMA]:
+    """The engines' ``ema_decay=`` switch: None builds nothing (no shadow buffer, no launch), a value in (0, 1) an ``optim.EMA``
+    over every bucket ``optimizer`` steps, following its on-device skip decision."""
+    if ema_decay is None:
+        return None
+    return EMA(optimizer.buckets, ema_decay, warmup=ema_warmup, guard=optimizer.guard)
+
+
+def _optimizer_step(engine) -> None:
+    """the end of every ``train_step``: the optimizer's step and, when the engine averages, the average's update behind it"""
+    engine.optimizer.step(1.0)
+    if engine.ema is not None:
+        engine.ema.update()
+
+
+def _check_trainable(engine) -> None:
+    if engine.ema is not None and engine.ema.swapped_in:
+        raise RuntimeError("train_step inside ema_weights(): the parameters point at the averaged weights, which are not trained")
+
+
+@contextlib.contextmanager
+def ema_weights(engine):
+    """Inside the context every parameter the optimizer steps IS its exponential moving average: ``p.data`` points at the
+    parameter's view of the shadow buffer and comes back to its view of ``bucket.flat`` on exit, also when the body raises.
+    The live weights are never written.  The address of every parameter changes on entry and on exit, so every 16-bit pack, the
+    merged LoRA weights included, rebuilds both times (``packs.tag_of`` keys on ``data_ptr``).  Buffers are not averaged: BatchNorm
+    running statistics inside the context are the live ones.  ``train_step`` inside the context raises."""
+    if engine.ema is None:
+        raise ValueError("ema_weights(): the engine keeps no average (ema_decay=None)")
+    engine.ema.swap_in()
+    try:
+        yield engine
+    finally:
+        engine.ema.swap_out()
+
+
 class SegEngine(nn.Module):
     """One object owning the frozen ViT, the CNN encoder, the adapters, the decode head and the optimizer.
 
@@ -143,7 +179,8 @@ class SegEngine(nn.Module):
                  blocks_per_bucket: int = 4, grad_compress: Optional[str] = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
                  layer_decay: Optional[float] = None, topk_percent: float = 10.0, focal_gamma: float = 2.0,
-                 drop_path_seed: int = 0, lora_rank: Optional[int] = None, lora_alpha: Optional[float] = None):
+                 drop_path_seed: int = 0, lora_rank: Optional[int] = None, lora_alpha: Optional[float] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -176,7 +213,13 @@ class SegEngine(nn.Module):
         backbone weights frozen: both ViT passes run the training forward on the K-augmented qkv GEMM, the backward produces
         input gradients plus the three LoRA gradients per block, no backbone gradient bucket exists, a small LoRA bucket is
         all-reduced once (after block 0's backward) and joins the optimizer; ``eval_logits`` (validation, prediction) runs the
-        frozen forward on the merged weights.  Not with ``optimize_backbone``, ``layer_decay``, stochastic depth or the MLA flow."""
+        frozen forward on the merged weights.  Not with ``optimize_backbone``, ``layer_decay``, stochastic depth or the MLA flow.
+
+        ``ema_decay`` (in (0, 1); default None: nothing is allocated or launched): ``self.ema`` = ``optim.EMA`` over every bucket the
+        optimizer steps (decoder, adapters, encoder, the backbone under ``optimize_backbone``, LoRA), updated on the device right
+        after every optimizer step and skipped with it; ``ema_warmup``: update t uses the decay ``min(ema_decay, (1 + t) / (10 + t))``.
+        ``ema_weights()`` evaluates and predicts with the average.  BatchNorm running statistics are buffers and are not averaged:
+        an evaluation under ``ema_weights()`` uses the live ones."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -290,8 +333,69 @@ class SegEngine(nn.Module):
         self.optimizer = make_optimizer(optimizer, buckets, lr=lr, momentum=momentum, weight_decay=weight_decay, betas=betas, eps=eps,
                                         clip_grad=clip_grad, no_decay=no_decay, depth=len(model.blocks),
                                         layer_decay=[layer_decay if b is self.vit_bucket else None for b in buckets])
+        self.ema = make_ema(self.optimizer, ema_decay, ema_warmup)
         self.reducer = StageReducer(self.bucket.grad, self.stage_ranges, process_group)
         self._geom = {}
+
+    ema_weights = ema_weights
+
+    def _ema_modules(self) -> Dict[str, nn.Module]:
+        """checkpoint key -> module, for the modules this engine trains (the keys ``train_seg`` saves them under)"""
+        mods = {"state_dict": self.seg_decoder}
+        if self.mode == "train_adapters":
+            mods.update(cross_vit=self.cross_vit, cross_cnn=self.cross_cnn)
+            if self.train_encoder:
+                mods["backbone_encoder"] = self.backbone_encoder
+            if self.vit_bucket is not None and any(b is self.vit_bucket for b in self.optimizer.buckets):
+                mods["backbone"] = self.model
+        return mods
+
+    def ema_state_dict(self) -> dict:
+        """The ``ema`` entry of a checkpoint, shaped like the checkpoint itself: ``decay``, ``warmup``, ``updates`` (a host read)
+        and, under the keys and ``module.`` prefixes of the live entries, the state of every module this engine trains —
+        parameters from the average, buffers (BatchNorm running statistics) from the live module — plus ``lora`` with LoRA."""
+        if self.ema is None:
+            raise ValueError("ema_state_dict(): the engine keeps no average (ema_decay=None)")
+        out = {"decay": self.ema.decay, "warmup": self.ema.warmup, "updates": self.ema.updates}
+        with self.ema_weights():
+            for key, mod in self._ema_modules().items():
+                out[key] = {"module." + n: v.detach().clone() for n, v in mod.state_dict().items()}
+            if self.lora is not None:
+                out["lora"] = self.lora.state_dict()
+        return out
+
+    def load_ema_state_dict(self, entry: dict) -> str:
+        """Restore the average and its update count from an ``ema_state_dict()`` entry.  Everything is checked before anything is
+        written; buffers in the entry are ignored (they are the live module's, restored with it)."""
+        if self.ema is None:
+            raise ValueError("load_ema_state_dict(): the engine keeps no average (ema_decay=None)")
+        upd = entry.get("updates") if isinstance(entry, dict) else None
+        if isinstance(upd, bool) or not isinstance(upd, int) or upd < 0:
+            raise ValueError("ema entry: no update count (not written by SegEngine.ema_state_dict)")
+        shadow = {id(p): view for _, p, view in self.ema.named_shadows()}
+        named = [(key, "module." + n, p) for key, mod in self._ema_modules().items() for n, p in mod.named_parameters()]
+        sources = {key: entry.get(key) for key in self._ema_modules()}
+        if self.lora is not None:
+            named += [("lora", n, p) for n, p in self.lora.named_parameters()]
+            sources["lora"] = entry["lora"].get("params") if isinstance(entry.get("lora"), dict) else None
+        todo = []
+        for key, n, p in named:
+            if id(p) not in shadow:
+                continue
+            src = sources[key].get(n) if isinstance(sources[key], dict) else None
+            if not torch.is_tensor(src) or tuple(src.shape) != tuple(p.shape):
+                raise ValueError(f"ema entry: '{key}' does not hold '{n}' with shape {list(p.shape)}: not written with the same "
+                                 "trainable set")
+            todo.append((shadow[id(p)], src))
+        if len(todo) != len(shadow):
+            raise ValueError("ema entry: the modules of this engine do not cover every averaged parameter")
+        for dst, src in todo:
+            dst.copy_(src.to(dst.device, torch.float32))
+        self.ema.state[0] = upd
+        if float(entry.get("decay", self.ema.decay)) != self.ema.decay or bool(entry.get("warmup", self.ema.warmup)) != self.ema.warmup:
+            print(f"ema entry was written with decay {entry.get('decay')} / warmup {entry.get('warmup')}; continuing with "
+                  f"{self.ema.decay} / {self.ema.warmup}")
+        return "<All EMA keys matched successfully>"
 
     # ------------------------------------------------------------------------------------------
     def _geometry(self, H, W, shapes, dev):
@@ -562,6 +666,7 @@ class SegEngine(nn.Module):
     def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         """One `train.py:268-436` (or `train_mla.py:260-407`) iteration; returns the loss as a 0-dim device
         tensor (no host sync)."""
+        _check_trainable(self)
         dec = self.seg_decoder
         S = config.loss_scale
         asaves = None
@@ -622,7 +727,7 @@ class SegEngine(nn.Module):
                     self.encoder_reducer.finish()
                 self.adapter_reducer.finish()
                 self.reducer.finish()
-                self.optimizer.step(1.0)
+                _optimizer_step(self)
                 if taps is not None:
                     taps.update(logits=logits, loss=loss)
                 return loss.view(())
@@ -637,7 +742,7 @@ class SegEngine(nn.Module):
         else:
             dec._backward_core(saved, d16, bpart, inv, self.bucket.views, stage_done=self.reducer.stage_done, d_lo=d_lo)
         self.reducer.finish()
-        self.optimizer.step(1.0)
+        _optimizer_step(self)
         if taps is not None:
             taps.update(logits=logits, loss=loss)
         return loss.view(())
@@ -1046,7 +1151,10 @@ class EndToEndEngine(nn.Module):
     def __init__(self, model, seg_decoder, *, lr: float = 0.01, momentum: float = 0.9, weight_decay: float = 0.0,
                  loss: str = "ce_dc", process_group=None, blocks_per_bucket: int = 4, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
-                 drop_path_seed: int = 0, lora_rank: Optional[int] = None):
+                 drop_path_seed: int = 0, lora_rank: Optional[int] = None, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
+        """``ema_decay`` / ``ema_warmup``: as in ``SegEngine``; the optimizer steps the decoder bucket alone, so that is what is
+        averaged (``self.ema``, ``ema_weights()``)."""
         super().__init__()
         if lora_rank is not None:
             raise ValueError("EndToEndEngine trains every backbone weight: LoRA (lora_rank) is built for SegEngine's adapter flow")
@@ -1065,10 +1173,13 @@ class EndToEndEngine(nn.Module):
         self.stage_ranges = [self.bucket.range_of([n for n in named if n.startswith(pre + ".")]) for pre in order]
         self.optimizer = make_optimizer(optimizer, [self.bucket], lr=lr, momentum=momentum, weight_decay=weight_decay, betas=betas,
                                         eps=eps, clip_grad=clip_grad, no_decay=no_decay)
+        self.ema = make_ema(self.optimizer, ema_decay, ema_warmup)
         self.reducer = StageReducer(self.bucket.grad, self.stage_ranges, process_group)
         # backbone: gradient-ready order = final norm, blocks last..first, then the token embedding parameters; reduced
         # after every `blocks_per_bucket` blocks
         self.vit_bucket, self.vit_reducer, self._fire_at = make_vit_bucket(model, blocks_per_bucket, process_group)
+
+    ema_weights = ema_weights
 
     def _block_done(self, i: int) -> None:
         if i in self._fire_at:
@@ -1076,6 +1187,7 @@ class EndToEndEngine(nn.Module):
 
     @torch.no_grad()
     def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+        _check_trainable(self)
         m, dec = self.model, self.seg_decoder
         S = config.loss_scale
         dt = config.operand_dtype
@@ -1104,7 +1216,7 @@ class EndToEndEngine(nn.Module):
         m.backward(vsaved, dX.view(B, N, D), inv, self.vit_bucket.views, block_done=self._block_done)
         self.reducer.finish()
         self.vit_reducer.finish()
-        self.optimizer.step(1.0)
+        _optimizer_step(self)
         if taps is not None:
             taps.update(logits=logits, loss=loss, tokens=t2.view(B, N, D))
         return loss.view(())

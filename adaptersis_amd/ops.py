@@ -2099,6 +2099,41 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
                                 float(beta2), float(eps), float(inv_scale), guard.data_ptr(), rec.data_ptr()), "asis_adamw_step")
 
 
+# launch geometry of asis_ema_update (csrc/ema.hip): lanes per workgroup, grid cap, elements one workgroup covers per tile
+EMA_BLOCK, EMA_GRID_CAP = 256, 2048
+EMA_TILE = 16 * EMA_BLOCK      # four 16-byte quads per lane
+
+
+def _ema_state(state: torch.Tensor, rec: torch.Tensor) -> None:
+    if state.dtype != torch.int32 or state.numel() != 1:
+        raise ValueError("state must be an int32 tensor of 1 element (updates applied)")
+    if _f32c(rec).numel() != 2:
+        raise ValueError("rec must be a float32 tensor of 2 elements (1 - decay of this update, apply flag)")
+
+
+def ema_prepare(guard: Optional[torch.Tensor], state: torch.Tensor, rec: torch.Tensor, decay: float, warmup: bool) -> None:
+    """Once per update, behind the optimizer's step: ``guard[0] != 0`` (the step was skipped; ``guard`` None: never) clears the
+    apply flag ``rec[1]``; otherwise ``t = ++state[0]``, ``rec = (1 - optim.ema_decay_at(t, decay, warmup), 1)``, all on the
+    device (include/asis_hip.h)."""
+    _dev(state, rec)
+    _ema_state(state, rec)
+    if guard is not None:
+        _dev(guard)
+        if guard.dtype != torch.int32 or guard.numel() < 1 or not guard.is_contiguous():
+            raise ValueError("guard must be a contiguous int32 tensor whose first element is the skip flag")
+    check(lib().asis_ema_prepare(_stream(), None if guard is None else guard.data_ptr(), state.data_ptr(), rec.data_ptr(),
+                                 float(decay), int(bool(warmup))), "asis_ema_prepare")
+
+
+def ema_update(ema: torch.Tensor, p: torch.Tensor, rec: torch.Tensor) -> None:
+    """``ema += rec[0] * (p - ema)`` (one fused multiply-add per element) when ``rec[1]`` is set, nothing otherwise."""
+    _dev(ema, p, rec)
+    n = _f32c(ema).numel()
+    if _f32c(p).numel() != n or _f32c(rec).numel() != 2:
+        raise ValueError("ema_update: ema and p must have the same length and rec 2 elements")
+    check(lib().asis_ema_update(_stream(), ema.data_ptr(), p.data_ptr(), n, rec.data_ptr()), "asis_ema_update")
+
+
 # --------------------------------------------------------------------------------------------
 # input pipeline
 # --------------------------------------------------------------------------------------------

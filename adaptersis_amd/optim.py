@@ -13,6 +13,9 @@ compatibility (parameters stay ``nn.Parameter`` objects with their reference key
 ``AdamW`` has the same surface and is ``torch.optim.AdamW`` behind ``torch.nn.utils.clip_grad_norm_`` over ALL buckets, as the
 DINOv2 half of the reference trains its transformer (`dinov2/train/train.py:62,250-259`: AdamW, gradient clipping, no weight
 decay on 1-D parameters, layer-wise learning-rate decay) — three launches per step (csrc/adamw.hip), no host synchronisation.
+
+``EMA`` keeps an exponential moving average of the buckets an optimizer steps, one fp32 shadow per bucket, updated behind the
+optimizer's step and skipped with it on the device (csrc/ema.hip); ``ema_decay_at`` is its decay schedule on the host.
 """
 from __future__ import annotations
 
@@ -279,3 +282,106 @@ class AdamW:
             g["betas"], g["group_table"] = tuple(g["betas"]), [tuple(t) for t in g["group_table"]]
             self.lr_scale[i].copy_(torch.tensor([t[0] for t in g["group_table"]], dtype=torch.float32))
             self.weight_decay[i].copy_(torch.tensor([t[1] for t in g["group_table"]], dtype=torch.float32))
+
+
+def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
+    """The decay ``EMA`` applies at its ``t``-th update (t = 1, 2, ...): ``min(decay, (1 + t) / (10 + t))`` with ``warmup`` (the
+    average follows the weights closely while they still move fast), else ``decay``.  The host restatement of what
+    ``asis_ema_prepare`` computes on the device, in the same double arithmetic; for tests and logs."""
+    t = int(t)
+    if t < 1:
+        raise ValueError("ema_decay_at: updates count from 1")
+    d = float(decay)
+    return min(d, (1.0 + t) / (10.0 + t)) if warmup else d
+
+
+class EMA:
+    """Exponential moving average of the parameters in ``buckets``: one fp32 shadow per bucket, ``shadow += (1 - d_t) (flat -
+    shadow)`` after every optimizer step, with ``d_t = ema_decay_at(t, decay, warmup)`` and t the number of updates APPLIED.
+
+    ``guard``: the optimizer's guard tensor (``SGD.guard`` / ``AdamW.guard``; element 0 is the skip flag of its last step).  A step
+    the optimizer skipped on the device is skipped here too, and does not count, without the host learning of it: ``update()`` is
+    one ``asis_ema_prepare`` plus one ``asis_ema_update`` per bucket on the current stream (csrc/ema.hip), no host sync.
+    Gradient-only buckets (``momentum=False``) are not averaged: nothing steps them.  Buffers (BatchNorm running statistics) are
+    not parameters and are not averaged either."""
+
+    def __init__(self, buckets: Sequence[FlatBucket], decay: float, warmup: bool = True, guard: Optional[torch.Tensor] = None):
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError(f"EMA: decay must lie in (0, 1): got {decay}")
+        self.buckets = [b for b in buckets if b.momentum is not None]
+        if not self.buckets:
+            raise ValueError("EMA: no bucket that an optimizer steps")
+        self.decay, self.warmup, self.guard = decay, bool(warmup), guard
+        dev = self.buckets[0].flat.device
+        self.shadows = [b.flat.detach().clone() for b in self.buckets]
+        self.state = torch.zeros(1, device=dev, dtype=torch.int32)      # updates applied
+        self.record = torch.zeros(2, device=dev, dtype=torch.float32)   # 1 - decay of this update, apply flag
+        self._live = None                                               # the parameters' own views while ``swapped`` is active
+
+    @property
+    def updates(self) -> int:
+        """updates applied so far (skipped steps do not count).  A host read: it waits for the device."""
+        return int(self.state[0].item())
+
+    @property
+    def swapped_in(self) -> bool:
+        return self._live is not None
+
+    def update(self):
+        ops.ema_prepare(self.guard, self.state, self.record, self.decay, self.warmup)
+        for b, e in zip(self.buckets, self.shadows):
+            ops.ema_update(e, b.flat, self.record)
+
+    def reset(self):
+        """restart the average from the current weights (a resume from a checkpoint without an average)"""
+        for b, e in zip(self.buckets, self.shadows):
+            e.copy_(b.flat)
+        self.state.zero_()
+
+    def named_shadows(self) -> Iterable[Tuple[str, nn.Parameter, torch.Tensor]]:
+        """(bucket name, parameter, its view of the shadow) for every averaged parameter"""
+        for b, e in zip(self.buckets, self.shadows):
+            for n, p, off in zip(b.names, b.params, b.offsets):
+                yield n, p, e[off:off + p.numel()].view(p.shape)
+
+    def swap_in(self):
+        """Point ``p.data`` of every averaged parameter at its view of the shadow.  The address changes, so every pack keyed by
+        ``packs.tag_of`` rebuilds; the live weights are not written."""
+        if self._live is not None:
+            raise RuntimeError("EMA: the averaged weights are already swapped in")
+        self._live = []
+        for _, p, view in self.named_shadows():
+            self._live.append((p, p.data))
+            p.data = view
+
+    def swap_out(self):
+        if self._live is None:
+            return
+        for p, data in self._live:
+            p.data = data
+        self._live = None
+
+    def state_dict(self):
+        return {"decay": self.decay, "warmup": self.warmup, "updates": self.updates,
+                "state": {i: {"shadow": e.clone()} for i, e in enumerate(self.shadows)}}
+
+    def load_state_dict(self, sd):
+        # validate first, like the optimizers: nothing is modified when the entry does not fit
+        state = sd.get("state") if isinstance(sd, dict) else None
+        upd = sd.get("updates") if isinstance(sd, dict) else None
+        if not isinstance(state, dict) or isinstance(upd, bool) or not isinstance(upd, int) or upd < 0:
+            raise ValueError("EMA state was not written by adaptersis_amd.optim.EMA (no flat shadows / update count)")
+        if len(state) != len(self.buckets):
+            raise ValueError("EMA state has a different number of buckets")
+        bufs = []
+        for i, b in enumerate(self.buckets):
+            ent = state.get(i, state.get(str(i)))
+            e = ent.get("shadow") if isinstance(ent, dict) else None
+            if not torch.is_tensor(e) or e.numel() != b.numel:
+                raise ValueError(f"EMA state does not match flat bucket {i} ({b.numel} elements): not written by "
+                                 "adaptersis_amd.optim.EMA with the same trainable set")
+            bufs.append(e)
+        for e, src in zip(self.shadows, bufs):
+            e.copy_(src.reshape(-1))
+        self.state[0] = upd

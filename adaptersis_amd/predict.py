@@ -116,6 +116,9 @@ def get_args_parser():
                         "window's inner edges) or uniform")
     p.add_argument("--slide_context", action="store_true",
                    help="with --slide_size: one more tile, the whole frame at --imsize (the input of the plain prediction)")
+    p.add_argument("--ema", action="store_true",
+                   help="predict with the averaged weights: the checkpoint's 'ema' entry (a run with --ema_decay) instead of the live "
+                        "modules; a checkpoint without that entry is an error")
     p.add_argument("--seed", default=None, type=int,
                    help="torch seed the TRAINING process was given before it built its modules; required when the checkpoint lacks "
                         "cross_vit / cross_cnn / backbone_encoder (the training command lines do not seed, so only a caller that "
@@ -383,11 +386,18 @@ def build_engine(args) -> SegEngine:
     model, enc, cv, cn, dec = _t.build_modules(args, args.head, args.num_classes, dev)
     eng = SegEngine(model, enc, cv, cn, dec, num_classes=args.num_classes)
     # "backbone": the ViT of a run with --optimize_backbone (absent from any other checkpoint: the pretrained weights stay)
+    src = ck
+    if getattr(args, "ema", False):     # the averaged weights: the same loader, pointed at the entry shaped like the checkpoint
+        src = ck.get("ema")
+        if not isinstance(src, dict) or "state_dict" not in src:
+            raise ValueError(f"{path} holds no 'ema' entry: --ema needs a checkpoint of a run with --ema_decay (the live weights "
+                             "are not used in its place)")
     load_checkpoint(path, dec, {"cross_vit": cv, "cross_cnn": cn, "backbone_encoder": enc, "backbone": model},
-                    hint=f" (--head {args.head} --num_classes {args.num_classes})", ck=ck)
-    if "lora" in ck:    # a run with --lora_rank: every forward of the engine goes through the merged weights (SegEngine.eval_logits)
-        eng.lora = LoRA.from_state(model, ck["lora"])
-    print(f"loaded {path} (epoch {ck.get('epoch')}, entries {sorted(k for k in ck if isinstance(ck[k], dict))})")
+                    hint=f" (--head {args.head} --num_classes {args.num_classes})", ck=src)
+    if "lora" in src:    # a run with --lora_rank: every forward of the engine goes through the merged weights (SegEngine.eval_logits)
+        eng.lora = LoRA.from_state(model, src["lora"])
+    print(f"loaded {path} (epoch {ck.get('epoch')}, entries {sorted(k for k in ck if isinstance(ck[k], dict))}"
+          + (f"; averaged weights after {src.get('updates')} updates" if src is not ck else "") + ")")
     return eng
 
 

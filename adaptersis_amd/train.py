@@ -199,7 +199,32 @@ def check_backbone_args(args) -> Optional[str]:
             return "--lora_rank and --optimize_backbone exclude each other (with LoRA the backbone weights stay frozen)"
         if r > 0.0:
             return "--lora_rank needs --drop_path 0"
+    d = getattr(args, "ema_decay", None)
+    if d is not None and not 0.0 < float(d) < 1.0:
+        return "--ema_decay must lie in (0, 1)"
+    if d is None and (getattr(args, "ema_no_warmup", False) or getattr(args, "ema_validate_live", False)):
+        return "--ema_no_warmup / --ema_validate_live need --ema_decay"
     return None
+
+
+def _ema_args(args) -> dict:
+    """The weight-averaging flags (--ema_decay, --ema_no_warmup) as ``SegEngine`` arguments; without --ema_decay nothing is passed
+    and the engine is what it was."""
+    if getattr(args, "ema_decay", None) is None:
+        return {}
+    return {"ema_decay": float(args.ema_decay), "ema_warmup": not getattr(args, "ema_no_warmup", False)}
+
+
+class _EmaEntry:
+    """the ``ema`` entry of a checkpoint as ``restart_from_checkpoint`` sees it: loaded into the engine's average"""
+
+    def __init__(self, engine):
+        self.engine, self.loaded = engine, False
+
+    def load_state_dict(self, entry):
+        msg = self.engine.load_ema_state_dict(entry)
+        self.loaded = True
+        return msg
 
 
 def _loss_args(args) -> dict:
@@ -263,13 +288,13 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
                              weight_decay=0.0 if wd is None else wd, num_classes=num_classes, loss=loss, **_optimizer_args(args),
-                             **_loss_args(args), **_backbone_args(args))
+                             **_loss_args(args), **_backbone_args(args), **_ema_args(args))
     else:
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=args.lr,
                              weight_decay=3e-5 if wd is None else wd,
                              mode="train_adapters" if getattr(args, "train_adapters", False) else "reference_exact",
                              train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss,
-                             **_optimizer_args(args), **_loss_args(args), **_backbone_args(args))
+                             **_optimizer_args(args), **_loss_args(args), **_backbone_args(args), **_ema_args(args))
     optimizer = engine.optimizer
     engine.aug_non_rigid = non_rigid_p      # read by train(): its signature is the reference's and carries no arguments
 
@@ -319,10 +344,30 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
         if getattr(args, "optimize_backbone", False):   # a fine-tuned ViT is part of the trained model: saved and restored
             extra["backbone"] = model
     lora = getattr(engine, "lora", None)       # --lora_rank: the checkpoint gains a "lora" entry (parameters, rank, alpha)
-    utils.restart_from_checkpoint(os.path.join(args.output_dir, "checkpoint.pth.tar"), run_variables=to_restore,
+    # --ema_decay: the checkpoint gains an "ema" entry; it is restored after the live modules, and a file without one restarts
+    # the average from the weights just restored
+    ema_entry = None if engine.ema is None else _EmaEntry(engine)
+    ckpt_path = os.path.join(args.output_dir, "checkpoint.pth.tar")
+    resumed = os.path.isfile(ckpt_path)
+    utils.restart_from_checkpoint(ckpt_path, run_variables=to_restore,
                                   state_dict=seg_decoder, **extra, **({} if lora is None else {"lora": lora}), optimizer=optimizer,
-                                  scheduler=scheduler)
+                                  scheduler=scheduler, **({} if ema_entry is None else {"ema": ema_entry}))
+    if ema_entry is not None and resumed and not ema_entry.loaded:
+        engine.ema.reset()
+        print(f"=> no usable 'ema' entry in '{ckpt_path}': the average starts from the restored live weights")
     start_epoch, best_acc = to_restore["epoch"], to_restore["best_acc"]
+    live_validate = validate
+
+    def validate(*a):
+        """with --ema_decay the metrics are those of the averaged weights; --ema_validate_live adds the live ones as live_*"""
+        if engine.ema is None:
+            return live_validate(*a)
+        with engine.ema_weights():
+            stats = live_validate(*a)
+        if getattr(args, "ema_validate_live", False):
+            stats = {**stats, **{f"live_{k}": v for k, v in live_validate(*a).items()}}
+        return stats
+
     if args.evaluate:
         stats = validate(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_decoder,
                                  args.n_last_blocks, args.avgpool_patchtokens)
@@ -353,6 +398,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                 ckpt[k] = {"module." + n: v for n, v in mod.state_dict().items()}
             if lora is not None:
                 ckpt["lora"] = lora.state_dict()
+            if engine.ema is not None:
+                ckpt["ema"] = engine.ema_state_dict()
             torch.save(ckpt, os.path.join(args.output_dir, "checkpoint.pth.tar"))
     print("Training of the supervised linear classifier on frozen features completed.\n"
           "Top-1 test accuracy: {acc:.1f}".format(acc=best_acc))
@@ -503,6 +550,14 @@ def get_args_parser():
                         "linspace(0, R, depth)[i]; above 0.1 a branch runs on a random subset of the batch only")
     p.add_argument("--drop_path_uniform", action="store_true", help="every block gets --drop_path")
     p.add_argument("--drop_path_seed", default=0, type=int, help="seed of the stochastic-depth draws (the generator is seeded with this and the rank)")
+    # extension: an exponential moving average of the trained weights (optim.EMA), used for validation and kept in the checkpoint
+    p.add_argument("--ema_decay", default=None, type=float, metavar="D",
+                   help="keep an exponential moving average of every trained weight with this decay (in (0, 1)); validation, "
+                        "--evaluate and best_acc then use the averaged weights and the checkpoint gains an 'ema' entry")
+    p.add_argument("--ema_no_warmup", action="store_true",
+                   help="with --ema_decay: use D from the first update on instead of min(D, (1 + t) / (10 + t))")
+    p.add_argument("--ema_validate_live", action="store_true",
+                   help="with --ema_decay: also validate the live weights and log their metrics as test_live_*")
     # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
     p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
                    help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that; "

@@ -1022,6 +1022,18 @@ int asis_adamw_prepare(void* stream, const float* partials, int n_partials, int3
 int asis_adamw_step(void* stream, float* p, const float* g, float* m, float* v, int64_t n, const uint8_t* codes,
                     const float* lr_scale, const float* weight_decay, int n_groups, double lr, double beta1, double beta2,
                     double eps, float inv_scale, const int32_t* guard, const float* rec);
+/* Exponential moving average of the flat fp32 buckets (csrc/ema.hip).  Two launches per update and no host synchronisation;
+ * the update count and this update's weight live on the device, so no argument changes from step to step.
+ *   asis_ema_prepare (one thread, once per update, after the optimizer's step): guard = the optimizer's guard (int32, element
+ *     0 = its skip flag) or NULL, state = int32[1] {updates applied}, rec = fp32[2].
+ *       guard && guard[0] != 0 (the step was skipped): rec[1] = 0, nothing else changes;
+ *       else t = ++state[0], d = warmup ? min(decay, (1 + t) / (10 + t)) : decay (in double), rec = {(float)(1 - d), 1}.
+ *     decay must lie in (0, 1).
+ *   asis_ema_update (per bucket): nothing when rec[1] == 0; else per element e = fmaf(rec[0], p - e, e) in fp32.  16-byte
+ *     accesses when both ema and p are 16-byte aligned (flat buckets are), else one element per lane; any n >= 0.
+ *     Only asis_ema_prepare writes state and rec. */
+int asis_ema_prepare(void* stream, const int32_t* guard, int32_t* state, float* rec, double decay, int warmup);
+int asis_ema_update(void* stream, float* ema, const float* p, int64_t n, const float* rec);
 int asis_scale_f32(void* stream, float* x, int64_t n, float a);
 /* zero `bytes` bytes at p on `stream` (hipMemsetAsync: the DMA fill, ~6 TB/s; the step's few accumulate-into buffers) */
 int asis_zero(void* stream, void* p, int64_t bytes);
