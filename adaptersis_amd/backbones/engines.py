@@ -29,7 +29,7 @@ from .. import config, ops
 from .. import lora as lora_mod
 from ..dinov2.layers.blocks import _Packed, _pack, run_blocks
 from ..droppath import DropPathSampler
-from ..optim import EMA, SGD, AdamW, FlatBucket
+from ..optim import EMA, SGD, AdamW, FlatBucket, consistency_ramp
 from ..parallel import StageReducer, world_size
 from .adapter_blocks import CACNN, CAViT, deform_inputs
 
@@ -180,7 +180,9 @@ class SegEngine(nn.Module):
                  betas=(0.9, 0.999), eps: float = 1e-8, clip_grad: Optional[float] = None, no_decay: bool = True,
                  layer_decay: Optional[float] = None, topk_percent: float = 10.0, focal_gamma: float = 2.0,
                  drop_path_seed: int = 0, lora_rank: Optional[int] = None, lora_alpha: Optional[float] = None,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, teacher=None, distill_weight: float = 1.0,
+                 distill_temperature: float = 1.0, distill_threshold: Optional[float] = None, distill_rampup: int = 0,
+                 distill_flip: bool = False):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -219,7 +221,15 @@ class SegEngine(nn.Module):
         optimizer steps (decoder, adapters, encoder, the backbone under ``optimize_backbone``, LoRA), updated on the device right
         after every optimizer step and skipped with it; ``ema_warmup``: update t uses the decay ``min(ema_decay, (1 + t) / (10 + t))``.
         ``ema_weights()`` evaluates and predicts with the average.  BatchNorm running statistics are buffers and are not averaged:
-        an evaluation under ``ema_weights()`` uses the live ones."""
+        an evaluation under ``ema_weights()`` uses the live ones.
+
+        ``teacher`` (default None: nothing is allocated, launched or loaded, the step is the one without the keyword): mean-teacher
+        training.  "ema" (needs ``ema_decay``): the teacher is this engine under ``ema_weights()``; a ``SegEngine``: a frozen
+        teacher, which is never stepped.  Every ``train_step`` first takes the teacher's logits of ``teacher_inp`` (and, with
+        ``distill_flip``, of its mirror image) under the guard of ``predict``, then adds ``ops.consistency_loss`` against them
+        (``distill_temperature``, ``distill_threshold``) to the hard loss: total = hard + lambda_t kd with lambda_t =
+        ``distill_weight`` * ``optim.consistency_ramp(distill_step, distill_rampup)``, ``distill_step`` the number of steps so
+        far (a host counter)."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -336,8 +346,58 @@ class SegEngine(nn.Module):
         self.ema = make_ema(self.optimizer, ema_decay, ema_warmup)
         self.reducer = StageReducer(self.bucket.grad, self.stage_ranges, process_group)
         self._geom = {}
+        if teacher is not None and teacher != "ema" and not isinstance(teacher, SegEngine):
+            raise ValueError("teacher must be None, 'ema' or a SegEngine")
+        if isinstance(teacher, str) and self.ema is None:
+            raise ValueError("teacher='ema' needs ema_decay: the teacher is the average of the weights")
+        if isinstance(teacher, SegEngine) and teacher.num_classes != num_classes:
+            raise ValueError(f"the teacher predicts {teacher.num_classes} classes, the student {num_classes}")
+        if teacher is not None:
+            if not float(distill_weight) >= 0.0:
+                raise ValueError("distill_weight must be >= 0")
+            if not float(distill_temperature) > 0.0:
+                raise ValueError("distill_temperature must be > 0")
+            if distill_threshold is not None and not float(distill_threshold) <= 1.0:
+                raise ValueError("distill_threshold must be at most 1 (None or <= 0 keeps every pixel)")
+            if int(distill_rampup) < 0:
+                raise ValueError("distill_rampup counts steps: it must be >= 0")
+        # not a submodule: a teacher engine's parameters are not this engine's (state_dict, .to(), the optimizer's buckets)
+        object.__setattr__(self, "teacher", teacher)
+        self.distill_weight, self.distill_temperature = float(distill_weight), float(distill_temperature)
+        self.distill_threshold = None if distill_threshold is None else float(distill_threshold)
+        self.distill_rampup, self.distill_flip = int(distill_rampup), bool(distill_flip)
+        self.distill_step = 0
+        self.last_loss_kd = self.last_kd_kept = None
 
     ema_weights = ema_weights
+
+    @torch.no_grad()
+    def _teacher_maps(self, inp: torch.Tensor):
+        """The teacher's logit maps of ``inp`` (and of its mirror image with ``distill_flip``) under the guard of ``predict``
+        -> (maps, flips).  With ``teacher="ema"`` every averaged parameter is re-packed on the way in and on the way out
+        (``packs.tag_of`` keys on ``data_ptr``)."""
+        views, flips = [inp], [False]
+        if self.distill_flip:
+            views.append(inp.flip(-1))
+            flips.append(True)
+        if isinstance(self.teacher, SegEngine):
+            return self.teacher._guarded_logits(views), flips
+        with self.ema_weights():
+            return self._guarded_logits(views), flips
+
+    def _add_consistency(self, logits, target, dz, hard, maps, flips, S: float, taps: Optional[dict]) -> torch.Tensor:
+        """The soft term of a step with a teacher: ``ops.consistency_loss`` against ``maps`` added into the hard term's ``dz`` at
+        S lambda_t -> hard + lambda_t kd (a device tensor, no host sync).  Counts the step."""
+        lam = self.distill_weight * consistency_ramp(self.distill_step, self.distill_rampup)
+        self.distill_step += 1
+        scratch = _loss_scratch(self, "_consist_scratch", ops.consistency_scratch_bytes(target.numel()), logits.device)
+        kd, kept, _ = ops.consistency_loss(logits, maps, target, flips=flips, temperature=self.distill_temperature,
+                                           threshold=self.distill_threshold, grad_scale=S * lam, dz=dz, scratch=scratch)
+        self.last_loss_kd, self.last_kd_kept = kd, kept
+        total = hard + lam * kd
+        if taps is not None:
+            taps.update(loss_hard=hard, loss_kd=kd, kd_kept=kept, teacher_logits=maps, distill_scale=lam)
+        return total
 
     def _ema_modules(self) -> Dict[str, nn.Module]:
         """checkpoint key -> module, for the modules this engine trains (the keys ``train_seg`` saves them under)"""
@@ -663,10 +723,16 @@ class SegEngine(nn.Module):
         return res
 
     @torch.no_grad()
-    def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None,
+                   teacher_inp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One `train.py:268-436` (or `train_mla.py:260-407`) iteration; returns the loss as a 0-dim device
-        tensor (no host sync)."""
+        tensor (no host sync).  With a ``teacher``: the teacher sees ``teacher_inp`` (default ``inp``; the same geometry), and the
+        loss is hard + lambda_t kd (``taps``: ``loss_hard``, ``loss_kd``, ``kd_kept``, ``teacher_logits``, ``distill_scale``)."""
         _check_trainable(self)
+        if self.teacher is not None:   # before the student's forward: the teacher's activations are gone when the student's are saved
+            tmaps, tflips = self._teacher_maps(inp if teacher_inp is None else teacher_inp)
+        elif teacher_inp is not None:
+            raise ValueError("train_step: teacher_inp without a teacher")
         dec = self.seg_decoder
         S = config.loss_scale
         asaves = None
@@ -688,6 +754,8 @@ class SegEngine(nn.Module):
                 logits, saved = dec._forward_core(cat[0], cat[1], save=True, training=True)
         target = target.long().contiguous()
         loss, dz = loss_and_dz(self, logits, target, S)
+        if self.teacher is not None:
+            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, S, taps)
         B, hh, ww, C = logits.shape
         r = ops.resize_bilinear_bwd(dz, hh, ww, config.operand_dtype, config.split_conv)
         d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])
@@ -1017,6 +1085,20 @@ class SegEngine(nn.Module):
         return (m, loss1, counts) if with_counts else (m, loss1)
 
     @torch.no_grad()
+    def _guarded_logits(self, inps) -> List[torch.Tensor]:
+        """``eval_logits`` of every input under the guard of prediction: decoder in eval mode, the encoder's running statistics
+        not updated, both restored afterwards, also when a forward raises."""
+        enc = self.backbone_encoder
+        was, upd = self.seg_decoder.training, enc.update_running_stats
+        self.seg_decoder.eval()
+        enc.update_running_stats = False
+        try:
+            return [self.eval_logits(inp) for inp in inps]
+        finally:
+            self.seg_decoder.train(was)
+            enc.update_running_stats = upd
+
+    @torch.no_grad()
     def predict(self, inp: torch.Tensor, size=None, **kw):
         """Masks of ``inp`` (float [B,3,S,S] as validation feeds it) at ``size`` = (H, W) (None: the input's own), uint8 [B,H,W]:
         ``ops.predict_mask`` (keywords: ``encode``, ``frames`` / ``palette`` / ``alpha`` for the overlay, ``target`` / ``lut``
@@ -1024,15 +1106,7 @@ class SegEngine(nn.Module):
         encoder's SyncBatchNorm in train mode as validation leaves it, so a frame's mask depends on the batch it is predicted
         in exactly as the validation metrics do.  Forward only: no optimizer state, BatchNorm running buffer
         or saved activation of a training step is touched."""
-        enc = self.backbone_encoder
-        was, upd = self.seg_decoder.training, enc.update_running_stats
-        self.seg_decoder.eval()
-        enc.update_running_stats = False
-        try:
-            logits = self.eval_logits(inp)
-        finally:
-            self.seg_decoder.train(was)
-            enc.update_running_stats = upd
+        logits = self._guarded_logits([inp])[0]
         return ops.predict_mask(logits, tuple(inp.shape[-2:]) if size is None else size, **kw)
 
     @torch.no_grad()
@@ -1046,16 +1120,7 @@ class SegEngine(nn.Module):
         inps, flips = list(inps), list(flips)
         if len(inps) != len(flips):
             raise ValueError(f"predict_views: {len(inps)} inputs and {len(flips)} flips")
-        enc = self.backbone_encoder
-        was, upd = self.seg_decoder.training, enc.update_running_stats
-        self.seg_decoder.eval()
-        enc.update_running_stats = False
-        try:
-            logits = [self.eval_logits(inp) for inp in inps]
-        finally:
-            self.seg_decoder.train(was)
-            enc.update_running_stats = upd
-        return ops.predict_mask_views(logits, size, flips=flips, **kw)
+        return ops.predict_mask_views(self._guarded_logits(inps), size, flips=flips, **kw)
 
     @torch.no_grad()
     def predict_tiles(self, inps, tiles, work, size, **kw):
@@ -1071,16 +1136,7 @@ class SegEngine(nn.Module):
         inps, tiles = list(inps), list(tiles)
         if len(inps) != len(tiles):
             raise ValueError(f"predict_tiles: {len(inps)} inputs and {len(tiles)} tiles")
-        enc = self.backbone_encoder
-        was, upd = self.seg_decoder.training, enc.update_running_stats
-        self.seg_decoder.eval()
-        enc.update_running_stats = False
-        try:
-            logits = [self.eval_logits(inp) for inp in inps]
-        finally:
-            self.seg_decoder.train(was)
-            enc.update_running_stats = upd
-        return ops.predict_mask_tiles(logits, tiles, work, size, **kw)
+        return ops.predict_mask_tiles(self._guarded_logits(inps), tiles, work, size, **kw)
 
 
 def make_optimizer(kind: str, buckets, *, lr, momentum, weight_decay, betas=(0.9, 0.999), eps=1e-8, clip_grad=None, no_decay=True,

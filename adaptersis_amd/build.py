@@ -34,8 +34,8 @@ def _hipcc() -> str:
 
 # Libraries beside libasis_hip.so: file name -> its sources.  The training step loads libasis_hip.so alone, whose source list and
 # link line do not change when an optional op arrives; such an op lives in a library of its own, loaded on first use
-# (adaptersis_amd/_lib_distill.py), linked against libasis_hip.so for the error plumbing (asis_set_error_ / asis_last_error).
-SIDE_LIBS = {"libasis_distill.so": ("distill.hip",)}
+# (adaptersis_amd/_lib_distill.py, _lib_consist.py), linked against libasis_hip.so for the error plumbing (asis_set_error_ / asis_last_error).
+SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",)}
 
 
 def sources():
@@ -45,7 +45,7 @@ def sources():
 
 def _deps_mtime() -> float:
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "asis_hip.h"))
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("asis_hip.h", "asis_consist.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -1782,9 +1782,22 @@ def distill_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=
     logits); a given ``dz`` is added into (and returned).  Nothing else of size [B,H,W,C] is written however many maps there are.
     ``scratch``: a uint8 buffer of at least ``distill_scratch_bytes(B*H*W)`` to reuse between calls (default: a fresh one).
     No host sync; bit-identical from call to call."""
-    import ctypes
     from . import _lib_distill
     op = "distill_loss"
+    B, h, w, V, H, W, Cc, dev, ptrs, hs, ws, fl = _distill_args(op, logits, teacher_logits, size_or_target, flips, temperature, dz,
+                                                                scratch)
+    N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: distill_scratch_bytes(n), dz, scratch)
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    check(_lib_distill.lib().asis_distill_loss(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature),
+                                  float(grad_scale), int(accumulate), scratch.data_ptr(), loss.data_ptr(), dz.data_ptr()),
+          "asis_distill_loss")
+    return loss, dz
+
+
+def _distill_args(op: str, logits, teacher_logits, size_or_target, flips, temperature, dz, scratch):
+    """The argument checks ``distill_loss`` and ``consistency_loss`` share: the student, the teacher maps, their flips, the size
+    and the temperature -> (B, h, w, V, H, W, C, device, ptrs, hs, ws, flips): the last four are the ctypes arrays of the ABI."""
+    import ctypes
     maps = [teacher_logits] if torch.is_tensor(teacher_logits) else teacher_logits
     V, B, Cc, dev, ptrs, hs, ws = _predict_maps(op, "views", DISTILL_MAX_VIEWS, maps)
     flips = [False] * V if flips is None else [bool(f) for f in flips]
@@ -1803,14 +1816,55 @@ def distill_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=
     if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
         raise ValueError(f"{op}: size must be a positive int, (H, W) or a tensor [..., H, W], got {size_or_target!r}")
     _dev(logits, maps[0], dz, scratch)
-    h, w, H, W = int(logits.shape[1]), int(logits.shape[2]), int(size[0]), int(size[1])
-    N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: distill_scratch_bytes(n), dz, scratch)
-    loss = torch.empty((1,), device=dev, dtype=torch.float32)
     fl = (ctypes.c_int * V)(*[int(f) for f in flips])
-    check(_lib_distill.lib().asis_distill_loss(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature),
-                                  float(grad_scale), int(accumulate), scratch.data_ptr(), loss.data_ptr(), dz.data_ptr()),
-          "asis_distill_loss")
-    return loss, dz
+    return B, int(logits.shape[1]), int(logits.shape[2]), V, int(size[0]), int(size[1]), Cc, dev, ptrs, hs, ws, fl
+
+
+def consistency_scratch_bytes(n_pixels: int) -> int:
+    """bytes of caller-owned scratch ``asis_consist_loss`` needs for ``n_pixels`` = B*H*W: two doubles per workgroup (needs no GPU)."""
+    from . import _lib_consist     # its library is loaded on first use, beside libasis_hip.so
+    nb = _lib_consist.lib().asis_consist_nblk(int(n_pixels))
+    if nb < 0:
+        check(int(nb), "asis_consist_nblk")
+    return 16 * int(nb)
+
+
+def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,
+                     threshold: Optional[float] = None, sample_weight: Optional[torch.Tensor] = None, grad_scale: float = 1.0,
+                     dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """The consistency term of teacher-student training in one pass (csrc/consist.hip, libasis_consist.so): ``distill_loss`` with a
+    per-pixel confidence gate, a per-sample weight and the count of the pixels the gate let through.  ``logits``,
+    ``teacher_logits``, ``size_or_target``, ``flips``, ``temperature`` as there.  ``threshold`` (None or <= 0: every pixel is
+    kept; at most 1): a pixel takes part where conf = max_c q_c >= threshold, q the teacher's mean distribution at THIS
+    temperature.  ``sample_weight``: fp32 [B] on the device, finite and >= 0 (not checked on the device); None = all 1.
+    -> (loss [1] = T^2 sum_i w_b m_i KL_i(q || p) / N, normalised by N = B*H*W and not by the kept count; kept int32 [1] = the
+    pixels with m_i = 1 in samples with w_b > 0; dz fp32 [B,H,W,C] = grad_scale (T / N) w_b m_i (p - q)).  A fresh ``dz`` holds
+    zeros on the dropped pixels; a given ``dz`` is added into on the kept pixels and neither read nor written on the others (and
+    returned).  A sample of weight 0 reads none of its maps.  ``scratch``: a uint8 buffer of at least
+    ``consistency_scratch_bytes(B*H*W)`` to reuse between calls (default: a fresh one).  No host sync; bit-identical from call to
+    call."""
+    from . import _lib_consist
+    op = "consistency_loss"
+    B, h, w, V, H, W, Cc, dev, ptrs, hs, ws, fl = _distill_args(op, logits, teacher_logits, size_or_target, flips, temperature, dz,
+                                                                scratch)
+    thr = 0.0 if threshold is None else float(threshold)
+    if not thr <= 1.0:
+        raise ValueError(f"{op}: threshold={threshold} must be at most 1 (None or <= 0 keeps every pixel)")
+    if sample_weight is not None:
+        _dev(sample_weight)
+        if sample_weight.dtype != torch.float32 or not sample_weight.is_contiguous() or tuple(sample_weight.shape) != (B,) \
+                or sample_weight.device != dev:
+            raise ValueError(f"{op}: sample_weight must be a contiguous float32 tensor [B={B}] on {dev}")
+    N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: consistency_scratch_bytes(n), dz, scratch)
+    if scratch.data_ptr() % 8:
+        raise ValueError(f"{op}: scratch must be 8-byte aligned")
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    kept = torch.empty((1,), device=dev, dtype=torch.int32)
+    check(_lib_consist.lib().asis_consist_loss(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc,
+                                               float(temperature), thr, _p(sample_weight), float(grad_scale), int(accumulate),
+                                               scratch.data_ptr(), loss.data_ptr(), kept.data_ptr(), dz.data_ptr()),
+          "asis_consist_loss")
+    return loss, kept, dz
 
 
 # --------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ optimizer's step and skipped with it on the device (csrc/ema.hip); ``ema_decay_a
 """
 from __future__ import annotations
 
+import math
 import re
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -293,6 +294,19 @@ def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
         raise ValueError("ema_decay_at: updates count from 1")
     d = float(decay)
     return min(d, (1.0 + t) / (10.0 + t)) if warmup else d
+
+
+def consistency_ramp(t: int, rampup: int) -> float:
+    """The ramp-up of the consistency weight in mean-teacher training (Tarvainen & Valpola 2017): ``exp(-5 (1 - min(t, R) / R)^2)``
+    for ``R = rampup`` > 0 steps, t = 0, 1, ... the number of training steps so far — e^-5 at t = 0, rising monotonically, exactly
+    1 from t = R on; 1 for R = 0 (no ramp-up).  A plain host function: ``SegEngine.train_step`` multiplies ``distill_weight`` by
+    it."""
+    t, R = int(t), int(rampup)
+    if t < 0 or R < 0:
+        raise ValueError("consistency_ramp: t and rampup count from 0")
+    if R == 0 or t >= R:
+        return 1.0
+    return math.exp(-5.0 * (1.0 - t / R) ** 2)
 
 
 class EMA:

@@ -129,6 +129,12 @@ def elastic_affine(S: int, pts) -> np.ndarray:
     return np.linalg.inv(M)[:2]
 
 
+def weak_params(params):
+    """The draws ``params`` with the photometric stage neutralised (no CLAHE, identity brightness / contrast / gamma tables) and
+    the geometry kept (crop, flip, rot90, the non-rigid member and its draws): the teacher's view in mean-teacher training."""
+    return [{**p, "clahe": None, "alpha": 1.0, "beta": 0.0, "gamma": None} for p in params]
+
+
 class TrainAugment:
     def __init__(self, size: int = 588, seed: int = 0, crop_p: float = 0.5, pad_p: float = 1.0, flip_p: float = 0.5,
                  rot_p: float = 0.5, clahe_p: float = 0.8, bc_p: float = 0.8, gamma_p: float = 0.8,
@@ -255,8 +261,10 @@ class TrainAugment:
             out.update(self.nonrigid_tables(params, device))
         return out
 
-    def __call__(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, params=None):
-        """uint8 [B,S,S,3] + uint8 [B,S,S] on the device -> (fp32 [B,3,S,S] in [0,1], int64 [B,S,S])."""
+    def __call__(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, params=None, return_params: bool = False):
+        """uint8 [B,S,S,3] + uint8 [B,S,S] on the device -> (fp32 [B,3,S,S] in [0,1], int64 [B,S,S]); ``return_params`` appends the
+        parameters used (the ones drawn when ``params`` is None)."""
         if params is None:
             params = self.draw(img_u8.shape[0])
-        return ops.augment(img_u8, mask_u8, self.tables(params, img_u8.device))
+        out = ops.augment(img_u8, mask_u8, self.tables(params, img_u8.device))
+        return (*out, params) if return_params else out

@@ -60,24 +60,32 @@ _AUGMENTERS = {}
 _IDENTITY = {"crop": None, "flip": False, "rotk": 0, "alpha": 1.0, "beta": 0.0, "gamma": None}
 
 
-def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0):
+def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0, weak: bool = False):
     """Batch from the loader -> (float [B,3,S,S] in [0,1], long [B,S,S]) on the device.  uint8 HWC batches (``tools.dataset.Robomis``
     without a host transform) go through the GPU augmentation pipeline (`train.py:139-163`) when training, and through the same
     kernel with identity parameters (= `/255`, `tools/dataset.py:159`; the reference's val transform is a no-op Resize to the
     image size, `train.py:119-122`) when validating.  A ``tools.dataset.collate_frames`` batch (native-size frames) is uploaded and
-    resized on the device first (``ops.frame_resize``, PIL-exact), then takes the same uint8 path."""
+    resized on the device first (``ops.frame_resize``, PIL-exact), then takes the same uint8 path.
+    ``weak`` (training batches, --distill_weak): -> (inp, target, teacher_inp), the third the same frames under the same drawn
+    geometry without the photometric stage (``tools.augment.weak_params``: a second ``ops.augment`` call, no further draw); a batch
+    that does not go through the GPU augmentation has no photometric stage, its ``teacher_inp`` is ``inp`` itself."""
     from .tools.dataset import FrameBatch
     if isinstance(inp, FrameBatch):
         inp, target = _resize_frames(inp)
     inp, target = inp.cuda(non_blocking=True), target.cuda(non_blocking=True)
     if inp.dtype != torch.uint8:
-        return inp, target
+        return (inp, target, inp) if weak else (inp, target)
     from .tools.augment import TrainAugment
     S = inp.shape[1]
     aug = _AUGMENTERS.get(S)
     if aug is None or (train and aug.non_rigid_p != non_rigid_p):     # --aug_non_rigid: training batches only
         aug = _AUGMENTERS[S] = TrainAugment(size=S, seed=1000 + utils.get_rank(), non_rigid_p=non_rigid_p if train else 0.0)
-    return aug(inp.contiguous(), target.to(torch.uint8).contiguous(), None if train else [dict(_IDENTITY) for _ in range(inp.shape[0])])
+    img, msk = inp.contiguous(), target.to(torch.uint8).contiguous()
+    if not weak:
+        return aug(img, msk, None if train else [dict(_IDENTITY) for _ in range(inp.shape[0])])
+    from .tools.augment import weak_params
+    x, y, params = aug(img, msk, None, return_params=True)
+    return x, y, aug(img, msk, weak_params(params))[0]
 
 
 def _resize_frames(fb):
@@ -207,6 +215,98 @@ def check_backbone_args(args) -> Optional[str]:
     return None
 
 
+DISTILL_FLAGS = ("distill_teacher_arch", "distill_teacher_ema", "distill_weight", "distill_temperature", "distill_threshold",
+                 "distill_rampup", "distill_flip", "distill_weak")
+
+
+def check_distill_args(args) -> Optional[str]:
+    """What is wrong with the combination of the mean-teacher flags (--distill_*), or None.  Needs no device and no process group."""
+    t = getattr(args, "distill_teacher", None)
+    if t is None:
+        given = [f for f in DISTILL_FLAGS if getattr(args, f, None) is not None and getattr(args, f) is not False]
+        return f"--{given[0]} needs --distill_teacher (ema or the path of a checkpoint)" if given else None
+    if t == "ema":
+        if getattr(args, "ema_decay", None) is None:
+            return "--distill_teacher ema needs --ema_decay: the teacher is the average of the weights"
+        if getattr(args, "distill_teacher_arch", None) is not None or getattr(args, "distill_teacher_ema", False):
+            return "--distill_teacher_arch / --distill_teacher_ema describe a checkpoint teacher: not with --distill_teacher ema"
+    elif not os.path.isfile(t):
+        return f"--distill_teacher {t}: no such checkpoint (ema, or the path of a file train_seg wrote)"
+    elif getattr(args, "distill_teacher_arch", None) is not None and args.distill_teacher_arch not in ARCH_FFN:
+        return f"--distill_teacher_arch must be one of {sorted(ARCH_FFN)}"
+    w, T = getattr(args, "distill_weight", None), getattr(args, "distill_temperature", None)
+    th, R = getattr(args, "distill_threshold", None), getattr(args, "distill_rampup", None)
+    if w is not None and not float(w) >= 0.0:
+        return "--distill_weight must be >= 0"
+    if T is not None and not float(T) > 0.0:
+        return "--distill_temperature must be > 0"
+    if th is not None and not float(th) <= 1.0:
+        return "--distill_threshold must be at most 1 (0 or less keeps every pixel)"
+    if R is not None and int(R) < 0:
+        return "--distill_rampup counts steps: it must be >= 0"
+    return None
+
+
+def _distill_engine_args(args, teacher) -> dict:
+    """The mean-teacher flags as ``SegEngine`` arguments (``teacher``: "ema" or the engine ``build_teacher`` made); without
+    --distill_teacher nothing is passed and the engine is what it was."""
+    if teacher is None:
+        return {}
+    pick = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)
+    return {"teacher": teacher, "distill_weight": float(pick("distill_weight", 1.0)),
+            "distill_temperature": float(pick("distill_temperature", 1.0)), "distill_threshold": getattr(args, "distill_threshold", None),
+            "distill_rampup": int(pick("distill_rampup", 0)), "distill_flip": bool(getattr(args, "distill_flip", False))}
+
+
+def teacher_shares_backbone(args, src: dict) -> bool:
+    """Whether a checkpoint teacher runs on the student's ViT module: the same architecture, a student that does not step the
+    backbone weights (no --optimize_backbone) and a teacher file (``src``: the entry loaded) without a 'backbone' / 'lora' entry;
+    otherwise the teacher owns one."""
+    same = (getattr(args, "distill_teacher_arch", None) or args.arch) == args.arch
+    return same and not getattr(args, "optimize_backbone", False) and "backbone" not in src and "lora" not in src
+
+
+def build_teacher(args, head: str, num_classes: int, dev, student_model) -> SegEngine:
+    """The frozen teacher of --distill_teacher PATH: modules as ``build_modules`` makes them for --distill_teacher_arch (default:
+    the student's), the checkpoint loaded as ``adaptersis_amd.predict`` loads it (--distill_teacher_ema: its 'ema' entry), one
+    ``SegEngine`` that is never stepped."""
+    import copy
+    from . import predict as _p
+    from .lora import LoRA
+    path = args.distill_teacher
+    ck = _p.read_checkpoint(path)
+    _p.modules_not_in_checkpoint(ck, None, path)
+    src = ck
+    if getattr(args, "distill_teacher_ema", False):
+        src = ck.get("ema")
+        if not isinstance(src, dict) or "state_dict" not in src:
+            raise ValueError(f"{path} holds no 'ema' entry: --distill_teacher_ema needs a checkpoint of a run with --ema_decay")
+    targs = copy.copy(args)
+    targs.arch = getattr(args, "distill_teacher_arch", None) or args.arch
+    targs.drop_path = 0.0
+    shared = teacher_shares_backbone(args, src)
+    model, enc, cv, cn, dec = build_modules(targs, head, num_classes, dev, model=student_model if shared else None)
+    eng = SegEngine(model, enc, cv, cn, dec, num_classes=num_classes)
+    _p.load_checkpoint(path, dec, {"cross_vit": cv, "cross_cnn": cn, "backbone_encoder": enc, "backbone": model},
+                       hint=f" (the teacher: --distill_teacher_arch {targs.arch}, {num_classes} classes)", ck=src)
+    if "lora" in src:
+        eng.lora = LoRA.from_state(model, src["lora"])
+    print(f"teacher: loaded {path} (epoch {ck.get('epoch')}" + ("; averaged weights" if src is not ck else "")
+          + ("; on the student's ViT" if shared else "; on a ViT of its own") + ")")
+    return eng
+
+
+class _DistillEntry:
+    """the ``distill`` entry of a checkpoint as ``restart_from_checkpoint`` sees it: the step count of the ramp-up"""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def load_state_dict(self, entry):
+        self.engine.distill_step = int(entry["step"])
+        return f"<distill step {self.engine.distill_step}>"
+
+
 def _ema_args(args) -> dict:
     """The weight-averaging flags (--ema_decay, --ema_no_warmup) as ``SegEngine`` arguments; without --ema_decay nothing is passed
     and the engine is what it was."""
@@ -232,12 +332,7 @@ def _loss_args(args) -> dict:
     return {"topk_percent": getattr(args, "topk_percent", 10.0), "focal_gamma": getattr(args, "focal_gamma", 2.0)}
 
 
-def build_modules(args, head: str, num_classes: int, dev):
-    """The five modules of `train.py:170-191` on ``dev``, constructed in the reference's order (so a seeded run draws the same
-    initial weights wherever it is called from: ``train_seg`` and ``adaptersis_amd.predict``):
-    -> (model, backbone_encoder, cross_vit, cross_cnn, seg_decoder)."""
-    arch = args.arch if args.arch in ARCH_FFN else "vit_large"
-    D = W.VIT_CONFIGS[arch][0]
+def _build_vit(args, arch: str, dev):
     # dinov2/eval/setup.py:62-75 + models/__init__.py:14-29 (teacher, img_size 518, layerscale 1e-5, block_chunks 0)
     model = vits.__dict__[arch](patch_size=args.patch_size, img_size=518, init_values=1e-5, ffn_layer=ARCH_FFN[arch],
                                 block_chunks=0, drop_path_rate=float(getattr(args, "drop_path", 0.0)),
@@ -247,7 +342,18 @@ def build_modules(args, head: str, num_classes: int, dev):
     else:
         model.load_state_dict(W.make_vit_state_dict(arch, patch_size=args.patch_size, layerscale="init"))
         print("No pretrained weights: deterministic synthetic initialisation (adaptersis_amd.utils.weights)")
-    model = model.to(dev).eval()
+    return model.to(dev).eval()
+
+
+def build_modules(args, head: str, num_classes: int, dev, model=None):
+    """The five modules of `train.py:170-191` on ``dev``, constructed in the reference's order (so a seeded run draws the same
+    initial weights wherever it is called from: ``train_seg`` and ``adaptersis_amd.predict``):
+    -> (model, backbone_encoder, cross_vit, cross_cnn, seg_decoder).  ``model``: a ViT of this architecture that exists already
+    (a teacher on the student's backbone): none is built."""
+    arch = args.arch if args.arch in ARCH_FFN else "vit_large"
+    D = W.VIT_CONFIGS[arch][0]
+    if model is None:
+        model = _build_vit(args, arch, dev)
     backbone_encoder = FeatureEncoder(embed_dim=D).to(dev)
     cross_vit = CAViT(dim=D, n_levels=3, num_heads=8, init_values=0.0, n_points=4).to(dev)
     cross_cnn = CACNN(dim=D, n_levels=1, num_heads=8, n_points=4, with_cffn=True, cffn_ratio=0.25).to(dev)
@@ -272,7 +378,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     non_rigid_p = float(getattr(args, "aug_non_rigid", 0.0))
     if not 0.0 <= non_rigid_p <= 1.0:
         raise ValueError("--aug_non_rigid must be a probability in [0, 1]")
-    bad = check_backbone_args(args)
+    bad = check_backbone_args(args) or check_distill_args(args)
     if bad:
         raise ValueError(bad)
     utils.init_distributed_mode(args)
@@ -284,19 +390,26 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     # rank 0's parameters and buffers: without it every rank would train its own randomly initialised copy
     broadcast_module_states([backbone_encoder, cross_vit, cross_cnn, seg_decoder])
     wd = getattr(args, "weight_decay", None)   # --weight_decay; default: the script's own value
+    # --distill_teacher: "ema" = the engine's own average; a path = a frozen engine built after the student's modules (whose
+    # initial draws are then those of a run without the flag)
+    teacher = getattr(args, "distill_teacher", None)
+    if teacher is not None and teacher != "ema":
+        teacher = build_teacher(args, head, num_classes, dev, model)
+    distill = _distill_engine_args(args, teacher)
     if head == "mla":
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
                              weight_decay=0.0 if wd is None else wd, num_classes=num_classes, loss=loss, **_optimizer_args(args),
-                             **_loss_args(args), **_backbone_args(args), **_ema_args(args))
+                             **_loss_args(args), **_backbone_args(args), **_ema_args(args), **distill)
     else:
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=args.lr,
                              weight_decay=3e-5 if wd is None else wd,
                              mode="train_adapters" if getattr(args, "train_adapters", False) else "reference_exact",
                              train_encoder=getattr(args, "train_encoder", False), num_classes=num_classes, loss=loss,
-                             **_optimizer_args(args), **_loss_args(args), **_backbone_args(args), **_ema_args(args))
+                             **_optimizer_args(args), **_loss_args(args), **_backbone_args(args), **_ema_args(args), **distill)
     optimizer = engine.optimizer
     engine.aug_non_rigid = non_rigid_p      # read by train(): its signature is the reference's and carries no arguments
+    engine.distill_weak = bool(getattr(args, "distill_weak", False))
 
     dataset_train, dataset_val, collate = open_datasets(args)
     workers = args.num_workers if collate is not None else 0      # PNG decode runs in loader workers; tensors in memory do not need any
@@ -351,7 +464,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     resumed = os.path.isfile(ckpt_path)
     utils.restart_from_checkpoint(ckpt_path, run_variables=to_restore,
                                   state_dict=seg_decoder, **extra, **({} if lora is None else {"lora": lora}), optimizer=optimizer,
-                                  scheduler=scheduler, **({} if ema_entry is None else {"ema": ema_entry}))
+                                  scheduler=scheduler, **({} if ema_entry is None else {"ema": ema_entry}),
+                                  **({} if engine.teacher is None else {"distill": _DistillEntry(engine)}))
     if ema_entry is not None and resumed and not ema_entry.loaded:
         engine.ema.reset()
         print(f"=> no usable 'ema' entry in '{ckpt_path}': the average starts from the restored live weights")
@@ -400,6 +514,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                 ckpt["lora"] = lora.state_dict()
             if engine.ema is not None:
                 ckpt["ema"] = engine.ema_state_dict()
+            if engine.teacher is not None:     # --distill_teacher: where the ramp-up of the consistency weight stands
+                ckpt["distill"] = {"step": engine.distill_step}
             torch.save(ckpt, os.path.join(args.output_dir, "checkpoint.pth.tar"))
     print("Training of the supervised linear classifier on frozen features completed.\n"
           "Top-1 test accuracy: {acc:.1f}".format(acc=best_acc))
@@ -423,9 +539,13 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
     for (inp, target, idx) in metric_logger.log_every(loader, 20, "Epoch: [{}]".format(epoch)):
         if ragged:
             parallel.set_batch_ratio(int(inp.shape[0]))
-        loss = engine.train_step(*_to_device_batch(inp, target, train=True, non_rigid_p=getattr(engine, "aug_non_rigid", 0.0)))
+        batch = _to_device_batch(inp, target, train=True, non_rigid_p=getattr(engine, "aug_non_rigid", 0.0),
+                                 weak=engine.teacher is not None and getattr(engine, "distill_weak", False))
+        loss = engine.train_step(batch[0], batch[1], None, *batch[2:])
         torch.cuda.synchronize()  # the reference syncs and reads the loss every step (train.py:439-440)
         metric_logger.update(loss=loss.item())
+        if engine.teacher is not None:     # the soft term and the share of the pixels its confidence gate let through
+            metric_logger.update(loss_kd=engine.last_loss_kd.item(), kd_kept=engine.last_kd_kept.item() / batch[1].numel())
         metric_logger.update(lr=optimizer.param_groups[0]["lr"])
         if with_norm:
             metric_logger.update(grad_norm=optimizer.last_grad_norm)
@@ -491,7 +611,7 @@ class _ArgumentParser(argparse.ArgumentParser):
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        bad = check_backbone_args(ns)
+        bad = check_backbone_args(ns) or check_distill_args(ns)
         if bad:
             self.error(bad)
         return ns, rest
@@ -558,6 +678,22 @@ def get_args_parser():
                    help="with --ema_decay: use D from the first update on instead of min(D, (1 + t) / (10 + t))")
     p.add_argument("--ema_validate_live", action="store_true",
                    help="with --ema_decay: also validate the live weights and log their metrics as test_live_*")
+    # extension: mean-teacher training (SegEngine teacher=): a consistency loss against the averaged weights or a frozen checkpoint
+    p.add_argument("--distill_teacher", default=None, type=str, metavar="ema|PATH",
+                   help="add a gated consistency term (ops.consistency_loss) against a teacher: 'ema' = this run's averaged weights "
+                        "(needs --ema_decay), or the checkpoint of an earlier run (a frozen teacher)")
+    p.add_argument("--distill_teacher_arch", default=None, type=str, help="architecture of a checkpoint teacher (default: --arch)")
+    p.add_argument("--distill_teacher_ema", action="store_true", help="checkpoint teacher: load its 'ema' entry, as predict --ema does")
+    p.add_argument("--distill_weight", default=None, type=float, help="weight of the consistency term (default 1)")
+    p.add_argument("--distill_temperature", default=None, type=float, help="temperature of both distributions (default 1)")
+    p.add_argument("--distill_threshold", default=None, type=float,
+                   help="keep a pixel where the teacher's largest class probability (at the temperature) reaches this (default: all)")
+    p.add_argument("--distill_rampup", default=None, type=int, metavar="STEPS",
+                   help="ramp the weight up over this many steps by exp(-5 (1 - t / STEPS)^2) (default 0: none)")
+    p.add_argument("--distill_flip", action="store_true", help="the teacher also sees the mirrored batch (two views averaged)")
+    p.add_argument("--distill_weak", action="store_true",
+                   help="the teacher sees the batch under the student's geometry without CLAHE / brightness-contrast / gamma "
+                        "(uint8 datasets; other batches have no photometric stage)")
     # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
     p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
                    help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that; "
