@@ -61,12 +61,7 @@ def lib() -> C.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise AsisError(
-            f"{LIB_PATH} is missing: build it with `python -m adaptersis_amd.build` "
-            "(hipcc --offload-arch=gfx950). adaptersis_amd has no fallback path.")
-    _lib = C.CDLL(LIB_PATH)
-    _declare(_lib)
+    _lib = load(LIB_PATH, SIGNATURES)
     _lib.asis_last_error.restype = _lib.asis_gemm_form_name.restype = C.c_char_p
     _lib.asis_lovasz_scratch_bytes.restype = _lib.asis_hardpixel_scratch_bytes.restype = C.c_int64
     _lib.asis_surface_quantile_scratch_bytes.restype = C.c_int64
@@ -242,11 +237,19 @@ SIGNATURES = {
 }
 
 
-def _declare(l: C.CDLL) -> None:
-    for name, argtypes in SIGNATURES.items():
+def load(path: str, signatures) -> C.CDLL:
+    """Open the library at ``path`` and declare ``signatures`` (name -> argtypes, every function returning int): what ``lib()``
+    here and in _lib_distill / _lib_consist does once.  No fallback: a missing library raises."""
+    if not os.path.exists(path):
+        raise AsisError(
+            f"{path} is missing: build it with `python -m adaptersis_amd.build` "
+            "(hipcc --offload-arch=gfx950). adaptersis_amd has no fallback path.")
+    l = C.CDLL(path)
+    for name, argtypes in signatures.items():
         fn = getattr(l, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.argtypes = argtypes
         fn.restype = C.c_int
+    return l
 
 
 def check(rc: int, what: str = "") -> None:

@@ -30,12 +30,5 @@ def lib() -> C.CDLL:
     if _dlib is not None:
         return _dlib
     _lib.lib()
-    if not os.path.exists(LIB_PATH):
-        raise _lib.AsisError(f"{LIB_PATH} is missing: build it with `python -m adaptersis_amd.build` "
-                             "(hipcc --offload-arch=gfx950). adaptersis_amd has no fallback path.")
-    _dlib = C.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(_dlib, name)
-        fn.argtypes = argtypes
-        fn.restype = C.c_int
+    _dlib = _lib.load(LIB_PATH, SIGNATURES)
     return _dlib

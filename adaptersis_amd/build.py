@@ -34,7 +34,8 @@ def _hipcc() -> str:
 
 # Libraries beside libasis_hip.so: file name -> its sources.  The training step loads libasis_hip.so alone, whose source list and
 # link line do not change when an optional op arrives; such an op lives in a library of its own, loaded on first use
-# (adaptersis_amd/_lib_distill.py, _lib_consist.py), linked against libasis_hip.so for the error plumbing (asis_set_error_ / asis_last_error).
+# (adaptersis_amd/_lib_distill.py, _lib_consist.py), linked against libasis_hip.so for the error plumbing (asis_set_error_ /
+# asis_last_error).  The two here are instantiations of one kernel, csrc/soft_target.h, which neither exports.
 SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",)}
 
 
@@ -44,8 +45,9 @@ def sources():
 
 
 def _deps_mtime() -> float:
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("asis_hip.h", "asis_consist.h")]
+    """the newest header: every .h of csrc/ and every file of include/ (a change of one recompiles every source)"""
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(inc, f) for f in os.listdir(inc)]
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -82,43 +84,36 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             fcntl.flock(lk, fcntl.LOCK_UN)
 
 
-def _build_locked(force: bool, verbose: bool) -> str:
-    dep_t = _deps_mtime()
-    todo, objs = [], []
-    for src in sources():
-        obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-        objs.append(obj)
-        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), dep_t):
-            todo.append(src)
+def _stale(out: str, than: float, force: bool = False) -> bool:
+    """`out` has to be made again: forced, missing, or older than the time `than`"""
+    return force or not os.path.exists(out) or os.path.getmtime(out) < than
+
+
+def _make(out: str, srcs, dep_t: float, force: bool, verbose: bool, link_args=(), after: float = 0.0) -> None:
+    """Compile the sources whose object is stale and link `out` from all the objects, if one was compiled or `out` is older
+    than an object or than the time `after`."""
+    objs = [os.path.join(OBJ, os.path.basename(s)[:-4] + ".o") for s in srcs]
+    todo = [s for s, o in zip(srcs, objs) if _stale(o, max(os.path.getmtime(s), dep_t), force)]
     if todo:
         workers = min(len(todo), max(1, (os.cpu_count() or 4) // 2))
         with cf.ThreadPoolExecutor(workers) as ex:
             list(ex.map(lambda s: _compile(s, verbose), todo))
-    if todo or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
-        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB, *objs]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
-    for name, files in SIDE_LIBS.items():
-        _build_side(os.path.join(LIBDIR, name), [os.path.join(CSRC, f) for f in files], dep_t, force, verbose)
-    return LIB
-
-
-def _build_side(out: str, srcs, dep_t: float, force: bool, verbose: bool) -> None:
-    objs = [os.path.join(OBJ, os.path.basename(s)[:-4] + ".o") for s in srcs]
-    todo = [s for s, o in zip(srcs, objs) if force or not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), dep_t)]
-    for s in todo:
-        _compile(s, verbose)
-    if todo or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(LIB):
-        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, *objs, f"-L{LIBDIR}", "-l:libasis_hip.so",
-               "-Wl,-rpath,$ORIGIN"]
+    if todo or _stale(out, max([after] + [os.path.getmtime(o) for o in objs])):
+        cmd = [_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, *objs, *link_args]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link of {out} failed:\n{r.stdout}\n{r.stderr}")
+
+
+def _build_locked(force: bool, verbose: bool) -> str:
+    dep_t = _deps_mtime()
+    _make(LIB, sources(), dep_t, force, verbose)
+    for name, files in SIDE_LIBS.items():  # relinked when libasis_hip.so is newer
+        _make(os.path.join(LIBDIR, name), [os.path.join(CSRC, f) for f in files], dep_t, force, verbose,
+              (f"-L{LIBDIR}", "-l:libasis_hip.so", "-Wl,-rpath,$ORIGIN"), os.path.getmtime(LIB))
+    return LIB
 
 
 def main():

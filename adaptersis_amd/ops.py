@@ -1761,13 +1761,18 @@ def hardpixel_loss(logits: torch.Tensor, target: torch.Tensor, kind: int, K: int
 DISTILL_MAX_VIEWS = 8
 
 
+def _soft_scratch_bytes(binding, nblk_fn: str, n_pixels: int, doubles: int) -> int:
+    """``doubles`` doubles per workgroup of the side library ``binding`` (loaded on first use, beside libasis_hip.so)"""
+    nb = getattr(binding.lib(), nblk_fn)(int(n_pixels))
+    if nb < 0:
+        check(int(nb), nblk_fn)
+    return 8 * doubles * int(nb)
+
+
 def distill_scratch_bytes(n_pixels: int) -> int:
     """bytes of caller-owned scratch ``asis_distill_loss`` needs for ``n_pixels`` = B*H*W: one double per workgroup (needs no GPU)."""
-    from . import _lib_distill     # its library is loaded on first use, beside libasis_hip.so
-    nb = _lib_distill.lib().asis_distill_nblk(int(n_pixels))
-    if nb < 0:
-        check(int(nb), "asis_distill_nblk")
-    return 8 * int(nb)
+    from . import _lib_distill
+    return _soft_scratch_bytes(_lib_distill, "asis_distill_nblk", n_pixels, 1)
 
 
 def distill_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,
@@ -1822,11 +1827,8 @@ def _distill_args(op: str, logits, teacher_logits, size_or_target, flips, temper
 
 def consistency_scratch_bytes(n_pixels: int) -> int:
     """bytes of caller-owned scratch ``asis_consist_loss`` needs for ``n_pixels`` = B*H*W: two doubles per workgroup (needs no GPU)."""
-    from . import _lib_consist     # its library is loaded on first use, beside libasis_hip.so
-    nb = _lib_consist.lib().asis_consist_nblk(int(n_pixels))
-    if nb < 0:
-        check(int(nb), "asis_consist_nblk")
-    return 16 * int(nb)
+    from . import _lib_consist
+    return _soft_scratch_bytes(_lib_consist, "asis_consist_nblk", n_pixels, 2)
 
 
 def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,

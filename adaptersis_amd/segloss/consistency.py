@@ -17,28 +17,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .distill import _nhwc
-
-
-class _ConsistFn(torch.autograd.Function):
-    """loss(NCHW student logits) against NCHW teacher maps through ``asis_consist_loss`` (+ the resize transpose when H,W differ)"""
-
-    @staticmethod
-    def forward(ctx, x_nchw, teachers, flips, size, temperature, threshold, sample_weight, owner):
-        x = _nhwc(x_nchw)
-        loss, kept, dz = ops.consistency_loss(x, [_nhwc(t) for t in teachers], tuple(x.shape[1:3]) if size is None else size,
-                                              flips=flips, temperature=temperature, threshold=threshold, sample_weight=sample_weight)
-        owner.last_kept = kept
-        ctx.dz, ctx.hw = dz, x.shape[1:3]
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        dz = ctx.dz
-        h, w = ctx.hw
-        if tuple(dz.shape[1:3]) != (h, w):
-            dz, _ = ops.resize_bilinear_bwd(dz, h, w, torch.float32)
-        return (dz.permute(0, 3, 1, 2) * gout,) + (None,) * 7
+from .distill import _SoftTargetFn
 
 
 class ConsistencyLoss(nn.Module):
@@ -57,4 +36,10 @@ class ConsistencyLoss(nn.Module):
         if logit.dim() != 4:
             raise NotImplementedError("only (B,C,H,W) input is built")
         teachers = [teacher] if torch.is_tensor(teacher) else list(teacher)
-        return _ConsistFn.apply(logit, teachers, self.flips, size, self.temperature, self.threshold, sample_weight, self)
+
+        def op(x, ts, sz):
+            loss, self.last_kept, dz = ops.consistency_loss(x, ts, sz, flips=self.flips, temperature=self.temperature,
+                                                            threshold=self.threshold, sample_weight=sample_weight)
+            return loss, dz
+
+        return _SoftTargetFn.apply(logit, teachers, size, op)

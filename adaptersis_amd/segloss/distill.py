@@ -21,14 +21,14 @@ def _nhwc(x: torch.Tensor) -> torch.Tensor:
     return x.detach().permute(0, 2, 3, 1).contiguous().float()  # no copy when it is an NHWC buffer view
 
 
-class _DistillFn(torch.autograd.Function):
-    """loss(NCHW student logits) against NCHW teacher maps through ``asis_distill_loss`` (+ the resize transpose when H,W differ)"""
+class _SoftTargetFn(torch.autograd.Function):
+    """loss(NCHW student logits) against NCHW teacher maps through ``op(student, teachers, size) -> (loss, dz)``, both NHWC:
+    ``ops.distill_loss`` here, ``ops.consistency_loss`` in consistency.py (+ the resize transpose when H,W differ)"""
 
     @staticmethod
-    def forward(ctx, x_nchw, teachers, flips, size, temperature):
+    def forward(ctx, x_nchw, teachers, size, op):
         x = _nhwc(x_nchw)
-        loss, dz = ops.distill_loss(x, [_nhwc(t) for t in teachers], tuple(x.shape[1:3]) if size is None else size, flips=flips,
-                                    temperature=temperature)
+        loss, dz = op(x, [_nhwc(t) for t in teachers], tuple(x.shape[1:3]) if size is None else size)
         ctx.dz, ctx.hw = dz, x.shape[1:3]
         return loss.view(())
 
@@ -38,7 +38,7 @@ class _DistillFn(torch.autograd.Function):
         h, w = ctx.hw
         if tuple(dz.shape[1:3]) != (h, w):
             dz, _ = ops.resize_bilinear_bwd(dz, h, w, torch.float32)
-        return (dz.permute(0, 3, 1, 2) * gout,) + (None,) * 4
+        return (dz.permute(0, 3, 1, 2) * gout,) + (None,) * 3
 
 
 class DistillationLoss(nn.Module):
@@ -53,4 +53,5 @@ class DistillationLoss(nn.Module):
         if logit.dim() != 4:
             raise NotImplementedError("only (B,C,H,W) input is built")
         teachers = [teacher] if torch.is_tensor(teacher) else list(teacher)
-        return _DistillFn.apply(logit, teachers, self.flips, size, self.temperature)
+        return _SoftTargetFn.apply(logit, teachers, size,
+                                   lambda x, ts, sz: ops.distill_loss(x, ts, sz, flips=self.flips, temperature=self.temperature))

@@ -15,20 +15,11 @@ from adaptersis_amd import _lib, _lib_distill, ops
 from adaptersis_amd.segloss.distill import DistillationLoss
 from tests import distill_ref as R
 from tests.bound_helpers import U_ELEM, U_SUM, _bound, _err, _gen
+from tests.soft_target_helpers import STUDENT, TEACHER_SETS, _factor, _maps, _tile_sizes
 
 pytestmark = pytest.mark.gpu
 
 TEMPS = [1.0, 2.0, 4.0]
-STUDENT = (5, 7)
-TEACHER_SETS = {"same": [((5, 7), False)], "other": [((6, 4), False)], "three": [((5, 7), False), ((9, 3), True), ((4, 4), False)]}
-
-
-def _maps(B, C, hw, views, scale, *key):
-    """student NHWC [B,h,w,C], teacher maps and their flip flags, N(0,1) * scale, on the CPU"""
-    g = _gen(*key)
-    z = torch.randn((B,) + tuple(hw) + (C,), generator=g) * scale
-    ts = [torch.randn((B,) + tuple(s) + (C,), generator=g) * scale for s, _ in views]
-    return z, ts, [f for _, f in views]
 
 
 def _against_float64(dev, tag, z, ts, flips, size, temp, **kw):
@@ -74,22 +65,10 @@ def test_zero_log_zero_and_saturated_student(dev, C, views):
 
 
 # ---- 2. sizes around the tile, more workgroups than one sweep of the finalize kernel, more tiles than workgroups ------------------
-def _factor(n):
-    a = max(d for d in range(1, int(math.isqrt(n)) + 1) if n % d == 0)
-    return a, n // a
-
-
-def _tile_sizes():
-    lib = _lib_distill.lib()
-    tile, cap = lib.asis_distill_tile(), lib.asis_distill_nblk((1 << 31) - 1)
-    assert cap > 256                                                           # the finalize kernel sums 256 partials a sweep
-    return tile, cap
-
-
 @pytest.mark.parametrize("C", [3, 8])
 @pytest.mark.parametrize("which", ["tile-1", "tile", "tile+1", "257 tiles + 1"])
 def test_sizes_around_the_tile(dev, which, C):
-    tile, _ = _tile_sizes()
+    tile, _ = _tile_sizes(_lib_distill.lib(), "distill")
     N = {"tile-1": tile - 1, "tile": tile, "tile+1": tile + 1, "257 tiles + 1": 257 * tile + 1}[which]
     assert _lib_distill.lib().asis_distill_nblk(N) == -(-N // tile)
     H, Wd = _factor(N)
@@ -100,7 +79,7 @@ def test_sizes_around_the_tile(dev, which, C):
 def test_more_tiles_than_workgroups(dev):
     """a workgroup walks several tiles (the grid is capped); C = 3 only: the walk does not depend on the store path, and the
     float64 restatement of 2 M pixels x 8 classes would take the seconds a test has"""
-    tile, cap = _tile_sizes()
+    tile, cap = _tile_sizes(_lib_distill.lib(), "distill")
     N = cap * tile + 1
     assert _lib_distill.lib().asis_distill_nblk(N) == cap
     H, Wd = _factor(N)
@@ -156,7 +135,7 @@ def test_accumulation(dev, C):
 # ---- 6. determinism and scaling ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C", [3, 8])
 def test_determinism_and_scaling(dev, C):
-    tile, _ = _tile_sizes()
+    tile, _ = _tile_sizes(_lib_distill.lib(), "distill")
     z, ts, flips = _maps(2, C, STUDENT, TEACHER_SETS["three"], 1.0, 8, C)
     zd, td = z.to(dev), [t.to(dev) for t in ts]
     size = (61, 3 * tile // 61)                              # several workgroups
