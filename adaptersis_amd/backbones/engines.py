@@ -182,7 +182,8 @@ class SegEngine(nn.Module):
                  drop_path_seed: int = 0, lora_rank: Optional[int] = None, lora_alpha: Optional[float] = None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, teacher=None, distill_weight: float = 1.0,
                  distill_temperature: float = 1.0, distill_threshold: Optional[float] = None, distill_rampup: int = 0,
-                 distill_flip: bool = False):
+                 distill_flip: bool = False, mix: Optional[str] = None, mix_p: float = 1.0, mix_seed: int = 0,
+                 mix_background: bool = False):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -229,7 +230,15 @@ class SegEngine(nn.Module):
         ``distill_flip``, of its mirror image) under the guard of ``predict``, then adds ``ops.consistency_loss`` against them
         (``distill_temperature``, ``distill_threshold``) to the hard loss: total = hard + lambda_t kd with lambda_t =
         ``distill_weight`` * ``optim.consistency_ramp(distill_step, distill_rampup)``, ``distill_step`` the number of steps so
-        far (a host counter)."""
+        far (a host counter).
+
+        ``mix`` (default None: nothing is drawn, allocated, launched or loaded, the step is the one without the keyword): "cutmix"
+        or "classmix" — every ``train_step`` draws the tables of ``tools.mix.MixSampler(mix, mix_p, mix_seed, num_classes,
+        mix_background)`` for step ``mix_step`` (a host counter) and rank ``mix_rank`` (an attribute, default 0), and, where the
+        draw mixes a sample, the student's forward and the hard loss see ``ops.mix_batch`` of the batch.  A teacher still sees the
+        unmixed batch; the consistency term reads its maps through the same mixing (``ops.consistency_loss(mix=)``).  A step
+        whose draw mixes no sample is the unmixed step.  ``last_mix_pasted``: int32 [B] on the device, the pasted pixels per
+        sample of the last step (None where nothing was mixed)."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -368,6 +377,12 @@ class SegEngine(nn.Module):
         self.distill_rampup, self.distill_flip = int(distill_rampup), bool(distill_flip)
         self.distill_step = 0
         self.last_loss_kd = self.last_kd_kept = None
+        self.mix_sampler = None
+        if mix is not None:
+            from ..tools.mix import MixSampler
+            self.mix_sampler = MixSampler(mix, mix_p, mix_seed, num_classes, mix_background)
+        self.mix_step, self.mix_rank = 0, 0
+        self.last_mix_pasted = None
 
     ema_weights = ema_weights
 
@@ -385,14 +400,30 @@ class SegEngine(nn.Module):
         with self.ema_weights():
             return self._guarded_logits(views), flips
 
-    def _add_consistency(self, logits, target, dz, hard, maps, flips, S: float, taps: Optional[dict]) -> torch.Tensor:
-        """The soft term of a step with a teacher: ``ops.consistency_loss`` against ``maps`` added into the hard term's ``dz`` at
-        S lambda_t -> hard + lambda_t kd (a device tensor, no host sync).  Counts the step."""
+    def _mix(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict]):
+        """The draw of step ``mix_step`` and, where it mixes a sample, ``ops.mix_batch`` -> (inp, target, (sel, donor) or None).
+        Counts the step."""
+        tables = self.mix_sampler.draw(inp.shape[0], inp.shape[-2], inp.shape[-1], self.mix_step, self.mix_rank)
+        self.mix_step += 1
+        self.last_mix_pasted = None
+        if not bool(tables["kind"].any()):
+            return inp, target, None
+        inp, target, sel, pasted = ops.mix_batch(inp.contiguous(), target.long().contiguous(), tables, self.num_classes,
+                                                 self.mix_sampler.background)
+        self.last_mix_pasted = pasted
+        if taps is not None:
+            taps.update(mix_inp=inp, mix_target=target, mix_sel=sel, mix_tables=tables, mix_pasted=pasted)
+        return inp, target, (sel, tables["donor"])
+
+    def _add_consistency(self, logits, target, dz, hard, maps, flips, S: float, taps: Optional[dict], mix=None) -> torch.Tensor:
+        """The soft term of a step with a teacher: ``ops.consistency_loss`` against ``maps`` (read through ``mix`` where the
+        batch was mixed) added into the hard term's ``dz`` at S lambda_t -> hard + lambda_t kd (a device tensor, no host sync).
+        Counts the step."""
         lam = self.distill_weight * consistency_ramp(self.distill_step, self.distill_rampup)
         self.distill_step += 1
         scratch = _loss_scratch(self, "_consist_scratch", ops.consistency_scratch_bytes(target.numel()), logits.device)
         kd, kept, _ = ops.consistency_loss(logits, maps, target, flips=flips, temperature=self.distill_temperature,
-                                           threshold=self.distill_threshold, grad_scale=S * lam, dz=dz, scratch=scratch)
+                                           threshold=self.distill_threshold, grad_scale=S * lam, dz=dz, scratch=scratch, mix=mix)
         self.last_loss_kd, self.last_kd_kept = kd, kept
         total = hard + lam * kd
         if taps is not None:
@@ -727,12 +758,17 @@ class SegEngine(nn.Module):
                    teacher_inp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One `train.py:268-436` (or `train_mla.py:260-407`) iteration; returns the loss as a 0-dim device
         tensor (no host sync).  With a ``teacher``: the teacher sees ``teacher_inp`` (default ``inp``; the same geometry), and the
-        loss is hard + lambda_t kd (``taps``: ``loss_hard``, ``loss_kd``, ``kd_kept``, ``teacher_logits``, ``distill_scale``)."""
+        loss is hard + lambda_t kd (``taps``: ``loss_hard``, ``loss_kd``, ``kd_kept``, ``teacher_logits``, ``distill_scale``).  With
+        ``mix``: the teacher sees the unmixed batch, the student's forward and the hard loss the mixed one (``taps``: ``mix_inp``,
+        ``mix_target``, ``mix_sel``, ``mix_tables``, ``mix_pasted``)."""
         _check_trainable(self)
         if self.teacher is not None:   # before the student's forward: the teacher's activations are gone when the student's are saved
             tmaps, tflips = self._teacher_maps(inp if teacher_inp is None else teacher_inp)
         elif teacher_inp is not None:
             raise ValueError("train_step: teacher_inp without a teacher")
+        mixed = None
+        if self.mix_sampler is not None:   # after the teacher, which sees the batch as it came
+            inp, target, mixed = self._mix(inp, target, taps)
         dec = self.seg_decoder
         S = config.loss_scale
         asaves = None
@@ -755,7 +791,7 @@ class SegEngine(nn.Module):
         target = target.long().contiguous()
         loss, dz = loss_and_dz(self, logits, target, S)
         if self.teacher is not None:
-            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, S, taps)
+            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, S, taps, mixed)
         B, hh, ww, C = logits.shape
         r = ops.resize_bilinear_bwd(dz, hh, ww, config.operand_dtype, config.split_conv)
         d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])

@@ -34,9 +34,10 @@ def _hipcc() -> str:
 
 # Libraries beside libasis_hip.so: file name -> its sources.  The training step loads libasis_hip.so alone, whose source list and
 # link line do not change when an optional op arrives; such an op lives in a library of its own, loaded on first use
-# (adaptersis_amd/_lib_distill.py, _lib_consist.py), linked against libasis_hip.so for the error plumbing (asis_set_error_ /
-# asis_last_error).  The two here are instantiations of one kernel, csrc/soft_target.h, which neither exports.
-SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",)}
+# (adaptersis_amd/_lib_distill.py, _lib_consist.py, _lib_mix.py), linked against libasis_hip.so for the error plumbing
+# (asis_set_error_ / asis_last_error).  The first two are instantiations of one kernel, csrc/soft_target.h, which neither exports;
+# the third holds the batch-mixing kernels and that kernel's instantiation over a mixed batch.
+SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",), "libasis_mix.so": ("mix.hip",)}
 
 
 def sources():

@@ -1,6 +1,7 @@
 // The soft-target loss that distill.hip and consist.hip export: one kernel body, its finalize kernel and the host code in front of
-// them, included by those two sources and by nothing in libasis_hip.so.  distill.hip documents the arithmetic, consist.hip what
-// the gate and the weight add; the gate is a type (NoGate / Gate), so the ungated kernel carries none of it.
+// them, included by those two sources and by mix.hip, and by nothing in libasis_hip.so.  distill.hip documents the arithmetic,
+// consist.hip what the gate and the weight add, mix.hip what the mixing adds; the gate is a type (NoGate / Gate / MixGate), so the
+// ungated kernel carries nothing of the gate and neither of the first two anything of the mixing.
 //
 // A tile is 256 threads x 4 pixels, pixel = tile*1024 + item*256 + thread (consecutive threads hold consecutive pixels:
 // coalesced); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ...  The sums have a fixed order: per thread the
@@ -28,13 +29,23 @@ struct StViews {
 
 // every pixel of every sample takes part with weight 1: one partial per workgroup
 struct NoGate {
-  static constexpr bool on = false;
+  static constexpr bool on = false, mix = false;
 };
 // a pixel takes part where max_c q_c >= threshold, times sample_weight[b] (NULL: 1): two partials per workgroup, loss and kept
 struct Gate {
-  static constexpr bool on = true;
+  static constexpr bool on = true, mix = false;
   float threshold;
   const float* sample_weight;
+};
+// Gate over a mixed batch (mix.hip): where sel[i] != 0 every teacher map of pixel i is read from sample donor[b], at the same
+// (y, x); the student, the weight and dz are sample b's.  A donor outside 0..B-1 is read as b: it is never an address.
+struct MixGate {
+  static constexpr bool on = true, mix = true;
+  float threshold;
+  const float* sample_weight;
+  const uint8_t* sel;
+  const int* donor;
+  int B;
 };
 
 // sample_logits of bilinear_tap.h for a map whose columns may be mirrored
@@ -113,6 +124,13 @@ __global__ __launch_bounds__(RX_THREADS) void st_kernel(const float* __restrict_
           continue;
         }
       }
+      int bt = b;  // the sample the teacher's maps are read from
+      if constexpr (G::mix) {
+        if (gate.sel[i]) {
+          const int d = gate.donor[b];
+          if ((unsigned)d < (unsigned)gate.B) bt = d;
+        }
+      }
       float p[CB], zs[CB], q[CB];
 #pragma unroll
       for (int c = 0; c < CB; ++c) p[c] = zs[c] = q[c] = 0.f;
@@ -126,7 +144,9 @@ __global__ __launch_bounds__(RX_THREADS) void st_kernel(const float* __restrict_
         const int hk = student ? h : vs.h[k], wk = student ? w : vs.w[k];
         const float* lg = student ? logits : vs.p[k];
         float t[MAXC];  // MAXC: the row softmax_c of bilinear_tap.h takes; entries >= CB are never touched
-        sample_view<CB>(lg + (int64_t)b * hk * wk * C, hk, wk, C, y, x, H, W, !student && vs.flip[k] != 0, t);
+        int bk = b;
+        if constexpr (G::mix) bk = student ? b : bt;
+        sample_view<CB>(lg + (int64_t)bk * hk * wk * C, hk, wk, C, y, x, H, W, !student && vs.flip[k] != 0, t);
 #pragma unroll
         for (int c = 0; c < CB; ++c)
           if (c < C) t[c] = __fmul_rn(t[c], inv_t);
@@ -243,8 +263,8 @@ inline int st_nblk(const char* op, int64_t N) {
   return asis_grid(st_ntile(N), 1, ST_MAX_BLOCKS);
 }
 
-// asis_distill_loss (NoGate; kept unused) and asis_consist_loss (Gate): the argument checks under the name `op`, the launch by
-// class count and the finalize
+// asis_distill_loss (NoGate; kept unused), asis_consist_loss (Gate) and asis_mix_consist_loss (MixGate): the argument checks under
+// the name `op`, the launch by class count and the finalize
 template <typename G>
 int st_loss(const char* op, G gate, void* stream, const float* logits, int B, int h, int w, const float* const* teachers,
             const int* hs, const int* ws, const int* flips, int V, int H, int W, int C, float temperature, float grad_scale,
@@ -256,6 +276,7 @@ int st_loss(const char* op, G gate, void* stream, const float* logits, int B, in
   ASIS_REQUIRE(temperature > 0.f, "%s: temperature=%g must be > 0", op, (double)temperature);
   if constexpr (G::on)
     ASIS_REQUIRE(gate.threshold <= 1.f, "%s: threshold=%g must be <= 1 (<= 0 keeps every pixel)", op, (double)gate.threshold);
+  if constexpr (G::mix) ASIS_REQUIRE(gate.sel && gate.donor, "%s: null pointer (sel, donor)", op);
   const int64_t N = (int64_t)B * H * W;
   ASIS_REQUIRE(N < ((int64_t)1 << 31), "%s: B*H*W=%lld must be < 2^31", op, (long long)N);
   ASIS_REQUIRE((reinterpret_cast<uintptr_t>(partial) & 7) == 0, "%s: partial must be 8-byte aligned", op);

@@ -1833,7 +1833,7 @@ def consistency_scratch_bytes(n_pixels: int) -> int:
 
 def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,
                      threshold: Optional[float] = None, sample_weight: Optional[torch.Tensor] = None, grad_scale: float = 1.0,
-                     dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+                     dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, mix=None):
     """The consistency term of teacher-student training in one pass (csrc/consist.hip, libasis_consist.so): ``distill_loss`` with a
     per-pixel confidence gate, a per-sample weight and the count of the pixels the gate let through.  ``logits``,
     ``teacher_logits``, ``size_or_target``, ``flips``, ``temperature`` as there.  ``threshold`` (None or <= 0: every pixel is
@@ -1844,8 +1844,12 @@ def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, fl
     zeros on the dropped pixels; a given ``dz`` is added into on the kept pixels and neither read nor written on the others (and
     returned).  A sample of weight 0 reads none of its maps.  ``scratch``: a uint8 buffer of at least
     ``consistency_scratch_bytes(B*H*W)`` to reuse between calls (default: a fresh one).  No host sync; bit-identical from call to
-    call."""
-    from . import _lib_consist
+    call.
+    ``mix`` = (sel, donor) (default None: the call above, libasis_mix.so is not opened): the loss over a batch mixed by
+    ``mix_batch`` (csrc/mix.hip).  ``sel`` contiguous uint8 [B,H,W] on the logits' device; ``donor`` a host int32 tensor or a
+    sequence of B samples in 0..B-1 (checked here, on the host).  For pixel i of sample b every teacher map is read from sample
+    donor[b] where sel[i] is set and from b elsewhere, at the same (y, x) and through the same flips; the student, the weight, the
+    gate (on the confidence of the mixed q), kept, N and dz are as above."""
     op = "consistency_loss"
     B, h, w, V, H, W, Cc, dev, ptrs, hs, ws, fl = _distill_args(op, logits, teacher_logits, size_or_target, flips, temperature, dz,
                                                                 scratch)
@@ -1857,16 +1861,112 @@ def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, fl
         if sample_weight.dtype != torch.float32 or not sample_weight.is_contiguous() or tuple(sample_weight.shape) != (B,) \
                 or sample_weight.device != dev:
             raise ValueError(f"{op}: sample_weight must be a contiguous float32 tensor [B={B}] on {dev}")
-    N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: consistency_scratch_bytes(n), dz, scratch)
+    if mix is None:
+        from . import _lib_consist as binding
+        nblk, entry, gather = "asis_consist_nblk", "asis_consist_loss", ()
+    else:
+        from . import _lib_mix as binding
+        nblk, entry = "asis_mix_consist_nblk", "asis_mix_consist_loss"
+        sel, donor = _mix_gate_args(op, mix, B, H, W, dev)
+        gather = (sel.data_ptr(), donor.data_ptr())
+    N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: _soft_scratch_bytes(binding, nblk, n, 2), dz,
+                                                     scratch)
     if scratch.data_ptr() % 8:
         raise ValueError(f"{op}: scratch must be 8-byte aligned")
     loss = torch.empty((1,), device=dev, dtype=torch.float32)
     kept = torch.empty((1,), device=dev, dtype=torch.int32)
-    check(_lib_consist.lib().asis_consist_loss(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc,
-                                               float(temperature), thr, _p(sample_weight), float(grad_scale), int(accumulate),
-                                               scratch.data_ptr(), loss.data_ptr(), kept.data_ptr(), dz.data_ptr()),
-          "asis_consist_loss")
+    check(getattr(binding.lib(), entry)(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature), thr,
+                                        _p(sample_weight), *gather, float(grad_scale), int(accumulate), scratch.data_ptr(),
+                                        loss.data_ptr(), kept.data_ptr(), dz.data_ptr()), entry)
     return loss, kept, dz
+
+
+# --------------------------------------------------------------------------------------------
+# batch mixing (csrc/mix.hip, libasis_mix.so)
+# --------------------------------------------------------------------------------------------
+MIX_MAX_CLASSES = 16
+MIX_TABLES = {"donor": (torch.int32, ()), "kind": (torch.int32, ()), "box": (torch.int32, (4,)), "order": (torch.uint8, (16,))}
+
+
+def _host_donor(op: str, donor, B: int) -> torch.Tensor:
+    """``donor`` as a host int32 tensor [B] with every entry in 0..B-1: a bad table raises here and never reaches the device"""
+    if torch.is_tensor(donor):
+        if donor.is_cuda or donor.dtype != torch.int32:
+            raise ValueError(f"{op}: donor must be a host (CPU) int32 tensor or a sequence of ints")
+        d = donor.contiguous()
+    else:
+        d = torch.tensor([int(v) for v in donor], dtype=torch.int32)
+    if tuple(d.shape) != (B,):
+        raise ValueError(f"{op}: donor has shape {list(d.shape)}, the batch has B={B} samples")
+    if int(d.min()) < 0 or int(d.max()) >= B:
+        raise ValueError(f"{op}: donor={d.tolist()} must lie in 0..B-1={B - 1}")
+    return d
+
+
+def _upload_i32(parts, dev) -> torch.Tensor:
+    """host int32 tensors, concatenated, on ``dev`` through a pinned staging tensor and a non-blocking copy (the idiom of
+    droppath.py): the host does not wait for the stream"""
+    stage = torch.empty(sum(p.numel() for p in parts), dtype=torch.int32, pin_memory=torch.device(dev).type == "cuda")
+    torch.cat([p.reshape(-1) for p in parts], out=stage)
+    return stage.to(dev, non_blocking=True)
+
+
+def _mix_gate_args(op: str, mix, B: int, H: int, W: int, dev):
+    """(sel, donor) of ``consistency_loss(mix=)`` checked -> (sel, donor on the device)"""
+    if not isinstance(mix, (tuple, list)) or len(mix) != 2:
+        raise ValueError(f"{op}: mix must be (sel, donor)")
+    sel, donor = mix
+    if not torch.is_tensor(sel) or sel.dtype != torch.uint8 or not sel.is_contiguous() or tuple(sel.shape) != (B, H, W):
+        raise ValueError(f"{op}: mix sel must be a contiguous uint8 tensor [B={B},H={H},W={W}]")
+    if sel.device != dev:
+        raise ValueError(f"{op}: mix sel is on {sel.device}, the logits on {dev}")
+    return sel, _upload_i32([_host_donor(op, donor, B)], dev)
+
+
+def mix_batch(inp: torch.Tensor, target: torch.Tensor, tables: dict, num_classes: int, background: bool = False):
+    """CutMix / ClassMix over the samples of one batch (csrc/mix.hip, libasis_mix.so): sample b receives pixels of sample
+    donor[b].  ``inp`` contiguous fp32 [B,3,H,W], ``target`` contiguous int64 [B,H,W], both on the device; ``tables`` the host
+    (CPU) tensors of ``tools.mix.MixSampler.draw``: donor int32 [B] (0..B-1, checked here), kind int32 [B] (0 not mixed, 1 CutMix,
+    2 ClassMix), box int32 [B,4] (y0, x0, y1, x1; half-open), order uint8 [B,16].  They are uploaded in one non-blocking copy from pinned memory.
+    -> (inp', target', sel uint8 [B,H,W], pasted int32 [B]), fresh buffers: sel is 1 inside the box (kind 1) or where the donor's
+    label is one of the classes pasted (kind 2: the first half, rounded up, of the donor's classes present in 0..num_classes-1, in
+    the order order[b]; class 0 only with ``background``); inp'[b] = sel ? inp[donor[b]] : inp[b], target' likewise (copies of
+    bits); pasted[b] = the pixels with sel = 1.  No host sync; bit-identical from call to call."""
+    from . import _lib_mix
+    op = "mix_batch"
+    _dev(inp, target)
+    if inp.dim() != 4 or inp.shape[1] != 3 or inp.dtype != torch.float32 or not inp.is_contiguous():
+        raise ValueError(f"{op}: inp must be a contiguous float32 tensor [B,3,H,W]")
+    B, _, H, W = (int(v) for v in inp.shape)
+    if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != (B, H, W) or target.device != inp.device:
+        raise ValueError(f"{op}: target must be a contiguous int64 tensor [B={B},H={H},W={W}] on {inp.device}")
+    if not 1 <= int(num_classes) <= MIX_MAX_CLASSES:
+        raise ValueError(f"{op}: num_classes={num_classes} must be in 1..{MIX_MAX_CLASSES}")
+    if B * H * W >= 1 << 31:
+        raise ValueError(f"{op}: B*H*W={B * H * W} must be < 2^31")
+    if not isinstance(tables, dict) or set(MIX_TABLES) - set(tables):
+        raise ValueError(f"{op}: tables must hold {sorted(MIX_TABLES)}")
+    for name, (dtype, tail) in MIX_TABLES.items():
+        t = tables[name]
+        if not torch.is_tensor(t) or t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != (B,) + tail:
+            raise ValueError(f"{op}: tables[{name!r}] must be a contiguous host (CPU) {dtype} tensor {[B, *tail]}")
+    _host_donor(op, tables["donor"], B)
+    # one upload: donor | kind | box | order, every section on a 4-byte boundary
+    packed = _upload_i32([tables["donor"], tables["kind"], tables["box"], tables["order"].reshape(-1).view(torch.int32)], inp.device)
+    donor, kind, box, order = packed[:B], packed[B:2 * B], packed[2 * B:6 * B], packed[6 * B:]
+    lib_ = _lib_mix.lib()
+    sets = None
+    if bool((tables["kind"] == 2).any()):  # on the host copy
+        sets = torch.empty((2, B), device=inp.device, dtype=torch.int32)
+        check(lib_.asis_mix_class_sets(_stream(), target.data_ptr(), donor.data_ptr(), kind.data_ptr(), order.data_ptr(), B, H, W,
+                                       int(num_classes), int(bool(background)), sets.data_ptr()), "asis_mix_class_sets")
+    out, tout = torch.empty_like(inp), torch.empty_like(target)
+    sel = torch.empty((B, H, W), device=inp.device, dtype=torch.uint8)
+    pasted = torch.empty((B,), device=inp.device, dtype=torch.int32)
+    check(lib_.asis_mix_apply(_stream(), inp.data_ptr(), target.data_ptr(), donor.data_ptr(), kind.data_ptr(), box.data_ptr(),
+                              None if sets is None else sets[1].data_ptr(), B, H, W, out.data_ptr(), tout.data_ptr(), sel.data_ptr(),
+                              pasted.data_ptr()), "asis_mix_apply")
+    return out, tout, sel, pasted
 
 
 # --------------------------------------------------------------------------------------------

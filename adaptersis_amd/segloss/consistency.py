@@ -9,7 +9,9 @@ T = 1, the default.  ``logit`` is (B,C,h,w); ``teacher`` one (B,C,h_k,w_k) map o
 dimensions are H, W (the target); None = the student's own h, w.  ``sample_weight``: fp32 [B] on the device, finite and >= 0.
 Forward and gradient are one ``ops.consistency_loss`` call (csrc/consist.hip); the backward goes through the resize transpose
 (``ops.resize_bilinear_bwd``) when H, W differ from h, w.  ``last_kept`` holds the device count (int32 [1]) of the pixels the gate let
-through in the last forward.  No gradient reaches the teacher.
+through in the last forward.  No gradient reaches the teacher.  ``mix`` = (sel, donor): the loss over a batch mixed by
+``ops.mix_batch`` — the teacher's maps are read from sample donor[b] where sel is set (``ops.consistency_loss``); sel has the
+size the loss is evaluated at.
 """
 from __future__ import annotations
 
@@ -32,14 +34,14 @@ class ConsistencyLoss(nn.Module):
         self.flips = None if flips is None else [bool(f) for f in flips]
         self.last_kept = None
 
-    def forward(self, logit, teacher, size=None, sample_weight=None):
+    def forward(self, logit, teacher, size=None, sample_weight=None, mix=None):
         if logit.dim() != 4:
             raise NotImplementedError("only (B,C,H,W) input is built")
         teachers = [teacher] if torch.is_tensor(teacher) else list(teacher)
 
         def op(x, ts, sz):
             loss, self.last_kept, dz = ops.consistency_loss(x, ts, sz, flips=self.flips, temperature=self.temperature,
-                                                            threshold=self.threshold, sample_weight=sample_weight)
+                                                            threshold=self.threshold, sample_weight=sample_weight, mix=mix)
             return loss, dz
 
         return _SoftTargetFn.apply(logit, teachers, size, op)

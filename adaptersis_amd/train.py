@@ -296,6 +296,47 @@ def build_teacher(args, head: str, num_classes: int, dev, student_model) -> SegE
     return eng
 
 
+MIX_FLAGS = ("mix_p", "mix_seed", "mix_background")
+
+
+def check_mix_args(args) -> Optional[str]:
+    """What is wrong with the combination of the batch-mixing flags (--mix, --mix_*), or None.  Needs no device and no process group."""
+    from .tools.mix import KINDS
+    kind = getattr(args, "mix", None)
+    if kind is None:
+        given = [f for f in MIX_FLAGS if getattr(args, f, None) is not None and getattr(args, f) is not False]
+        return f"--{given[0]} needs --mix ({' or '.join(sorted(KINDS))})" if given else None
+    if kind not in KINDS:
+        return f"--mix must be one of {sorted(KINDS)}"
+    p = getattr(args, "mix_p", None)
+    if p is not None and not 0.0 <= float(p) <= 1.0:
+        return "--mix_p must be a probability in [0, 1]"
+    bs = getattr(args, "batch_size_per_gpu", None)
+    if bs is not None and int(bs) < 2:
+        return "--mix pastes pixels of another sample of the rank's batch: it needs --batch_size_per_gpu of at least 2"
+    return None
+
+
+def _mix_engine_args(args) -> dict:
+    """The batch-mixing flags as ``SegEngine`` arguments; without --mix nothing is passed and the engine is what it was."""
+    if getattr(args, "mix", None) is None:
+        return {}
+    pick = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)
+    return {"mix": args.mix, "mix_p": float(pick("mix_p", 1.0)), "mix_seed": int(pick("mix_seed", 0)),
+            "mix_background": bool(getattr(args, "mix_background", False))}
+
+
+class _MixEntry:
+    """the ``mix`` entry of a checkpoint as ``restart_from_checkpoint`` sees it: the step the next draw is seeded with"""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def load_state_dict(self, entry):
+        self.engine.mix_step = int(entry["step"])
+        return f"<mix step {self.engine.mix_step}>"
+
+
 class _DistillEntry:
     """the ``distill`` entry of a checkpoint as ``restart_from_checkpoint`` sees it: the step count of the ramp-up"""
 
@@ -378,7 +419,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     non_rigid_p = float(getattr(args, "aug_non_rigid", 0.0))
     if not 0.0 <= non_rigid_p <= 1.0:
         raise ValueError("--aug_non_rigid must be a probability in [0, 1]")
-    bad = check_backbone_args(args) or check_distill_args(args)
+    bad = check_backbone_args(args) or check_distill_args(args) or check_mix_args(args)
     if bad:
         raise ValueError(bad)
     utils.init_distributed_mode(args)
@@ -395,7 +436,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     teacher = getattr(args, "distill_teacher", None)
     if teacher is not None and teacher != "ema":
         teacher = build_teacher(args, head, num_classes, dev, model)
-    distill = _distill_engine_args(args, teacher)
+    distill = {**_distill_engine_args(args, teacher), **_mix_engine_args(args)}
     if head == "mla":
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
@@ -410,6 +451,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     optimizer = engine.optimizer
     engine.aug_non_rigid = non_rigid_p      # read by train(): its signature is the reference's and carries no arguments
     engine.distill_weak = bool(getattr(args, "distill_weak", False))
+    engine.mix_rank = utils.get_rank()      # --mix: every rank draws its own tables
 
     dataset_train, dataset_val, collate = open_datasets(args)
     workers = args.num_workers if collate is not None else 0      # PNG decode runs in loader workers; tensors in memory do not need any
@@ -465,7 +507,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     utils.restart_from_checkpoint(ckpt_path, run_variables=to_restore,
                                   state_dict=seg_decoder, **extra, **({} if lora is None else {"lora": lora}), optimizer=optimizer,
                                   scheduler=scheduler, **({} if ema_entry is None else {"ema": ema_entry}),
-                                  **({} if engine.teacher is None else {"distill": _DistillEntry(engine)}))
+                                  **({} if engine.teacher is None else {"distill": _DistillEntry(engine)}),
+                                  **({} if engine.mix_sampler is None else {"mix": _MixEntry(engine)}))
     if ema_entry is not None and resumed and not ema_entry.loaded:
         engine.ema.reset()
         print(f"=> no usable 'ema' entry in '{ckpt_path}': the average starts from the restored live weights")
@@ -516,6 +559,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                 ckpt["ema"] = engine.ema_state_dict()
             if engine.teacher is not None:     # --distill_teacher: where the ramp-up of the consistency weight stands
                 ckpt["distill"] = {"step": engine.distill_step}
+            if engine.mix_sampler is not None:  # --mix: the step the next draw is seeded with
+                ckpt["mix"] = {"step": engine.mix_step}
             torch.save(ckpt, os.path.join(args.output_dir, "checkpoint.pth.tar"))
     print("Training of the supervised linear classifier on frozen features completed.\n"
           "Top-1 test accuracy: {acc:.1f}".format(acc=best_acc))
@@ -546,6 +591,9 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
         metric_logger.update(loss=loss.item())
         if engine.teacher is not None:     # the soft term and the share of the pixels its confidence gate let through
             metric_logger.update(loss_kd=engine.last_loss_kd.item(), kd_kept=engine.last_kd_kept.item() / batch[1].numel())
+        if engine.mix_sampler is not None:  # the share of the batch's pixels that came from another sample
+            pasted = engine.last_mix_pasted
+            metric_logger.update(mix_pasted=0.0 if pasted is None else int(pasted.sum()) / batch[1].numel())
         metric_logger.update(lr=optimizer.param_groups[0]["lr"])
         if with_norm:
             metric_logger.update(grad_norm=optimizer.last_grad_norm)
@@ -611,7 +659,7 @@ class _ArgumentParser(argparse.ArgumentParser):
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        bad = check_backbone_args(ns) or check_distill_args(ns)
+        bad = check_backbone_args(ns) or check_distill_args(ns) or check_mix_args(ns)
         if bad:
             self.error(bad)
         return ns, rest
@@ -694,6 +742,13 @@ def get_args_parser():
     p.add_argument("--distill_weak", action="store_true",
                    help="the teacher sees the batch under the student's geometry without CLAHE / brightness-contrast / gamma "
                         "(uint8 datasets; other batches have no photometric stage)")
+    # extension: batch mixing (SegEngine mix=): CutMix / ClassMix on the device, with or without a teacher
+    p.add_argument("--mix", default=None, choices=["cutmix", "classmix"],
+                   help="paste pixels of another sample of the rank's batch into each sample (ops.mix_batch): cutmix = a box, "
+                        "classmix = half of the donor's classes; a teacher's targets are mixed the same way")
+    p.add_argument("--mix_p", default=None, type=float, help="probability that a sample is mixed (default 1)")
+    p.add_argument("--mix_seed", default=None, type=int, help="seed of the draws, which depend on (seed, rank, step) alone (default 0)")
+    p.add_argument("--mix_background", action="store_true", help="classmix: class 0 may be pasted too")
     # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
     p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
                    help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that; "
