@@ -204,6 +204,7 @@ __device__ __forceinline__ float erf_fast(float x) {
 // at M = 42348).  Fitted in the training container by iteratively re-weighted least squares on the ABSOLUTE gelu error;
 // float32 evaluation over [-12, 12] and the fp16 range ends: max |error| 5.1e-7 (A&S: 5.2e-7; both are the rounding of
 // x - x q near x = 4), relative error with a 1e-3 floor 8.5e-5 (A&S: 1.7e-4).  The argument is clamped at 7, where 1 - Phi is 1.3e-12.
+// Beyond |x| ~ 4e5 (bf16 / fp32 operands only) that clamp shows: a negative x returns -|x| 1.3e-12 where it should return 0.
 __device__ __forceinline__ float gelu_erf(float x) {
   const float ax = fabsf(x);
   const float a = fminf(ax, 7.0f);
