@@ -105,6 +105,43 @@ def loss_and_dz(engine, logits: torch.Tensor, target: torch.Tensor, S: float):
     return (loss if ce is None else ce.add_(loss)), dz
 
 
+def loss_head(engine, logits: torch.Tensor, target: torch.Tensor):
+    """The loss of every engine's ``train_step`` -> (loss [1], dz, target as the contiguous int64 the loss kernels read).  ``dz`` may
+    still receive further terms (``SegEngine._add_consistency``) before ``logit_gradient`` takes it to the head."""
+    target = target.long().contiguous()
+    loss, dz = loss_and_dz(engine, logits, target, config.loss_scale)
+    return loss, dz, target
+
+
+def logit_gradient(engine, dz: torch.Tensor, logits: torch.Tensor):
+    """``dz`` back through the bilinear resize to the head's logits -> (d16, d_lo | None, bias partials, inv) with ``inv`` the factor
+    every gradient kernel of the backward applies."""
+    _, hh, ww, _ = logits.shape
+    r = ops.resize_bilinear_bwd(dz, hh, ww, config.operand_dtype, config.split_conv)
+    d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])
+    inv = 1.0 / (config.loss_scale * world_size(engine.process_group))  # gradient mean over ranks folded into the un-scaling (DDP semantics)
+    return d16, d_lo, bpart, inv
+
+
+def _hi_lo(t: torch.Tensor, B: int, h: int, w: int, D: int):
+    """fp32 token map [B * h * w, D] -> the 16-bit NHWC operand of a head, (hi, lo | None) [B, h, w, D]"""
+    dt = config.operand_dtype
+    hi = ops.cast_pad(t, D, dt).view(B, h, w, D)
+    lo = ops.cast_pad(t, D, dt, part=1).view(B, h, w, D) if config.split_conv else None
+    return hi, lo
+
+
+def make_decoder_bucket(seg_decoder):
+    """The head's parameters in the gradient-ready order of its backward (final conv first, decoder_1 last) -> (flat bucket,
+    the bucket range of every stage of ``seg_decoder.GRAD_ORDER``: what a ``StageReducer`` exchanges per ``stage_done``)."""
+    order = list(seg_decoder.GRAD_ORDER)
+    named = dict(seg_decoder.named_parameters())
+    ordered = [(n, named[n]) for pre in order for n in named if n.startswith(pre + ".")]
+    assert len(ordered) == len(named)
+    bucket = FlatBucket(ordered)
+    return bucket, [bucket.range_of([n for n in named if n.startswith(pre + ".")]) for pre in order]
+
+
 def make_ema(optimizer, ema_decay: Optional[float], ema_warmup: bool) -> Optional[EMA]:
     """The engines' ``ema_decay=`` switch: None builds nothing (no shadow buffer, no launch), a value in (0, 1) an ``optim.EMA``
     over every bucket ``optimizer`` steps, following its on-device skip decision."""
@@ -271,13 +308,7 @@ class SegEngine(nn.Module):
             frozen += list(cross_vit.parameters()) + list(cross_cnn.parameters())
         for p in frozen:
             p.requires_grad_(False)  # no gradient reaches them in the reference step
-        # gradient-ready order of the decoder backward: final conv first, decoder_1 last
-        order = list(seg_decoder.GRAD_ORDER)
-        named = dict(seg_decoder.named_parameters())
-        ordered = [(n, named[n]) for pre in order for n in named if n.startswith(pre + ".")]
-        assert len(ordered) == len(named)
-        self.bucket = FlatBucket(ordered)
-        self.stage_ranges = [self.bucket.range_of([n for n in named if n.startswith(pre + ".")]) for pre in order]
+        self.bucket, self.stage_ranges = make_decoder_bucket(seg_decoder)
         buckets = [self.bucket]
         self.adapter_bucket = None
         if mode == "train_adapters":
@@ -552,44 +583,111 @@ class SegEngine(nn.Module):
             x.record_stream(main)
         return torch.cat(xs, 0)
 
-    def _cavit(self, x2, c2, g, B, Lq, Lin):
+    def _cavit(self, x2, c2, g, B, Lq, Lin, save: bool = False):
+        """-> (CAViT output, its saved activations | None)"""
         cv = self.cross_vit
+        if save:
+            # CAViT keeps its query for the LayerNorm backward; the callers overwrite the rows ``x2`` views in place (the stage
+            # output, the next block's input), so the saved copy must be its own tensor
+            return cv.forward16_train(x2.clone(), c2, g, B, Lq, Lin)
         return cv.attn.forward16(cv._ln16("query_norm", x2), cv._ln16("feat_norm", c2), g["ref1"], g["shapes1"],
-                                 g["starts1"], B, Lq, Lin, res=x2, scale_n=cv._f32("gamma", cv.gamma))
+                                 g["starts1"], B, Lq, Lin, res=x2, scale_n=cv._f32("gamma", cv.gamma)), None
 
-    def _cacnn(self, c2, x2, g, B, Lq, Lin, grids):
+    def _cacnn(self, c2, x2, g, B, Lq, Lin, grids, save: bool = False):
+        """-> (CACNN output, its saved activations | None)"""
         cn = self.cross_cnn
+        if save:
+            return cn.forward16_train(c2, x2, g, B, Lq, Lin, grids)
         out = cn.attn.forward16(cn._ln16("query_norm", c2), cn._ln16("feat_norm", x2), g["ref2"], g["shapes2"],
                                 g["starts2"], B, Lq, Lin, res=c2)
-        return cn.ffn.forward16(cn._ln16("ffn_norm", out), out, B, Lq, grids) if cn.with_cffn else out
+        return (cn.ffn.forward16(cn._ln16("ffn_norm", out), out, B, Lq, grids) if cn.with_cffn else out), None
+
+    # ---- the pieces the three forward walks (``features``, ``features_mla``, ``_features_e2e``) share -------------------------
+    def _begin(self, inp: torch.Tensor):
+        """This engine's precision policy into ``config`` -> (the batch as contiguous fp32, (B, H, W, D, h, w, N, number of blocks))."""
+        config.split_attn_out = self.split_attn_out
+        config.precise_level = self.precise_level
+        config.precise_parts = self.precise_parts
+        B, _, H, W = inp.shape
+        h, w = H // self.patch, W // self.patch
+        return inp.float().contiguous(), (B, H, W, self.model.embed_dim, h, w, h * w, len(self.model.blocks))
+
+    def _encode(self, inp: torch.Tensor, train: bool, side_stream: bool = False):
+        """The spatial-prior CNN and the sampling geometry of its level shapes -> (c tokens, shapes, geometry, event | None).
+        ``train``: a training forward, which keeps the activations of an encoder that trains (``_esaved``, for
+        ``_encoder_backward``); ``side_stream``: a frozen encoder may run beside the trunk (config.encoder_stream), and the
+        caller waits for the returned event before it reads ``c``."""
+        done = None
+        if train and self.train_encoder:
+            c, shapes, esaved = self.backbone_encoder.forward_tokens_train(inp)
+            self._esaved = (esaved, shapes)
+        elif side_stream and config.encoder_stream and inp.is_cuda:
+            c, shapes, done = self._encoder_on_side_stream(inp)
+        else:
+            _, c, shapes = self.backbone_encoder.forward_tokens(inp, need_c1=not config.elide_c1)
+        return c, shapes, self._geometry(inp.shape[-2], inp.shape[-1], shapes, inp.device), done
+
+    def _adapter_stage(self, xb, c2d, feat, g, shapes, dead: bool, save: bool):
+        """One adapter stage of the `train.py` flow behind its block: CAViT, CACNN unless ``dead``, and the residual add of pass
+        A's feature ``feat`` [B, N, D] into pass B's rows ``xb`` [B * N, D] of the stacked buffer, in place: the next block reads
+        the stage output there -> (stage output [B, N, D], c, (CAViT save, CACNN save | None) when ``save`` else None)."""
+        B, N, D = feat.shape
+        Lc = c2d.shape[0] // B
+        x2, s_cv = self._cavit(xb, c2d, g, B, N, Lc, save)
+        s_cn = None
+        if not dead:
+            c2d, s_cn = self._cacnn(c2d, x2, g, B, Lc, N, shapes, save)
+        x = ops.add_f32(x2.view(B, N, D), feat, out=xb.view(B, N, D))
+        return x, c2d, ((s_cv, s_cn) if save else None)
+
+    def _decoder_cat(self, x, c_orig, feats, c2d, shapes, hw, taps: Optional[dict], mx: bool = False):
+        """`train.py:389-406`: the last stage's output ``x`` [B, N, D] -> the head's input (hi, lo | None): the FeatureDecoder concat
+        [x | c4 of the ENCODER output, zero-padded | last pass-A feature] as NHWC [B, h, w, 3D], or ``x`` alone for the UNet head."""
+        B, N, D = x.shape
+        Lc = c_orig.shape[1]
+        if self.stream_only:
+            cat = _hi_lo(x.reshape(B * N, D), B, *hw, D)
+        else:
+            n4 = shapes[2][0] * shapes[2][1]
+            cat = ops.decoder_input(x, c_orig[:, Lc - n4:], feats[-1], hw, shapes[2], config.operand_dtype, config.split_conv, mx=mx)
+            if not config.split_conv:
+                cat = (cat, None)
+        if taps is not None:
+            taps.update(feats=feats, x_final=x, c_final=c2d.view(B, Lc, D), cat=cat[0])
+        return cat
+
+    def _slab_views(self, slabs: torch.Tensor, s: int) -> Dict[str, torch.Tensor]:
+        """CAViT / CACNN are the same modules in every stage, so every stage writes its own gradient slab (the slabs are summed in
+        a fixed order afterwards) -> name -> view of slab ``s``, shaped like the parameter"""
+        ab = self.adapter_bucket
+        return {n: slabs[s, o:o + p.numel()].view(p.shape) for n, p, o in zip(ab.names, ab.params, ab.offsets)}
+
+    def _adapter_stage_backward(self, s_cv, s_cn, dx, dc_next, gs, inv: float):
+        """Backward of ``_adapter_stage``.  ``dx`` [B, N, D]: gradient of the stage's stream output (the residual add is the
+        identity, ``dx`` is not written); ``dc_next``: what the stage behind sent back for c, None for the last stage, whose CACNN
+        fed nothing.  CACNN, which sends its share of the stream gradient too, then CAViT -> (gradient of the block output in
+        front of the stage [B * N, D], gradient of the stage's c input [B * Lc, D])."""
+        B, _, D = dx.shape
+        dc_in = None
+        if dc_next is not None:
+            dc_in, dx_extra = self.cross_cnn.backward16(s_cn, dc_next, inv, gs, "cross_cnn")
+            dx = ops.add_f32(dx, dx_extra.view_as(dx))
+        dx_in, dc = self.cross_vit.backward16(s_cv, dx.view(-1, D), inv, gs, "cross_vit")
+        if dc_in is not None:
+            dc3 = dc.view(B, -1, D)
+            ops.add_f32(dc3, dc_in.view_as(dc3), out=dc3)
+        return dx_in, dc
 
     @torch.no_grad()
     def features(self, inp: torch.Tensor, taps: Optional[dict] = None, adapter_saves: Optional[list] = None):
         """`train.py:275-406`: image batch -> decoder input, NHWC 16-bit [B, h, w, 3D] as (hi, lo|None).
         ``adapter_saves`` (train_adapters mode): list that receives, per stage, the saved activations of the frozen
         block on pass B and of CAViT / CACNN."""
-        config.split_attn_out = self.split_attn_out
-        config.precise_level = self.precise_level
-        config.precise_parts = self.precise_parts
-        m = self.model
-        B, _, H, W = inp.shape
-        inp = inp.float().contiguous()
-        D = m.embed_dim
-        h, w = H // self.patch, W // self.patch
-        N = h * w
-        nb = len(m.blocks)
-        nl = self.n_last_blocks
-        enc_done = None
-        if self.train_encoder and adapter_saves is not None:
-            c, shapes, esaved = self.backbone_encoder.forward_tokens_train(inp)
-            self._esaved = (esaved, shapes)
-        elif config.encoder_stream and inp.is_cuda:
-            c, shapes, enc_done = self._encoder_on_side_stream(inp)
-        else:
-            _, c, shapes = self.backbone_encoder.forward_tokens(inp, need_c1=not config.elide_c1)
-        c_orig = c
+        inp, (B, H, W, D, h, w, N, nb) = self._begin(inp)
+        m, nl = self.model, self.n_last_blocks
+        train = self.mode == "train_adapters" and adapter_saves is not None
+        c, shapes, g, enc_done = self._encode(inp, train, side_stream=True)
         Lc = c.shape[1]
-        g = self._geometry(H, W, shapes, inp.device)
         # ---- pass A (train.py:287): cls + pos-embed, all blocks, final norm on the last n outputs ----
         # ---- both passes stacked along the rows: every block evaluation of pass A (cls + pos-embed tokens, all
         # blocks, `train.py:287`) has a pass-B partner on the same frozen weights (raw patch tokens through
@@ -621,7 +719,6 @@ class SegEngine(nn.Module):
         if taps is not None:
             taps.update(c=c, x_b0=xcat[Ra:].view(B, N, D).clone(), shapes=shapes)
         c2d = c.view(B * Lc, D)
-        train = self.mode == "train_adapters" and adapter_saves is not None
         for s in range(nl):
             bsaved = None
             if s > 0:
@@ -636,40 +733,14 @@ class SegEngine(nn.Module):
             # the last stage's CACNN output (`train.py:372-386`) feeds nothing: the decoder input takes c4 from the
             # ENCODER output (`:395`), so unless a caller asks for the taps it is dead code and skipped (same results)
             dead = s == nl - 1 and taps is None and config.elide_dead_cacnn
+            x, c2d, saves = self._adapter_stage(xcat[Ra:], c2d, feats[s], g, shapes, dead, train)
             if train:
-                # CAViT keeps its query for the LayerNorm backward; the stage output below overwrites these rows of the
-                # stacked buffer in place, so the saved copy must be its own tensor
-                x2, s_cv = self.cross_vit.forward16_train(xcat[Ra:].clone(), c2d, g, B, N, Lc)
-                s_cn = None
-                if not dead:
-                    c2d, s_cn = self.cross_cnn.forward16_train(c2d, x2, g, B, Lc, N, shapes)
-                adapter_saves.append((bsaved, s_cv, s_cn))
-            else:
-                x2 = self._cavit(xcat[Ra:], c2d, g, B, N, Lc)
-                if not dead:
-                    c2d = self._cacnn(c2d, x2, g, B, Lc, N, shapes)
-            # the stage output overwrites pass B's rows of the stacked buffer: the next block reads it in place
-            x = ops.add_f32(x2.view(B, N, D), feats[s], out=xcat[Ra:].view(B, N, D))
-        if taps is not None:
-            taps.update(feats=feats)
-        if self.stream_only:
-            xs = x.reshape(B * N, D)
-            hi = ops.cast_pad(xs, D, config.operand_dtype).view(B, h, w, D)
-            lo = ops.cast_pad(xs, D, config.operand_dtype, part=1).view(B, h, w, D) if config.split_conv else None
-            if taps is not None:
-                taps.update(x_final=x, c_final=c2d.view(B, Lc, D), cat=hi)
-            return hi, lo
-        n4 = shapes[2][0] * shapes[2][1]
+                adapter_saves.append((bsaved, *saves))
         d1 = getattr(self.seg_decoder, "decoder_1", None)     # FeatureDecoder: its first conv takes MX lo operands (config.mx_conv)
         mx = bool(config.mx_conv_on() and config.split_conv and d1 is not None and "d1" not in config.unsplit_layers and
                   ops.mx_conv_ok(B * h * w, 3 * D, d1[0].out_channels))
-        cat = ops.decoder_input(x, c_orig[:, Lc - n4:], feats[-1], (h, w), shapes[2], config.operand_dtype,
-                                config.split_conv, mx=mx)
-        if not config.split_conv:
-            cat = (cat, None)
-        if taps is not None:
-            taps.update(x_final=x, c_final=c2d.view(B, Lc, D), cat=cat[0])
-        return cat
+        # the one difference to the tail of ``_features_e2e``, which never asks for the MX form: kept as it is
+        return self._decoder_cat(x, c, feats, c2d, shapes, (h, w), taps, mx=mx)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -678,24 +749,11 @@ class SegEngine(nn.Module):
         (output_last, output_last_2, output_last_3, output_last_4), each NHWC 16-bit [B, h, w, D].
         ``adapter_saves`` (train_adapters): receives, per adapter use, (saved activations of the frozen block in front of it on
         pass B | None, CAViT save, CACNN save | None) — stage 0 is CAViT alone, stages 1..3 are block -> CACNN -> CAViT."""
-        config.split_attn_out = self.split_attn_out
-        config.precise_level = self.precise_level
-        config.precise_parts = self.precise_parts
+        inp, (B, H, W, D, h, w, N, nb) = self._begin(inp)
         m = self.model
-        B, _, H, W = inp.shape
-        inp = inp.float().contiguous()
-        D = m.embed_dim
-        h, w = H // self.patch, W // self.patch
-        N = h * w
-        nb = len(m.blocks)
         train = self.mode == "train_adapters" and adapter_saves is not None
-        if train and self.train_encoder:
-            c, shapes, esaved = self.backbone_encoder.forward_tokens_train(inp)
-            self._esaved = (esaved, shapes)
-        else:
-            _, c, shapes = self.backbone_encoder.forward_tokens(inp, need_c1=not config.elide_c1)
+        c, shapes, g, _ = self._encode(inp, train)
         Lc = c.shape[1]
-        g = self._geometry(H, W, shapes, inp.device)
         tokens = m.patch_embed(inp)
         if not config.share_patch_embed:   # pass A's own evaluation in the reference (same values)
             m.patch_embed(inp)
@@ -708,11 +766,9 @@ class SegEngine(nn.Module):
         xcat = torch.cat([xa.view(Ra, D), tokens.reshape(B * N, D)], 0)
         xcat = run_blocks(list(m.blocks[: nb - 3]), xcat, segs)
         c2d = c.view(B * Lc, D)
+        x2, s_cv = self._cavit(xcat[Ra:], c2d, g, B, N, Lc, train)
         if train:
-            x2, s_cv = self.cross_vit.forward16_train(xcat[Ra:].clone(), c2d, g, B, N, Lc)
             adapter_saves.append((None, s_cv, None))
-        else:
-            x2 = self._cavit(xcat[Ra:], c2d, g, B, N, Lc)
         outs = [x2]
         for j, bi in enumerate((nb - 3, nb - 2, nb - 2)):  # the reference's repeated [-2:-1]
             bsaved = None
@@ -731,27 +787,18 @@ class SegEngine(nn.Module):
                 x2 = xcat[Ra:]
             else:
                 x2 = m.blocks[bi](x2.view(B, N, D)).view(B * N, D)
+            c2d, s_cn = self._cacnn(c2d, x2, g, B, Lc, N, shapes, train)
+            x2, s_cv = self._cavit(x2, c2d, g, B, N, Lc, train)
             if train:
-                c2d, s_cn = self.cross_cnn.forward16_train(c2d, x2.contiguous(), g, B, Lc, N, shapes)
-                x2, s_cv = self.cross_vit.forward16_train(x2.clone(), c2d, g, B, N, Lc)
                 adapter_saves.append((bsaved, s_cv, s_cn))
-            else:
-                c2d = self._cacnn(c2d, x2, g, B, Lc, N, shapes)
-                x2 = self._cavit(x2, c2d, g, B, N, Lc)
             outs.append(x2)
         xa = m.blocks[nb - 1](xcat[:Ra].view(B, N + 1, D))
         vit_last = m._final_norm(xa)[:, 1:]
         last = ops.add_f32(outs[3].view(B, N, D), vit_last)
         maps = [last.view(B * N, D), outs[2], outs[1], outs[0]]
-        dt = config.operand_dtype
-        res = []
-        for t in maps:
-            hi = ops.cast_pad(t, D, dt).view(B, h, w, D)
-            lo = ops.cast_pad(t, D, dt, part=1).view(B, h, w, D) if config.split_conv else None
-            res.append((hi, lo))
         if taps is not None:
             taps.update(mla_inputs=[t.view(B, N, D) for t in maps])
-        return res
+        return [_hi_lo(t, B, h, w, D) for t in maps]
 
     @torch.no_grad()
     def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None,
@@ -770,82 +817,51 @@ class SegEngine(nn.Module):
         if self.mix_sampler is not None:   # after the teacher, which sees the batch as it came
             inp, target, mixed = self._mix(inp, target, taps)
         dec = self.seg_decoder
-        S = config.loss_scale
-        asaves = None
+        adapters = self.mode == "train_adapters"     # the head's input is trainable upstream: its gradient is needed
+        asaves = [] if adapters else None            # what the two walks on the frozen backbone keep for the adapter backward
         if self.is_mla:
-            asaves = [] if self.mode == "train_adapters" else None
-            logits, saved = dec._forward_core(self.features_mla(inp, taps, asaves), save=True, training=True)
+            dec_in = (self.features_mla(inp, taps, asaves),)
         elif self.train_backbone:
-            cat, e2e = self._features_e2e(inp, taps)
-            if self.stream_only:
-                logits, saved = dec._forward_core(cat[0], cat[1], save=True, training=True, need_input_grad=True)
-            else:
-                logits, saved = dec._forward_core(cat[0], cat[1], save=True, training=True)
+            dec_in, e2e = self._features_e2e(inp, taps)
         else:
-            asaves = [] if self.mode == "train_adapters" else None
-            cat = self.features(inp, taps, asaves)
-            if self.stream_only and asaves is not None:
-                logits, saved = dec._forward_core(cat[0], cat[1], save=True, training=True, need_input_grad=True)
-            else:
-                logits, saved = dec._forward_core(cat[0], cat[1], save=True, training=True)
-        target = target.long().contiguous()
-        loss, dz = loss_and_dz(self, logits, target, S)
+            dec_in = self.features(inp, taps, asaves)
+        # the UNet head alone takes the flag in its forward too: it keeps the arg-max of its first MaxPool for that gradient
+        fwd_kw = {"need_input_grad": True} if (self.stream_only and adapters) else {}
+        logits, saved = dec._forward_core(*dec_in, save=True, training=True, **fwd_kw)
+        loss, dz, target = loss_head(self, logits, target)
         if self.teacher is not None:
-            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, S, taps, mixed)
-        B, hh, ww, C = logits.shape
-        r = ops.resize_bilinear_bwd(dz, hh, ww, config.operand_dtype, config.split_conv)
-        d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])
-        world = world_size(self.process_group)
-        inv = 1.0 / (S * world)  # gradient mean over ranks folded into the un-scaling (DDP semantics)
-        self.reducer.begin()
-        if self.mode == "train_adapters" and self.is_mla:
-            dmaps = dec._backward_core(saved, d16, bpart, inv, self.bucket.views, stage_done=self.reducer.stage_done, d_lo=d_lo,
-                                       need_input_grad=True)
-            self.adapter_reducer.begin()
-            dc0 = self._mla_adapter_backward(asaves, dmaps, inv)
+            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, config.loss_scale, taps, mixed)
+        d16, d_lo, bpart, inv = logit_gradient(self, dz, logits)
+        # every reducer this step fires, in the order they are finished below (``begin`` only resets host counters)
+        reducers = []
+        if self.train_backbone:
+            reducers.append(self.vit_reducer)
+        if self.train_encoder:
+            reducers.append(self.encoder_reducer)
+        if adapters:
+            reducers.append(self.adapter_reducer)
+        reducers.append(self.reducer)
+        for r in reducers:
+            r.begin()
+        dgrad = dec._backward_core(saved, d16, bpart, inv, self.bucket.views, stage_done=self.reducer.stage_done, d_lo=d_lo,
+                                   need_input_grad=adapters)
+        if self.stream_only and (self.train_backbone or self.train_encoder):
+            # UNet head: the decoder input is the adapter stream alone; the encoder / backbone backward walks take the
+            # FeatureDecoder layout [stream | c4 (padded) | pass-A feature], whose other two gradient slices are zero here
+            Bq, hq, wq, Dq = dgrad.shape
+            full = ops.zeros((Bq, hq, wq, 3 * Dq), dgrad.device, dgrad.dtype)
+            ops.copy_channels(dgrad.view(-1, Dq), full.view(-1, 3 * Dq)[:, :Dq])
+            dgrad = full
+        if self.train_backbone:     # fires the adapter, encoder and backbone exchanges itself, from inside the walk
+            self._e2e_backward(e2e, dgrad, inv)
+        elif adapters:
+            dc0 = self._mla_adapter_backward(asaves, dgrad, inv) if self.is_mla else self._adapter_backward(asaves, dgrad, inv)
             self.adapter_reducer.stage_done()
-            if self.train_encoder:
-                self.encoder_reducer.begin()
-                self._encoder_backward(dc0, None, inv)
+            if self.train_encoder:   # on the train_mla.py flow c reaches the head through the adapters only: no c4 slice to add
+                self._encoder_backward(dc0, None if self.is_mla else dgrad, inv)
                 self.encoder_reducer.stage_done()
-                self.encoder_reducer.finish()
-            self.adapter_reducer.finish()
-        elif self.mode == "train_adapters":
-            dcat = dec._backward_core(saved, d16, bpart, inv, self.bucket.views, stage_done=self.reducer.stage_done, d_lo=d_lo,
-                                      need_input_grad=True)
-            if self.stream_only and (self.train_backbone or self.train_encoder):
-                # UNet head: the decoder input is the adapter stream alone; the encoder / backbone backward walks take the
-                # FeatureDecoder layout [stream | c4 (padded) | pass-A feature], whose other two gradient slices are zero here
-                Bq, hq, wq, Dq = dcat.shape
-                full = ops.zeros((Bq, hq, wq, 3 * Dq), dcat.device, dcat.dtype)
-                ops.copy_channels(dcat.view(-1, Dq), full.view(-1, 3 * Dq)[:, :Dq])
-                dcat = full
-            self.adapter_reducer.begin()
-            if self.train_backbone:
-                self.vit_reducer.begin()
-                if self.train_encoder:
-                    self.encoder_reducer.begin()
-                self._e2e_backward(e2e, dcat, inv)
-                self.vit_reducer.finish()
-                if self.train_encoder:
-                    self.encoder_reducer.finish()
-                self.adapter_reducer.finish()
-                self.reducer.finish()
-                _optimizer_step(self)
-                if taps is not None:
-                    taps.update(logits=logits, loss=loss)
-                return loss.view(())
-            dc0 = self._adapter_backward(asaves, dcat, inv)
-            self.adapter_reducer.stage_done()
-            if self.train_encoder:
-                self.encoder_reducer.begin()
-                self._encoder_backward(dc0, dcat, inv)
-                self.encoder_reducer.stage_done()
-                self.encoder_reducer.finish()
-            self.adapter_reducer.finish()
-        else:
-            dec._backward_core(saved, d16, bpart, inv, self.bucket.views, stage_done=self.reducer.stage_done, d_lo=d_lo)
-        self.reducer.finish()
+        for r in reducers:
+            r.finish()
         _optimizer_step(self)
         if taps is not None:
             taps.update(logits=logits, loss=loss)
@@ -858,24 +874,9 @@ class SegEngine(nn.Module):
         ``Block.forward_train_rows`` (so each block's weight gradients are later taken over the rows of both passes in
         one GEMM), the final norm's inputs of the last ``n_last_blocks`` outputs, CAViT / CACNN activations, the encoder's
         when it trains.  -> ((cat_hi, cat_lo|None), saved)."""
-        config.split_attn_out = self.split_attn_out
-        config.precise_level = self.precise_level
-        config.precise_parts = self.precise_parts
-        m = self.model
-        B, _, H, W = inp.shape
-        inp = inp.float().contiguous()
-        D = m.embed_dim
-        h, w = H // self.patch, W // self.patch
-        N = h * w
-        nb, nl = len(m.blocks), self.n_last_blocks
-        if self.train_encoder:
-            c, shapes, esaved = self.backbone_encoder.forward_tokens_train(inp)
-            self._esaved = (esaved, shapes)
-        else:
-            _, c, shapes = self.backbone_encoder.forward_tokens(inp, need_c1=not config.elide_c1)
-        c_orig = c
-        Lc = c.shape[1]
-        g = self._geometry(H, W, shapes, inp.device)
+        inp, (B, H, W, D, h, w, N, nb) = self._begin(inp)
+        m, nl = self.model, self.n_last_blocks
+        c, shapes, g, _ = self._encode(inp, train=True)
         tokens, a16 = m.patch_tokens_train(inp)           # shared by both passes: its gradient is the sum of both
         xa = ops.add_cls_pos(tokens, m.cls_token.detach().reshape(-1).float().contiguous(),
                              m._pos_for(N, H, W).detach().reshape(-1, D).float().contiguous())
@@ -895,7 +896,7 @@ class SegEngine(nn.Module):
                 fin.append(xcat)                           # rows [:Ra] = input of that final norm (never overwritten)
         if taps is not None:
             taps.update(c=c, x_b0=xcat[Ra:].view(B, N, D).clone(), shapes=shapes)
-        c2d = c.view(B * Lc, D)
+        c2d = c.view(-1, D)
         for s in range(nl):
             if s > 0:
                 xcat, sv = blk_train(nb - nl + s, xcat)
@@ -903,27 +904,10 @@ class SegEngine(nn.Module):
                 feats.append(m._final_norm(xcat[:Ra].view(B, N + 1, D))[:, 1:])
                 fin.append(xcat)
             dead = s == nl - 1 and taps is None and config.elide_dead_cacnn   # see ``features``: the last CACNN output feeds nothing
-            x2, s_cv = self.cross_vit.forward16_train(xcat[Ra:].clone(), c2d, g, B, N, Lc)
-            s_cn = None
-            if not dead:
-                c2d, s_cn = self.cross_cnn.forward16_train(c2d, x2, g, B, Lc, N, shapes)
-            asaves.append((s_cv, s_cn))
-            x = ops.add_f32(x2.view(B, N, D), feats[s], out=xcat[Ra:].view(B, N, D))
-        if taps is not None:
-            taps.update(feats=feats)
-        if self.stream_only:     # UNet head (BASELINE config 2 with everything trainable): the adapter stream alone
-            xs = x.reshape(B * N, D)
-            hi = ops.cast_pad(xs, D, config.operand_dtype).view(B, h, w, D)
-            lo = ops.cast_pad(xs, D, config.operand_dtype, part=1).view(B, h, w, D) if config.split_conv else None
-            if taps is not None:
-                taps.update(x_final=x, c_final=c2d.view(B, Lc, D), cat=hi)
-            return (hi, lo), (a16, bsaves, fin, asaves, (B, N, H, W))
-        n4 = shapes[2][0] * shapes[2][1]
-        cat = ops.decoder_input(x, c_orig[:, Lc - n4:], feats[-1], (h, w), shapes[2], config.operand_dtype, config.split_conv)
-        if not config.split_conv:
-            cat = (cat, None)
-        if taps is not None:
-            taps.update(x_final=x, c_final=c2d.view(B, Lc, D), cat=cat[0])
+            x, c2d, saves = self._adapter_stage(xcat[Ra:], c2d, feats[s], g, shapes, dead, save=True)
+            asaves.append(saves)
+        # unlike ``features`` this walk does not ask for the MX form of the FeatureDecoder's lo operand: kept as it is
+        cat = self._decoder_cat(x, c, feats, c2d, shapes, (h, w), taps)
         return cat, (a16, bsaves, fin, asaves, (B, N, H, W))
 
     def _block_done(self, i: int) -> None:
@@ -938,8 +922,8 @@ class SegEngine(nn.Module):
         later stage) and CAViT run their backward; then the block in front of the stage takes G for both passes at once.
         ``model.norm``, CAViT and CACNN are used once per stage: per-stage gradient slabs summed in a fixed order."""
         a16, bsaves, fin, asaves, (B, N, H, W) = saved
-        m, cv, cn = self.model, self.cross_vit, self.cross_cnn
-        _, h, w, D3 = dcat.shape
+        m = self.model
+        D3 = dcat.shape[-1]
         D = D3 // 3
         nb, nl = len(m.blocks), self.n_last_blocks
         Ra, Rb = B * (N + 1), B * N
@@ -956,8 +940,6 @@ class SegEngine(nn.Module):
         ops.copy_channels(dcat2[:, 2 * D:], dvit)
         dc_next = None
         for s in range(nl - 1, -1, -1):
-            s_cv, s_cn = asaves[s]
-            gs = {n: slabs[s, o:o + p.numel()].view(p.shape) for n, p, o in zip(ab.names, ab.params, ab.offsets)}
             # d f_s: the stage's residual add, + the decoder input's third slice for the last feature
             dyA = ops.zeros((B, N + 1, D), dev)
             ops.copy_channels(G[Ra:].view(B, N * D), dyA.view(B, (N + 1) * D)[:, D:])
@@ -967,16 +949,8 @@ class SegEngine(nn.Module):
             _, part = ops.layernorm_bwd(dyA.view(Ra, D), fin[s][:Ra], nw, m.norm.eps, res=G[:Ra], out=Gn[:Ra])
             if not lora:
                 ops.reduce_rows(part.view(part.shape[0], 2 * D), inv, nslab[s])
-            dx = G[Ra:]
-            dc_in = None
-            if dc_next is not None:
-                dc_in, dx_extra = cn.backward16(s_cn, dc_next, inv, gs, "cross_cnn")
-                dx = ops.add_f32(dx.view(B, N, D), dx_extra.view(B, N, D)).view(Rb, D)
-            dx_in, dc_cv = cv.backward16(s_cv, dx, inv, gs, "cross_vit")
-            if dc_in is not None:
-                Lc = dc_cv.shape[0] // B
-                ops.add_f32(dc_cv.view(B, Lc, D), dc_in.view(B, Lc, D), out=dc_cv.view(B, Lc, D))
-            dc_next = dc_cv
+            gs = self._slab_views(slabs, s)
+            dx_in, dc_next = self._adapter_stage_backward(*asaves[s], G[Ra:].view(B, N, D), dc_next, gs, inv)
             ops.copy_channels(dx_in, Gn[Ra:])
             if s == 0:   # every use of model.norm / CAViT / CACNN has contributed: finish their gradients, start the exchanges
                 if not lora:
@@ -1000,16 +974,15 @@ class SegEngine(nn.Module):
             m.embed_backward(a16, G[:Ra].view(B, N + 1, D), G[Ra:], H, W, inv, vg)
         self._block_done(-1)
 
-    def _adapter_backward(self, asaves, dcat: torch.Tensor, inv: float) -> None:
+    def _adapter_backward(self, asaves, dcat: torch.Tensor, inv: float) -> torch.Tensor:
         """(``dcat`` [B, h, w, 3D] = gradient of the FeatureDecoder input concat, or [B, h, w, D] = gradient of the
         adapter-stream map alone for the UNet head.)
         Backward of the four adapter stages (`train.py:304-387` under autograd, minus its no_grad):
         d cat[..., :D] is the gradient of the adapter stream; the c4 and pass-A slices of the decoder input come from
         the frozen encoder / backbone.  Per stage, in reverse: x = x2 + feat (identity), CACNN (only when its output
         fed a later stage: the last one is dead code in the reference flow), CAViT, and the input gradient of the
-        frozen ViT block in front of the stage.  CAViT / CACNN are the same modules in all four stages, so every
-        stage writes its own gradient slab and the slabs are summed in a fixed order."""
-        m, cv, cn = self.model, self.cross_vit, self.cross_cnn
+        frozen ViT block in front of the stage (``_slab_views``: one gradient slab per stage)."""
+        m = self.model
         B, h, w, D3 = dcat.shape
         D = m.embed_dim
         N = h * w
@@ -1022,16 +995,7 @@ class SegEngine(nn.Module):
         dc_next = None
         for s in range(nl - 1, -1, -1):
             bsaved, s_cv, s_cn = asaves[s]
-            gs = {n: slabs[s, o:o + p.numel()].view(p.shape) for n, p, o in zip(ab.names, ab.params, ab.offsets)}
-            dc_in = None
-            if dc_next is not None:
-                dc_in, dx_extra = cn.backward16(s_cn, dc_next, inv, gs, "cross_cnn")
-                ops.add_f32(dx.view(B, N, D), dx_extra.view(B, N, D), out=dx.view(B, N, D))
-            dx_in, dc_cv = cv.backward16(s_cv, dx, inv, gs, "cross_vit")
-            if dc_in is not None:
-                Lc = dc_cv.shape[0] // B
-                ops.add_f32(dc_cv.view(B, Lc, D), dc_in.view(B, Lc, D), out=dc_cv.view(B, Lc, D))
-            dc_next = dc_cv
+            dx_in, dc_next = self._adapter_stage_backward(s_cv, s_cn, dx.view(B, N, D), dc_next, self._slab_views(slabs, s), inv)
             if s > 0:
                 dx = m.blocks[nb - (nl - 1) + s - 1].backward(bsaved, dx_in, inv, None)
         ops.reduce_rows(slabs, 1.0, ab.grad)
@@ -1053,7 +1017,7 @@ class SegEngine(nn.Module):
         dc_from_next = None                                        # gradient of c_j through CACNN_{j+1}'s query input
         for j in (3, 2, 1):
             bsaved, s_cv, s_cn = asaves[j]
-            gs = {n: slabs[j, o:o + p.numel()].view(p.shape) for n, p, o in zip(ab.names, ab.params, ab.offsets)}
+            gs = self._slab_views(slabs, j)
             dx_q, dc_j = cv.backward16(s_cv, dx, inv, gs, "cross_vit")          # query (block output) and feat (c_j)
             if dc_from_next is not None:
                 Lc = dc_j.shape[0] // B
@@ -1063,9 +1027,7 @@ class SegEngine(nn.Module):
             bi = (nb - 3, nb - 2, nb - 2)[j - 1]
             dx_prev = m.blocks[bi].backward(bsaved, dxb, inv, None)
             dx = ops.add_f32(dx_prev.view(B, N, D), d_out[j - 1].reshape(B, N, D)).view(B * N, D)
-        _, s_cv, _ = asaves[0]
-        gs = {n: slabs[0, o:o + p.numel()].view(p.shape) for n, p, o in zip(ab.names, ab.params, ab.offsets)}
-        _, dc0 = cv.backward16(s_cv, dx, inv, gs, "cross_vit")
+        _, dc0 = cv.backward16(asaves[0][1], dx, inv, self._slab_views(slabs, 0), "cross_vit")
         Lc = dc0.shape[0] // B
         ops.add_f32(dc0.view(B, Lc, D), dc_from_next.view(B, Lc, D), out=dc0.view(B, Lc, D))
         ops.reduce_rows(slabs, 1.0, ab.grad)
@@ -1257,12 +1219,7 @@ class EndToEndEngine(nn.Module):
         self.patch = model.patch_size
         for p in model.parameters():
             p.requires_grad_(True)
-        order = list(seg_decoder.GRAD_ORDER)
-        named = dict(seg_decoder.named_parameters())
-        ordered = [(n, named[n]) for pre in order for n in named if n.startswith(pre + ".")]
-        assert len(ordered) == len(named)
-        self.bucket = FlatBucket(ordered)
-        self.stage_ranges = [self.bucket.range_of([n for n in named if n.startswith(pre + ".")]) for pre in order]
+        self.bucket, self.stage_ranges = make_decoder_bucket(seg_decoder)
         self.optimizer = make_optimizer(optimizer, [self.bucket], lr=lr, momentum=momentum, weight_decay=weight_decay, betas=betas,
                                         eps=eps, clip_grad=clip_grad, no_decay=no_decay)
         self.ema = make_ema(self.optimizer, ema_decay, ema_warmup)
@@ -1281,8 +1238,6 @@ class EndToEndEngine(nn.Module):
     def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         _check_trainable(self)
         m, dec = self.model, self.seg_decoder
-        S = config.loss_scale
-        dt = config.operand_dtype
         B, _, H, W = inp.shape
         h, w = H // self.patch, W // self.patch
         N, D = h * w, m.embed_dim
@@ -1292,15 +1247,9 @@ class EndToEndEngine(nn.Module):
             tok, vsaved = m.forward_train(inp)
         t2 = torch.empty((B * N, D), device=inp.device, dtype=torch.float32)
         ops.copy_channels(vsaved_tokens_view(tok, B, N, D), t2.view(B, N * D))
-        hi = ops.cast_pad(t2, D, dt).view(B, h, w, D)
-        lo = ops.cast_pad(t2, D, dt, part=1).view(B, h, w, D) if config.split_conv else None
-        logits, saved = dec._forward_core(hi, lo, save=True, training=True)
-        target = target.long().contiguous()
-        loss, dz = loss_and_dz(self, logits, target, S)
-        _, hh, ww, C = logits.shape
-        r = ops.resize_bilinear_bwd(dz, hh, ww, dt, config.split_conv)
-        d16, d_lo, bpart = r if config.split_conv else (r[0], None, r[1])
-        inv = 1.0 / (S * world_size(self.process_group))
+        logits, saved = dec._forward_core(*_hi_lo(t2, B, h, w, D), save=True, training=True)
+        loss, dz, _ = loss_head(self, logits, target)
+        d16, d_lo, bpart, inv = logit_gradient(self, dz, logits)
         self.reducer.begin()
         self.vit_reducer.begin()
         dX = dec._backward_core(saved, d16, bpart, inv, self.bucket.views, stage_done=self.reducer.stage_done, d_lo=d_lo,
