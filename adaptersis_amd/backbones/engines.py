@@ -76,8 +76,16 @@ def _loss_scratch(engine, attr: str, need: int, device) -> torch.Tensor:
 def loss_and_dz(engine, logits: torch.Tensor, target: torch.Tensor, S: float):
     """The loss stage of every engine's ``train_step``: logits fp32 NHWC [B,h,w,C], target int64 [B,H,W] ->
     (loss [1], dz fp32 [B,H,W,C] = S * d loss / d resized logits) for ``engine.loss_kind``, a key of ``SegEngine.LOSSES``.
-    No host sync.  The Lovasz and the hard-pixel losses keep their scratch on the engine between steps."""
+    No host sync.  The Lovasz and the hard-pixel losses keep their scratch on the engine between steps.  Where the engine's step
+    has an ignore value (``SegEngine(ignore_index=)`` or an unlabelled sample: ``engine._hard_ignore``) the fused family goes
+    through ``ops.seg_loss_ignore`` and the valid pixels per sample are left in ``engine.last_hard_valid``."""
     n_region, lmode, eps, n_ce = SegEngine.LOSSES[engine.loss_kind]
+    g = getattr(engine, "_hard_ignore", None)
+    if g is not None:
+        if lmode in (ops.LOSS_LOVASZ, ops.LOSS_TOPK, ops.LOSS_FOCAL):
+            raise ValueError(f"loss {engine.loss_kind!r} has no ignore label: {SegEngine.IGNORE_LOSSES} have one")
+        loss, dz, engine.last_hard_valid, _ = ops.seg_loss_ignore(logits, target, g, n_region, lmode, eps, n_ce, None, S)
+        return loss, dz
     if lmode not in (ops.LOSS_LOVASZ, ops.LOSS_TOPK, ops.LOSS_FOCAL):
         loss, coef, _ = ops.seg_loss_fwd(logits, target, n_region, lmode, eps, n_ce, None, S)
         return loss, ops.seg_loss_bwd(logits, target, coef, n_region, lmode, n_ce, None)
@@ -208,6 +216,9 @@ class SegEngine(nn.Module):
         "dc_and_topk": (1, ops.LOSS_TOPK, 1.0, 0),
         "focal": (1, ops.LOSS_FOCAL, 0.0, 0),
     }
+    # the losses of asis_seg_loss_fwd: the ones that have an ignore label (asis_semi_loss), so the ones a batch with unlabelled
+    # frames can train with
+    IGNORE_LOSSES = ("dice", "iou", "softdice", "dc_and_ce", "tversky", "ce_dc")
 
     def __init__(self, model, backbone_encoder, cross_vit: CAViT, cross_cnn: CACNN, seg_decoder, *,
                  n_last_blocks: int = 4, num_classes: int = 2, lr: float = 0.01, momentum: float = 0.99,
@@ -220,7 +231,7 @@ class SegEngine(nn.Module):
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, teacher=None, distill_weight: float = 1.0,
                  distill_temperature: float = 1.0, distill_threshold: Optional[float] = None, distill_rampup: int = 0,
                  distill_flip: bool = False, mix: Optional[str] = None, mix_p: float = 1.0, mix_seed: int = 0,
-                 mix_background: bool = False):
+                 mix_background: bool = False, ignore_index: Optional[int] = None, distill_labelled_weight: float = 1.0):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -275,7 +286,16 @@ class SegEngine(nn.Module):
         draw mixes a sample, the student's forward and the hard loss see ``ops.mix_batch`` of the batch.  A teacher still sees the
         unmixed batch; the consistency term reads its maps through the same mixing (``ops.consistency_loss(mix=)``).  A step
         whose draw mixes no sample is the unmixed step.  ``last_mix_pasted``: int32 [B] on the device, the pasted pixels per
-        sample of the last step (None where nothing was mixed)."""
+        sample of the last step (None where nothing was mixed).
+
+        ``ignore_index`` (an int outside 0..num_classes-1; default None: the step launches what it launches without the keyword and
+        libasis_semi.so is never opened): pixels with that label take no part in the hard loss (``ops.seg_loss_ignore``; a loss
+        of ``IGNORE_LOSSES``), ``last_hard_valid`` holds the valid pixels per sample of the last step.  ``train_step(labelled=)``
+        marks whole samples as unlabelled (it needs a ``teacher``): their target rows are filled with the ignore value (255
+        where ``ignore_index`` is None) on the device, the hard loss leaves them out, and the consistency term weighs them 1 and
+        the labelled samples ``distill_labelled_weight`` (0: a labelled sample reads none of its teacher maps).  With ``mix`` the
+        donors are drawn inside the two groups, and ClassMix takes the classes of an unlabelled donor from the teacher's
+        prediction (``ops.predict_mask_views`` of its maps)."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -286,6 +306,15 @@ class SegEngine(nn.Module):
         if loss not in self.LOSSES:
             raise ValueError(f"loss must be one of {sorted(self.LOSSES)}")
         self.loss_kind = loss
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or 0 <= ignore_index < num_classes:
+                raise ValueError(f"ignore_index={ignore_index!r} must be an int outside the classes 0..{num_classes - 1}")
+            if loss not in self.IGNORE_LOSSES:
+                raise ValueError(f"loss {loss!r} has no ignore label: ignore_index needs one of {self.IGNORE_LOSSES}")
+        if not float(distill_labelled_weight) >= 0.0 or float(distill_labelled_weight) == float("inf"):
+            raise ValueError("distill_labelled_weight must be finite and >= 0")
+        self.ignore_index, self.distill_labelled_weight = ignore_index, float(distill_labelled_weight)
+        self._hard_ignore, self.last_hard_valid, self._semi_cache = ignore_index, None, {}
         if not 0.0 < topk_percent <= 100.0:
             raise ValueError("topk_percent must be in (0, 100]")
         if focal_gamma < 0.0:
@@ -431,22 +460,48 @@ class SegEngine(nn.Module):
         with self.ema_weights():
             return self._guarded_logits(views), flips
 
-    def _mix(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict]):
+    def _semi_tables(self, lab, dev):
+        """the device tables of a ``labelled`` pattern, cached per pattern and uploaded without blocking: the unlabelled samples
+        (int64 indices) and the consistency term's fp32 [B] weights (1 unlabelled, ``distill_labelled_weight`` labelled)"""
+        key = (lab, self.distill_labelled_weight, str(dev))
+        if key not in self._semi_cache:
+            pin = torch.device(dev).type == "cuda"
+            idx = torch.tensor([b for b, l in enumerate(lab) if not l], dtype=torch.int64)
+            sw = torch.tensor([self.distill_labelled_weight if l else 1.0 for l in lab], dtype=torch.float32)
+            if pin:
+                idx, sw = idx.pin_memory(), sw.pin_memory()
+            self._semi_cache[key] = (idx.to(dev, non_blocking=True), sw.to(dev, non_blocking=True), idx, sw)   # the staging tensors stay alive
+        return self._semi_cache[key][:2]
+
+    def _mix(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict], lab=None, unl=None, g=None, tmaps=None, tflips=None):
         """The draw of step ``mix_step`` and, where it mixes a sample, ``ops.mix_batch`` -> (inp, target, (sel, donor) or None).
-        Counts the step."""
-        tables = self.mix_sampler.draw(inp.shape[0], inp.shape[-2], inp.shape[-1], self.mix_step, self.mix_rank)
+        Counts the step.  With unlabelled samples (``unl``: their indices on the device; ``lab`` the host pattern): donors are drawn
+        inside the labelled and inside the unlabelled group; ClassMix reads the classes of an unlabelled donor from the teacher's
+        prediction, CutMix reads none; the unlabelled rows of the mixed target are filled with ``g`` by the caller."""
+        tables = self.mix_sampler.draw(inp.shape[0], inp.shape[-2], inp.shape[-1], self.mix_step, self.mix_rank,
+                                       groups=None if lab is None else [int(l) for l in lab])
         self.mix_step += 1
         self.last_mix_pasted = None
         if not bool(tables["kind"].any()):
             return inp, target, None
-        inp, target, sel, pasted = ops.mix_batch(inp.contiguous(), target.long().contiguous(), tables, self.num_classes,
+        target = target.long().contiguous()
+        if unl is not None:   # the unlabelled rows the mixing reads: the teacher's classes (ClassMix), or the ignore value
+            if bool((tables["kind"] == 2).any()):
+                pseudo = ops.predict_mask_views(tmaps, tuple(target.shape[-2:]), flips=tflips)
+                target = target.index_copy(0, unl, pseudo.index_select(0, unl).long())
+                if taps is not None:
+                    taps.update(pseudo_target=pseudo)
+            else:
+                target = target.index_fill(0, unl, g)
+        inp, target, sel, pasted = ops.mix_batch(inp.contiguous(), target, tables, self.num_classes,
                                                  self.mix_sampler.background)
         self.last_mix_pasted = pasted
         if taps is not None:
             taps.update(mix_inp=inp, mix_target=target, mix_sel=sel, mix_tables=tables, mix_pasted=pasted)
         return inp, target, (sel, tables["donor"])
 
-    def _add_consistency(self, logits, target, dz, hard, maps, flips, S: float, taps: Optional[dict], mix=None) -> torch.Tensor:
+    def _add_consistency(self, logits, target, dz, hard, maps, flips, S: float, taps: Optional[dict], mix=None,
+                         sample_weight=None) -> torch.Tensor:
         """The soft term of a step with a teacher: ``ops.consistency_loss`` against ``maps`` (read through ``mix`` where the
         batch was mixed) added into the hard term's ``dz`` at S lambda_t -> hard + lambda_t kd (a device tensor, no host sync).
         Counts the step."""
@@ -454,7 +509,8 @@ class SegEngine(nn.Module):
         self.distill_step += 1
         scratch = _loss_scratch(self, "_consist_scratch", ops.consistency_scratch_bytes(target.numel()), logits.device)
         kd, kept, _ = ops.consistency_loss(logits, maps, target, flips=flips, temperature=self.distill_temperature,
-                                           threshold=self.distill_threshold, grad_scale=S * lam, dz=dz, scratch=scratch, mix=mix)
+                                           threshold=self.distill_threshold, sample_weight=sample_weight, grad_scale=S * lam, dz=dz,
+                                           scratch=scratch, mix=mix)
         self.last_loss_kd, self.last_kd_kept = kd, kept
         total = hard + lam * kd
         if taps is not None:
@@ -802,20 +858,45 @@ class SegEngine(nn.Module):
 
     @torch.no_grad()
     def train_step(self, inp: torch.Tensor, target: torch.Tensor, taps: Optional[dict] = None,
-                   teacher_inp: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   teacher_inp: Optional[torch.Tensor] = None, labelled=None) -> torch.Tensor:
         """One `train.py:268-436` (or `train_mla.py:260-407`) iteration; returns the loss as a 0-dim device
         tensor (no host sync).  With a ``teacher``: the teacher sees ``teacher_inp`` (default ``inp``; the same geometry), and the
         loss is hard + lambda_t kd (``taps``: ``loss_hard``, ``loss_kd``, ``kd_kept``, ``teacher_logits``, ``distill_scale``).  With
         ``mix``: the teacher sees the unmixed batch, the student's forward and the hard loss the mixed one (``taps``: ``mix_inp``,
-        ``mix_target``, ``mix_sel``, ``mix_tables``, ``mix_pasted``)."""
+        ``mix_target``, ``mix_sel``, ``mix_tables``, ``mix_pasted``).  ``labelled``: a host sequence of B bools (default None: every
+        sample is labelled); a False needs a teacher: that sample's target row is filled with the ignore value on the device
+        (what the caller put there does not matter), the hard loss leaves it out and the consistency term weighs it 1 (``taps``:
+        ``labelled``, ``hard_valid``, ``sample_weight``, with ClassMix ``pseudo_target``)."""
         _check_trainable(self)
+        lab = unl = sw = None
+        if labelled is not None:
+            lab = tuple(bool(v) for v in labelled)
+            if len(lab) != inp.shape[0]:
+                raise ValueError(f"train_step: labelled has {len(lab)} entries, the batch {inp.shape[0]} samples")
+            if not all(lab):
+                if self.teacher is None:
+                    raise ValueError("train_step: an unlabelled sample needs a teacher: the consistency term is all it trains with")
+                unl, sw = self._semi_tables(lab, inp.device)
+        if unl is None and self.teacher is not None and self.distill_labelled_weight != 1.0:
+            sw = self._semi_tables((True,) * inp.shape[0], inp.device)[1]
+        g = self.ignore_index if self.ignore_index is not None else (255 if unl is not None else None)
+        self._hard_ignore = g
+        if g is not None and self.loss_kind not in self.IGNORE_LOSSES:
+            raise ValueError(f"loss {self.loss_kind!r} has no ignore label: an unlabelled sample needs one of {self.IGNORE_LOSSES}")
         if self.teacher is not None:   # before the student's forward: the teacher's activations are gone when the student's are saved
             tmaps, tflips = self._teacher_maps(inp if teacher_inp is None else teacher_inp)
         elif teacher_inp is not None:
             raise ValueError("train_step: teacher_inp without a teacher")
         mixed = None
         if self.mix_sampler is not None:   # after the teacher, which sees the batch as it came
-            inp, target, mixed = self._mix(inp, target, taps)
+            if unl is None:
+                inp, target, mixed = self._mix(inp, target, taps, lab)
+            else:
+                inp, target, mixed = self._mix(inp, target, taps, lab, unl, g, tmaps, tflips)
+        if unl is not None:   # a copy: the caller's tensor keeps what it held
+            target = target.long().index_fill(0, unl, g)
+            if taps is not None and mixed is not None:
+                taps.update(mix_target=target)
         dec = self.seg_decoder
         adapters = self.mode == "train_adapters"     # the head's input is trainable upstream: its gradient is needed
         asaves = [] if adapters else None            # what the two walks on the frozen backbone keep for the adapter backward
@@ -830,7 +911,9 @@ class SegEngine(nn.Module):
         logits, saved = dec._forward_core(*dec_in, save=True, training=True, **fwd_kw)
         loss, dz, target = loss_head(self, logits, target)
         if self.teacher is not None:
-            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, config.loss_scale, taps, mixed)
+            loss = self._add_consistency(logits, target, dz, loss, tmaps, tflips, config.loss_scale, taps, mixed, sw)
+        if taps is not None and (g is not None or sw is not None):
+            taps.update(labelled=lab, hard_valid=self.last_hard_valid if g is not None else None, sample_weight=sw)
         d16, d_lo, bpart, inv = logit_gradient(self, dz, logits)
         # every reducer this step fires, in the order they are finished below (``begin`` only resets host counters)
         reducers = []

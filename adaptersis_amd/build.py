@@ -34,10 +34,12 @@ def _hipcc() -> str:
 
 # Libraries beside libasis_hip.so: file name -> its sources.  The training step loads libasis_hip.so alone, whose source list and
 # link line do not change when an optional op arrives; such an op lives in a library of its own, loaded on first use
-# (adaptersis_amd/_lib_distill.py, _lib_consist.py, _lib_mix.py), linked against libasis_hip.so for the error plumbing
+# (adaptersis_amd/_lib_distill.py, _lib_consist.py, _lib_mix.py, _lib_semi.py), linked against libasis_hip.so for the error plumbing
 # (asis_set_error_ / asis_last_error).  The first two are instantiations of one kernel, csrc/soft_target.h, which neither exports;
-# the third holds the batch-mixing kernels and that kernel's instantiation over a mixed batch.
-SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",), "libasis_mix.so": ("mix.hip",)}
+# the third holds the batch-mixing kernels and that kernel's instantiation over a mixed batch; the fourth is the fused loss of
+# loss.hip (csrc/seg_loss_body.h) instantiated with an ignore label.
+SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",), "libasis_mix.so": ("mix.hip",),
+             "libasis_semi.so": ("semi.hip",)}
 
 
 def sources():

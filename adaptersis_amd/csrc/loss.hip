@@ -14,212 +14,9 @@
 // decoder's (h, w) grid as the 16-bit operand of the dgrad / wgrad GEMMs.
 #include "asis_common.h"
 #include "bilinear_tap.h"  // MAXC, Tap, tap_ac_false, sample_logits, softmax_c, softmax_bwd_c
+#include "seg_loss_body.h"  // the fused loss: seg_loss_{fwd,finalize,bwd}_kernel and their launches; AllValid here, IgnoreLabel in semi.hip
 
 namespace {
-
-// One generalised pass for every loss of segloss/: with x0 = resized logits, x1 = softmax(x0), x2 = softmax(x1)
-//   region term on q = x_{n_region}:  per (b, c) sums I = sum q t, Sp = sum q, St = sum t   (tp = I, fp = Sp - I, fn = St - I)
-//   CE term (n_ce >= 1): nll = -log softmax(x_{n_ce-1})[t], weighted mean with optional class weights
-// partial[(b * nblk + blk) * (C*3 + 2) + {c*3 + {0,1,2}: I, Sp, St ; C*3: sum w nll ; C*3+1: sum w}]
-__global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                           const float* __restrict__ ce_w, int h, int w, int H, int W, int C,
-                                                           int n_region, int n_ce, float* __restrict__ partial) {
-  __shared__ float red[4][MAXC * 3 + 2];
-  const int b = blockIdx.y, nblk = gridDim.x;
-  const float* lg = logits + (int64_t)b * h * w * C;
-  const int64_t* tg = target + (int64_t)b * H * W;
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  float acc[MAXC * 3 + 2];
-#pragma unroll
-  for (int i = 0; i < MAXC * 3 + 2; ++i) acc[i] = 0.f;
-  const int npix = H * W;
-  const int nmax = n_region > n_ce ? n_region : n_ce;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += nblk * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    float z[MAXC];
-    sample_logits(lg, h, w, C, y, x, sh, sw, z);
-    const int t = (int)tg[p];
-    for (int k = 0; k <= nmax; ++k) {
-      if (k == n_region) {
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c)
-          if (c < C) {
-            const float tt = (t == c) ? 1.f : 0.f;
-            acc[c * 3 + 0] += z[c] * tt;
-            acc[c * 3 + 1] += z[c];
-            acc[c * 3 + 2] += tt;
-          }
-      }
-      if (k + 1 == n_ce) {  // log-sum-exp on the input of the CE's own softmax
-        float m = -INFINITY, zt = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c)
-          if (c < C) {
-            m = fmaxf(m, z[c]);
-            if (c == t) zt = z[c];
-          }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c)
-          if (c < C) se += expf(z[c] - m);
-        const float wt = (ce_w && t >= 0 && t < C) ? ce_w[t] : 1.f;
-        acc[MAXC * 3 + 0] += wt * (logf(se) - (zt - m));
-        acc[MAXC * 3 + 1] += wt;
-      }
-      if (k < nmax) softmax_c(z, C);
-    }
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < MAXC * 3 + 2; ++i)
-    if (i < C * 3 || i >= MAXC * 3) {
-      const float v = wave_sum(acc[i]);
-      if (lane == 0) red[wid][i] = v;
-    }
-  __syncthreads();
-  const int tx = threadIdx.x;
-  if (tx < C * 3 + 2) {
-    const int src = tx < C * 3 ? tx : MAXC * 3 + (tx - C * 3);
-    partial[((int64_t)b * nblk + blockIdx.x) * (C * 3 + 2) + tx] = (red[0][src] + red[1][src]) + (red[2][src] + red[3][src]);
-  }
-}
-
-// sums[b][c][3] (fp32, from double accumulation), loss, and the backward coefficients:
-//   coef[(b*C + c)*2 + {0,1}] : d region / d q[b,c,pix] = coef0 * t + coef1     (times grad_scale)
-//   coef[B*C*2]               : grad_scale / sum of CE weights (0 without a CE term)
-// region modes (all derive from I, Sp, St):
-//   0 Dice      segloss/dice.py:27-33            1 - mean 2I/(Sp+St+eps)
-//   1 soft IoU  segloss/iou_multi.py:38-49       mean [1 - (I+eps)/(Sp+St-I+eps)]
-//   2 SoftDice  segloss/dice_loss.py:255-291     -mean (2I+eps)/(Sp+St+eps)            (2tp+fp+fn = Sp+St)
-//   3 Tversky   segloss/dice_loss.py:333-372     -mean (I+eps)/((1-a-b)I + a Sp + b St + eps),  a=.3, b=.7
-//   4 none      (CE only, segloss/ND_Crossentropy.py:11-32)
-__global__ void seg_loss_finalize_kernel(const float* __restrict__ partial, int nblk, int B, int C, float eps, int mode,
-                                         int n_ce, float grad_scale, float* __restrict__ sums, float* __restrict__ loss,
-                                         float* __restrict__ coef) {
-  __shared__ double dsum[256];
-  __shared__ double ce_tot[2];
-  const int i = threadIdx.x;  // one thread per (b, c)
-  const int PS = C * 3 + 2;
-  double term = 0.0;
-  if (i < B * C) {
-    const int b = i / C, c = i - b * C;
-    double s0 = 0, s1 = 0, s2 = 0;
-    for (int k = 0; k < nblk; ++k) {
-      const float* p = partial + ((int64_t)b * nblk + k) * PS + c * 3;
-      s0 += p[0];
-      s1 += p[1];
-      s2 += p[2];
-    }
-    if (sums) {
-      sums[i * 3 + 0] = (float)s0;
-      sums[i * 3 + 1] = (float)s1;
-      sums[i * 3 + 2] = (float)s2;
-    }
-    const double bc = (double)B * C, e = (double)eps;
-    double c0 = 0.0, c1 = 0.0;
-    if (mode == 0) {
-      const double S = s1 + s2 + e;
-      term = 2.0 * s0 / S;
-      c0 = -2.0 / (bc * S);
-      c1 = 2.0 * s0 / (bc * S * S);
-    } else if (mode == 1) {
-      const double In = s0 + e, U = s1 + s2 - s0 + e;
-      term = In / U;  // d(-In/U)/dq = t * (-(U + In)/U^2) + In/U^2
-      c0 = -(U + In) / (U * U) / bc;
-      c1 = In / (U * U) / bc;
-    } else if (mode == 2) {
-      const double Nn = 2.0 * s0 + e, S = s1 + s2 + e;
-      term = Nn / S;
-      c0 = -2.0 / (bc * S);
-      c1 = Nn / (bc * S * S);
-    } else if (mode == 3) {
-      const double al = 0.3, be = 0.7, g = 1.0 - al - be;
-      const double Nn = s0 + e, Dn = g * s0 + al * s1 + be * s2 + e;
-      term = Nn / Dn;  // d(-Nn/Dn)/dq = -(t Dn - Nn (g t + al)) / Dn^2
-      c0 = -(Dn - Nn * g) / (Dn * Dn) / bc;
-      c1 = Nn * al / (Dn * Dn) / bc;
-    }
-    coef[i * 2 + 0] = (float)(c0 * grad_scale);
-    coef[i * 2 + 1] = (float)(c1 * grad_scale);
-  }
-  dsum[i] = term;
-  if (i < 2) {
-    double s = 0.0;
-    if (n_ce > 0)
-      for (int k = 0; k < B * nblk; ++k) s += partial[(int64_t)k * PS + C * 3 + i];
-    ce_tot[i] = s;
-  }
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (i < o) dsum[i] += dsum[i + o];
-    __syncthreads();
-  }
-  if (i == 0) {
-    const double mean = dsum[0] / ((double)B * C);
-    double l = (mode == 0 || mode == 1) ? 1.0 - mean : (mode == 4 ? 0.0 : -mean);
-    if (n_ce > 0) l += ce_tot[0] / ce_tot[1];
-    *loss = (float)l;
-    coef[B * C * 2] = n_ce > 0 ? (float)((double)grad_scale / ce_tot[1]) : 0.f;
-  }
-}
-
-// dz[b, y, x, c] = d loss / d (resized logits), fp32 at (H, W)
-__global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                           const float* __restrict__ coef, const float* __restrict__ ce_w,
-                                                           int B, int h, int w, int H, int W, int C, int n_region, int n_ce,
-                                                           int mode, float* __restrict__ dz) {
-  const int b = blockIdx.y;
-  const float* lg = logits + (int64_t)b * h * w * C;
-  const int64_t* tg = target + (int64_t)b * H * W;
-  float* out = dz + (int64_t)b * H * W * C;
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  const int npix = H * W;
-  const float ce_scale = coef[B * C * 2];
-  const int nmax = n_region > n_ce ? n_region : n_ce;
-  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += gridDim.x * blockDim.x) {
-    const int y = p / W, x = p - y * W;
-    float p1[MAXC], p2[MAXC];
-    sample_logits(lg, h, w, C, y, x, sh, sw, p1);
-    if (nmax >= 1) softmax_c(p1, C);
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) p2[c] = p1[c];
-    if (nmax >= 2) softmax_c(p2, C);
-    const int t = (int)tg[p];
-    float r[MAXC];  // region gradient wrt q
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-      r[c] = (c < C && mode != 4) ? coef[(b * C + c) * 2 + 0] * ((t == c) ? 1.f : 0.f) + coef[(b * C + c) * 2 + 1] : 0.f;
-    const float cw = n_ce > 0 ? ce_scale * ((ce_w && t >= 0 && t < C) ? ce_w[t] : 1.f) : 0.f;
-    float g[MAXC];
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) g[c] = 0.f;
-    if (nmax >= 2) {  // level x1: softmax2 backward of the region term + region at x1 + CE over softmax(x1)
-      if (n_region == 2) {
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) g[c] = r[c];
-        softmax_bwd_c(g, p2, C);
-      }
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c)
-        if (c < C) {
-          if (n_region == 1) g[c] += r[c];
-          if (n_ce == 2) g[c] += cw * (p2[c] - ((t == c) ? 1.f : 0.f));
-        }
-      softmax_bwd_c(g, p1, C);
-    } else if (nmax == 1 && n_region == 1) {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) g[c] = r[c];
-      softmax_bwd_c(g, p1, C);
-    }
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-      if (c < C) {
-        if (n_region == 0) g[c] += r[c];
-        if (n_ce == 1) g[c] += cw * (p1[c] - ((t == c) ? 1.f : 0.f));
-        out[(int64_t)p * C + c] = g[c];
-      }
-  }
-}
 
 // Transpose of the bilinear resize (align_corners=False), gather form (deterministic):
 // dsrc[b, sy, sx, c] = sum over output pixels whose taps touch (sy, sx).  Writes a 16-bit NHWC
@@ -415,33 +212,15 @@ extern "C" int asis_dice_nblk(int H, int W) {
 extern "C" int asis_seg_loss_fwd(void* stream, const float* logits, const int64_t* target, const float* ce_weight, int B,
                                  int h, int w, int H, int W, int C, int n_region, int mode, float eps, int n_ce,
                                  float grad_scale, float* partial, float* sums, float* loss, float* coef) {
-  ASIS_REQUIRE(logits && target && partial && loss && coef, "asis_seg_loss_fwd: null pointer");
-  ASIS_REQUIRE(C >= 1 && C <= MAXC, "asis_seg_loss_fwd: C=%d must be in 1..%d", C, MAXC);
-  ASIS_REQUIRE(B * C <= 256 && B <= 65535, "asis_seg_loss_fwd: B*C=%d must be <= 256", B * C);
-  ASIS_REQUIRE(n_region >= 0 && n_region <= 2, "asis_seg_loss_fwd: n_region must be 0, 1 or 2");
-  ASIS_REQUIRE(n_ce >= 0 && n_ce <= 2, "asis_seg_loss_fwd: n_ce must be 0 (no CE term), 1 or 2");
-  ASIS_REQUIRE(mode >= 0 && mode <= 4, "asis_seg_loss_fwd: mode must be 0..4");
-  ASIS_REQUIRE(mode != 4 || n_ce > 0, "asis_seg_loss_fwd: mode 4 (no region term) needs a CE term");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int nblk = asis_dice_nblk(H, W);
-  hipLaunchKernelGGL(seg_loss_fwd_kernel, dim3(nblk, B), dim3(256), 0, s, logits, target, ce_weight, h, w, H, W, C, n_region,
-                     n_ce, partial);
-  hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(256), 0, s, partial, nblk, B, C, eps, mode, n_ce, grad_scale,
-                     sums, loss, coef);
-  ASIS_CHECK_LAUNCH("asis_seg_loss_fwd");
-  return ASIS_OK;
+  return seg_loss_fwd_launch("asis_seg_loss_fwd", AllValid{}, stream, logits, target, ce_weight, B, h, w, H, W, C, n_region, mode, eps,
+                             n_ce, grad_scale, partial, sums, loss, coef);
 }
 
 extern "C" int asis_seg_loss_bwd(void* stream, const float* logits, const int64_t* target, const float* coef,
                                  const float* ce_weight, int B, int h, int w, int H, int W, int C, int n_region, int mode,
                                  int n_ce, float* dz) {
-  ASIS_REQUIRE(logits && target && coef && dz, "asis_seg_loss_bwd: null pointer");
-  ASIS_REQUIRE(C >= 1 && C <= MAXC && n_region >= 0 && n_region <= 2 && n_ce >= 0 && n_ce <= 2 && mode >= 0 && mode <= 4,
-               "asis_seg_loss_bwd: bad C / n_region / n_ce / mode");
-  hipLaunchKernelGGL(seg_loss_bwd_kernel, dim3(asis_dice_nblk(H, W), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     logits, target, coef, ce_weight, B, h, w, H, W, C, n_region, n_ce, mode, dz);
-  ASIS_CHECK_LAUNCH("asis_seg_loss_bwd");
-  return ASIS_OK;
+  return seg_loss_bwd_launch("asis_seg_loss_bwd", AllValid{}, stream, logits, target, coef, ce_weight, B, h, w, H, W, C, n_region, mode,
+                             n_ce, dz);
 }
 
 // the two-mode entry points of the train.py / train_mla.py losses (region term only)

@@ -1591,6 +1591,39 @@ def seg_loss_bwd(logits: torch.Tensor, target: torch.Tensor, coef: torch.Tensor,
     return dz
 
 
+def seg_loss_ignore(logits: torch.Tensor, target: torch.Tensor, ignore_index: int, n_region: int, mode: int = LOSS_DICE,
+                    eps: float = 1e-19, n_ce: int = 0, ce_weight: Optional[torch.Tensor] = None, grad_scale: float = 1.0):
+    """``seg_loss_fwd`` + ``seg_loss_bwd`` with an ignore label, in one call (csrc/semi.hip, libasis_semi.so; include/asis_semi.h
+    states the semantics): pixels whose label is ``ignore_index`` (an int outside 0..C-1) take part in no sum and get a dz of
+    exactly 0, their logits are not read; a sample without a valid pixel is left out of the mean of the region term.
+    -> (loss [1], dz fp32 [B,H,W,C] (times grad_scale), valid int32 [B] = the valid pixels per sample, sums fp32 [B,C,3])."""
+    from . import _lib_semi
+    op = "seg_loss_ignore"
+    _dev(logits, target, ce_weight)
+    B, h, w, Cc = logits.shape
+    H, W = target.shape[-2:]
+    if target.dtype != torch.int64 or not target.is_contiguous():
+        raise ValueError(f"{op}: target must be contiguous int64 [B,H,W]")
+    if ce_weight is not None and (ce_weight.numel() != Cc or ce_weight.dtype != torch.float32):
+        raise ValueError(f"{op}: ce_weight must be float32 [C]")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or 0 <= ignore_index < Cc \
+            or not -2 ** 31 <= ignore_index < 2 ** 31:
+        raise ValueError(f"{op}: ignore_index={ignore_index!r} must be an int outside the classes 0..{Cc - 1}")
+    semi = _lib_semi.lib()
+    nblk = lib().asis_dice_nblk(H, W)
+    dev = logits.device
+    partial = torch.empty((B, nblk, semi.asis_semi_partial_stride(Cc)), device=dev, dtype=torch.float32)
+    sums = torch.empty((B, Cc, 3), device=dev, dtype=torch.float32)
+    loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    coef = torch.empty((B * Cc * 2 + 1,), device=dev, dtype=torch.float32)
+    valid = torch.empty((B,), device=dev, dtype=torch.int32)
+    dz = torch.empty((B, H, W, Cc), device=dev, dtype=torch.float32)
+    check(semi.asis_semi_loss(_stream(), _f32c(logits).data_ptr(), target.data_ptr(), _p(_f32c(ce_weight)), B, h, w, H, W, Cc,
+                              ignore_index, int(n_region), int(mode), float(eps), int(n_ce), float(grad_scale), partial.data_ptr(),
+                              sums.data_ptr(), loss.data_ptr(), coef.data_ptr(), valid.data_ptr(), dz.data_ptr()), "asis_semi_loss")
+    return loss, dz, valid, sums
+
+
 def dice_fwd(logits: torch.Tensor, target: torch.Tensor, n_softmax: int, eps: float = 1e-19, grad_scale: float = 1.0,
              mode: int = 0):
     """Region-only shorthand: mode 0 = Dice (segloss/dice.py), mode 1 = soft IoU (segloss/iou_multi.py, eps = smooth)."""

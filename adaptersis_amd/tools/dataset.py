@@ -265,3 +265,44 @@ class Autolapro(_EndoFrames):
         d = [os.path.join(dir_main, split, f"seq_{i}") for i in rng]
         super().__init__([(os.path.join(p, "images"), os.path.join(p, "binary_masks")) for p in d], transform, imsize,
                          resize_on_gpu, os.path.join(dir_main, split))
+
+
+# ---- frames without labels (semi-supervised training: --unlabelled_path) ---------------------------------------------------------------
+class UnlabelledFrames(torch.utils.data.Dataset):
+    """Every ``*.png`` / ``*.jpg`` below ``root`` (sorted by path), decoded to RGB and resized on the host to ``imsize`` with PIL
+    BILINEAR as the labelled sets resize theirs.  An item has the form the labelled sets' items have after the device resize:
+    (uint8 HWC frame, uint8 mask [imsize, imsize] filled with ``IGNORE`` = 255, index); ``collate_u8`` batches them.  The mask
+    carries no information: ``SegEngine.train_step(labelled=)`` fills the rows of unlabelled samples itself.
+    ``root == "synthetic"``: ``n_synth`` seeded frames, the images of ``utils.weights.synthetic_batch`` under a seed of their own,
+    as ``--data_path synthetic`` makes its labelled ones."""
+    IGNORE = 255
+    EXTENSIONS = (".png", ".jpg")
+
+    def __init__(self, root, imsize, n_synth=24):
+        super().__init__()
+        self.imsize, self.frames = int(imsize), None
+        if root == "synthetic":
+            from ..utils import weights as W
+            img, _ = W.synthetic_batch(n_synth, self.imsize, seed=3)
+            self.frames = (img.permute(0, 2, 3, 1) * 255.0).round().clamp_(0, 255).to(torch.uint8).contiguous()
+            self.files = list(range(n_synth))
+            return
+        if not os.path.isdir(root):
+            raise ValueError(f"{root}: no such directory (the unlabelled frames: a directory, or 'synthetic')")
+        self.files = sorted(os.path.join(d, f) for d, _, fs in os.walk(root) for f in fs if f.lower().endswith(self.EXTENSIONS))
+        if not self.files:
+            raise ValueError(f"{root}: no *.png or *.jpg frame below it")
+
+    def __getitem__(self, index):
+        mask = torch.full((self.imsize, self.imsize), self.IGNORE, dtype=torch.uint8)
+        if self.frames is not None:
+            return self.frames[index], mask, index
+        from PIL import Image
+        with open(self.files[index], "rb") as f:
+            img = Image.open(f).convert("RGB")
+        if img.size != (self.imsize, self.imsize):
+            img = img.resize((self.imsize, self.imsize), resample=Image.BILINEAR)
+        return torch.from_numpy(np.array(img).astype(np.uint8)), mask, index
+
+    def __len__(self):
+        return len(self.files)

@@ -13,6 +13,12 @@ draws its own.  The tables (CPU tensors):
                         its entries < num_classes matter
 
 With B = 1 nothing is mixed (kind is 0).  The streams of the four tables do not depend on ``kind`` or ``p``.
+
+``draw(..., groups=)`` (a host int sequence of B entries; default None: the tables above, bit for bit): donors stay inside their
+group — semi-supervised training mixes labelled frames among themselves and unlabelled frames among themselves.  In the place of
+the one shift, one shift per group of more than one member is drawn, the groups in ascending id: with m_0 < m_1 < ... the n
+members of a group and r uniform in 1..n-1, donor[m_i] = m_{(i + r) mod n}.  A group of one is not mixed (kind 0, its own donor).
+The other three tables are drawn after the shifts exactly as without groups.
 """
 from __future__ import annotations
 
@@ -34,15 +40,29 @@ class MixSampler:
         self.kind, self.p, self.seed = kind, float(p), int(seed)
         self.num_classes, self.background = int(num_classes), bool(background)
 
-    def draw(self, B: int, H: int, W: int, step: int, rank: int = 0) -> dict:
+    def draw(self, B: int, H: int, W: int, step: int, rank: int = 0, groups=None) -> dict:
         B, H, W = int(B), int(H), int(W)
         if B < 1 or H < 1 or W < 1 or int(step) < 0 or int(rank) < 0:
             raise ValueError(f"draw: need B, H, W >= 1 and step, rank >= 0 (B={B} H={H} W={W} step={step} rank={rank})")
         r = np.random.RandomState([self.seed & 0xFFFFFFFF, int(rank) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF])
-        shift = int(r.randint(1, B)) if B > 1 else 0
-        donor = (np.arange(B) + shift) % B
+        if groups is None:
+            shift = int(r.randint(1, B)) if B > 1 else 0
+            donor = (np.arange(B) + shift) % B
+            alone = np.full(B, B == 1)
+        else:
+            gid = np.asarray(groups).astype(np.int64).reshape(-1)
+            if gid.shape[0] != B:
+                raise ValueError(f"draw: groups has {gid.shape[0]} entries, the batch {B} samples")
+            donor, alone = np.arange(B), np.zeros(B, dtype=bool)
+            for g in np.unique(gid):   # ascending
+                members = np.nonzero(gid == g)[0]
+                n = len(members)
+                if n == 1:
+                    alone[members] = True
+                    continue
+                donor[members] = members[(np.arange(n) + int(r.randint(1, n))) % n]
         mixed = r.uniform(size=B) < self.p
-        kind = np.where(mixed & (B > 1), KINDS[self.kind], 0)
+        kind = np.where(mixed & ~alone, KINDS[self.kind], 0)
         ratio = np.sqrt(1.0 - r.uniform(size=B))
         ch, cw = (H * ratio).astype(np.int64), (W * ratio).astype(np.int64)
         cy, cx = r.randint(0, H, size=B), r.randint(0, W, size=B)

@@ -88,6 +88,21 @@ def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0, weak: b
     return x, y, aug(img, msk, weak_params(params))[0]
 
 
+def _append_unlabelled(inp, target, frames, masks):
+    """The loader's labelled batch followed by the unlabelled frames (uint8 [U,S,S,3], masks of 255) -> (inp, target, labelled) on
+    the device, in the labelled batch's own form: a uint8 batch (a ``FrameBatch`` is resized first) stays uint8 and goes through
+    the GPU augmentation as one batch; a float batch takes the frames as float CHW / 255."""
+    from .tools.dataset import FrameBatch
+    if isinstance(inp, FrameBatch):
+        inp, target = _resize_frames(inp)
+    inp, target = inp.cuda(non_blocking=True), target.cuda(non_blocking=True)
+    frames, masks = frames.cuda(non_blocking=True), masks.cuda(non_blocking=True)
+    labelled = [True] * inp.shape[0] + [False] * frames.shape[0]
+    if inp.dtype == torch.uint8:
+        return torch.cat([inp, frames]), torch.cat([target.to(torch.uint8), masks]), labelled
+    return torch.cat([inp, frames.permute(0, 3, 1, 2).to(inp.dtype) / 255.0]), torch.cat([target, masks.to(target.dtype)]), labelled
+
+
 def _resize_frames(fb):
     """FrameBatch -> (uint8 [B,S,S,3], uint8 [B,S,S] labels) on the device; items the collate already resized on the host
     are put back in their places."""
@@ -348,6 +363,78 @@ class _DistillEntry:
         return f"<distill step {self.engine.distill_step}>"
 
 
+SEMI_FLAGS = ("unlabelled_per_batch", "distill_labelled_weight")
+
+
+def check_semi_args(args, loss: Optional[str] = None) -> Optional[str]:
+    """What is wrong with the combination of the semi-supervision flags (--unlabelled_path, --unlabelled_per_batch, --ignore_index,
+    --distill_labelled_weight), or None.  ``loss``: the loss the run trains with (default --loss).  Needs no device and no
+    process group."""
+    path, g = getattr(args, "unlabelled_path", None), getattr(args, "ignore_index", None)
+    loss = loss or getattr(args, "loss", "dice")
+    if path is not None and getattr(args, "distill_teacher", None) is None:
+        return "--unlabelled_path needs --distill_teacher: the consistency term is all an unlabelled frame trains with"
+    if path is None and getattr(args, "unlabelled_per_batch", None) is not None:
+        return "--unlabelled_per_batch needs --unlabelled_path (a directory of frames, or synthetic)"
+    if getattr(args, "distill_labelled_weight", None) is not None:
+        if getattr(args, "distill_teacher", None) is None:
+            return "--distill_labelled_weight needs --distill_teacher (ema or the path of a checkpoint)"
+        if not 0.0 <= float(args.distill_labelled_weight) < float("inf"):
+            return "--distill_labelled_weight must be finite and >= 0"
+    if path is not None and path != "synthetic" and not os.path.isdir(path):
+        return f"--unlabelled_path {path}: no such directory (a directory of *.png / *.jpg frames, or synthetic)"
+    u = getattr(args, "unlabelled_per_batch", None)
+    if u is not None and int(u) < 1:
+        return "--unlabelled_per_batch must be at least 1"
+    if (path is not None or g is not None) and loss not in SegEngine.IGNORE_LOSSES:
+        flag = "--ignore_index" if g is not None else "--unlabelled_path"
+        return f"{flag} needs a loss with an ignore label (--loss one of {', '.join(SegEngine.IGNORE_LOSSES)}), not {loss}"
+    return None
+
+
+def _semi_engine_args(args) -> dict:
+    """The semi-supervision flags as ``SegEngine`` arguments; without them nothing is passed and the engine is what it was."""
+    out = {}
+    if getattr(args, "ignore_index", None) is not None:
+        out["ignore_index"] = int(args.ignore_index)
+    if getattr(args, "distill_labelled_weight", None) is not None:
+        out["distill_labelled_weight"] = float(args.distill_labelled_weight)
+    return out
+
+
+class UnlabelledStream:
+    """The unlabelled half of a step's batch (--unlabelled_path): ``tools.dataset.UnlabelledFrames`` behind a
+    ``DistributedSampler`` and an epoch counter of its own.  ``next()`` -> (uint8 [U,S,S,3] frames, uint8 [U,S,S] masks of 255);
+    when the rank's share is used up the epoch is counted and the stream starts over under that epoch's shuffle.  The labelled
+    loader's epochs and the learning-rate schedule do not see it.  ``epoch`` is what the checkpoint's ``semi`` entry holds."""
+
+    def __init__(self, dataset, per_batch: int, num_workers: int = 0):
+        from .tools.dataset import collate_u8
+        self.dataset, self.per_batch, self.epoch, self._it = dataset, int(per_batch), 0, None
+        self.sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=utils.get_world_size(),
+                                                                       rank=utils.get_rank())
+        self.loader = torch.utils.data.DataLoader(dataset, sampler=self.sampler, batch_size=self.per_batch, num_workers=num_workers,
+                                                  pin_memory=True, collate_fn=collate_u8, drop_last=len(self.sampler) >= self.per_batch)
+
+    def next(self):
+        for _ in range(2):
+            if self._it is None:
+                self.sampler.set_epoch(self.epoch)
+                self._it = iter(self.loader)
+            try:
+                frames, masks, _ = next(self._it)
+                return frames, masks
+            except StopIteration:
+                self._it = None
+                self.epoch += 1
+        raise RuntimeError("the unlabelled stream gave no frame")
+
+    def load_state_dict(self, entry):
+        """the ``semi`` entry of a checkpoint as ``restart_from_checkpoint`` sees it: the unlabelled epoch"""
+        self.epoch, self._it = int(entry["epoch"]), None
+        return f"<unlabelled epoch {self.epoch}>"
+
+
 def _ema_args(args) -> dict:
     """The weight-averaging flags (--ema_decay, --ema_no_warmup) as ``SegEngine`` arguments; without --ema_decay nothing is passed
     and the engine is what it was."""
@@ -419,7 +506,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     non_rigid_p = float(getattr(args, "aug_non_rigid", 0.0))
     if not 0.0 <= non_rigid_p <= 1.0:
         raise ValueError("--aug_non_rigid must be a probability in [0, 1]")
-    bad = check_backbone_args(args) or check_distill_args(args) or check_mix_args(args)
+    bad = check_backbone_args(args) or check_distill_args(args) or check_mix_args(args) or check_semi_args(args, loss)
     if bad:
         raise ValueError(bad)
     utils.init_distributed_mode(args)
@@ -436,7 +523,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     teacher = getattr(args, "distill_teacher", None)
     if teacher is not None and teacher != "ema":
         teacher = build_teacher(args, head, num_classes, dev, model)
-    distill = {**_distill_engine_args(args, teacher), **_mix_engine_args(args)}
+    distill = {**_distill_engine_args(args, teacher), **_mix_engine_args(args), **_semi_engine_args(args)}
     if head == "mla":
         lr = args.lr * (args.batch_size_per_gpu * utils.get_world_size()) / 16.0  # linear scaling rule
         engine = _engine_for(model, backbone_encoder, cross_vit, cross_cnn, seg_decoder, lr=lr, momentum=0.9,
@@ -452,6 +539,7 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     engine.aug_non_rigid = non_rigid_p      # read by train(): its signature is the reference's and carries no arguments
     engine.distill_weak = bool(getattr(args, "distill_weak", False))
     engine.mix_rank = utils.get_rank()      # --mix: every rank draws its own tables
+    engine.unlabelled = None                # --unlabelled_path: read by train(), like aug_non_rigid
 
     dataset_train, dataset_val, collate = open_datasets(args)
     workers = args.num_workers if collate is not None else 0      # PNG decode runs in loader workers; tensors in memory do not need any
@@ -467,6 +555,13 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                                                                rank=utils.get_rank())
     train_loader = torch.utils.data.DataLoader(dataset_train, sampler=sampler, batch_size=args.batch_size_per_gpu,
                                                num_workers=workers, pin_memory=True, collate_fn=collate)   # no drop_last: train.py:168-174
+    if getattr(args, "unlabelled_path", None) is not None:
+        from .tools.dataset import UnlabelledFrames
+        unl_set = UnlabelledFrames(args.unlabelled_path, args.imsize)
+        per = getattr(args, "unlabelled_per_batch", None)
+        engine.unlabelled = UnlabelledStream(unl_set, args.batch_size_per_gpu if per is None else per,
+                                             0 if args.unlabelled_path == "synthetic" else args.num_workers)
+        print(f"Unlabelled stream: {len(unl_set)} frames, {engine.unlabelled.per_batch} a step.")
     print(f"Data loaded with {len(dataset_train)} train and {len(dataset_val)} val imgs.")
 
     class _Cosine:  # torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, epochs, eta_min=0), stepped per epoch
@@ -508,7 +603,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                                   state_dict=seg_decoder, **extra, **({} if lora is None else {"lora": lora}), optimizer=optimizer,
                                   scheduler=scheduler, **({} if ema_entry is None else {"ema": ema_entry}),
                                   **({} if engine.teacher is None else {"distill": _DistillEntry(engine)}),
-                                  **({} if engine.mix_sampler is None else {"mix": _MixEntry(engine)}))
+                                  **({} if engine.mix_sampler is None else {"mix": _MixEntry(engine)}),
+                                  **({} if engine.unlabelled is None else {"semi": engine.unlabelled}))
     if ema_entry is not None and resumed and not ema_entry.loaded:
         engine.ema.reset()
         print(f"=> no usable 'ema' entry in '{ckpt_path}': the average starts from the restored live weights")
@@ -561,6 +657,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                 ckpt["distill"] = {"step": engine.distill_step}
             if engine.mix_sampler is not None:  # --mix: the step the next draw is seeded with
                 ckpt["mix"] = {"step": engine.mix_step}
+            if engine.unlabelled is not None:   # --unlabelled_path: the epoch of the unlabelled stream
+                ckpt["semi"] = {"epoch": engine.unlabelled.epoch}
             torch.save(ckpt, os.path.join(args.output_dir, "checkpoint.pth.tar"))
     print("Training of the supervised linear classifier on frozen features completed.\n"
           "Top-1 test accuracy: {acc:.1f}".format(acc=best_acc))
@@ -581,16 +679,25 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
     # iteration (also in the short last batch); any other loader may not, so the ranks' batch sizes are exchanged per step
     ragged = parallel.collectives_on() and not isinstance(getattr(loader, "sampler", None),
                                                           torch.utils.data.distributed.DistributedSampler)
+    stream = getattr(engine, "unlabelled", None)
     for (inp, target, idx) in metric_logger.log_every(loader, 20, "Epoch: [{}]".format(epoch)):
         if ragged:
             parallel.set_batch_ratio(int(inp.shape[0]))
+        labelled = None
+        if stream is not None:   # the labelled batch followed by the unlabelled frames, through the augmentation in one call
+            inp, target, labelled = _append_unlabelled(inp, target, *stream.next())
         batch = _to_device_batch(inp, target, train=True, non_rigid_p=getattr(engine, "aug_non_rigid", 0.0),
                                  weak=engine.teacher is not None and getattr(engine, "distill_weak", False))
-        loss = engine.train_step(batch[0], batch[1], None, *batch[2:])
+        if labelled is None:
+            loss = engine.train_step(batch[0], batch[1], None, *batch[2:])
+        else:
+            loss = engine.train_step(batch[0], batch[1], None, *batch[2:], labelled=labelled)
         torch.cuda.synchronize()  # the reference syncs and reads the loss every step (train.py:439-440)
         metric_logger.update(loss=loss.item())
         if engine.teacher is not None:     # the soft term and the share of the pixels its confidence gate let through
             metric_logger.update(loss_kd=engine.last_loss_kd.item(), kd_kept=engine.last_kd_kept.item() / batch[1].numel())
+        if stream is not None or getattr(engine, "ignore_index", None) is not None:   # the share of the pixels that carry a label
+            metric_logger.update(hard_valid=int(engine.last_hard_valid.sum()) / batch[1].numel())
         if engine.mix_sampler is not None:  # the share of the batch's pixels that came from another sample
             pasted = engine.last_mix_pasted
             metric_logger.update(mix_pasted=0.0 if pasted is None else int(pasted.sum()) / batch[1].numel())
@@ -659,7 +766,7 @@ class _ArgumentParser(argparse.ArgumentParser):
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        bad = check_backbone_args(ns) or check_distill_args(ns) or check_mix_args(ns)
+        bad = check_backbone_args(ns) or check_distill_args(ns) or check_mix_args(ns) or check_semi_args(ns)
         if bad:
             self.error(bad)
         return ns, rest
@@ -749,6 +856,18 @@ def get_args_parser():
     p.add_argument("--mix_p", default=None, type=float, help="probability that a sample is mixed (default 1)")
     p.add_argument("--mix_seed", default=None, type=int, help="seed of the draws, which depend on (seed, rank, step) alone (default 0)")
     p.add_argument("--mix_background", action="store_true", help="classmix: class 0 may be pasted too")
+    # extension: semi-supervised training (SegEngine ignore_index=, train_step labelled=): unlabelled frames in every batch
+    p.add_argument("--unlabelled_path", default=None, type=str, metavar="DIR|synthetic",
+                   help="a stream of frames without labels (every *.png / *.jpg below DIR): each step's batch is the labelled "
+                        "batch followed by --unlabelled_per_batch of them, which train through the consistency term alone "
+                        "(needs --distill_teacher)")
+    p.add_argument("--unlabelled_per_batch", default=None, type=int, metavar="U", help="unlabelled frames a step (default: --batch_size_per_gpu)")
+    p.add_argument("--ignore_index", default=None, type=int, metavar="G",
+                   help="label value that takes no part in the training loss (outside the classes; the fused losses only; "
+                        "validation takes its sets as fully labelled)")
+    p.add_argument("--distill_labelled_weight", default=None, type=float, metavar="W",
+                   help="weight of the consistency term on labelled samples (default 1; unlabelled samples have 1; 0: a labelled "
+                        "sample reads none of its teacher maps)")
     # extension: the training loss (default: what each script applies, train.py:427-428 Dice, train_multi_class.py:390-393 soft IoU)
     p.add_argument("--loss", default="dice", choices=sorted(SegEngine.LOSSES),
                    help="training loss; lovasz = segloss/lovasz_loss.py LovaszSoftmax on softmax(out), ce_lovasz = CrossentropyND + that; "
