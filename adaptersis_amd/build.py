@@ -37,9 +37,10 @@ def _hipcc() -> str:
 # (adaptersis_amd/_lib_distill.py, _lib_consist.py, _lib_mix.py, _lib_semi.py), linked against libasis_hip.so for the error plumbing
 # (asis_set_error_ / asis_last_error).  The first two are instantiations of one kernel, csrc/soft_target.h, which neither exports;
 # the third holds the batch-mixing kernels and that kernel's instantiation over a mixed batch; the fourth is the fused loss of
-# loss.hip (csrc/seg_loss_body.h) instantiated with an ignore label.
+# loss.hip (csrc/seg_loss_body.h) instantiated with an ignore label; the fifth (_lib_strong.py) holds the strong student view (colour
+# jitter, greyscale, blur) that follows the augmentation.
 SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",), "libasis_mix.so": ("mix.hip",),
-             "libasis_semi.so": ("semi.hip",)}
+             "libasis_semi.so": ("semi.hip",), "libasis_strong.so": ("strongaug.hip",)}
 
 
 def sources():

@@ -2376,6 +2376,116 @@ def augment(img_u8: torch.Tensor, mask_u8: torch.Tensor, tables: dict):
     return out, mout
 
 
+STRONG_RMAX = 6
+STRONG_TABLES = {"st_ops": (torch.int32, (4,)), "st_fac": (torch.float32, (4,)), "st_flags": (torch.int32, (2,)),
+                 "st_gauss": (torch.float32, (2 * STRONG_RMAX + 1,))}
+
+
+def _strong_args(op: str, x: torch.Tensor, tables: dict, apply, out):
+    """The arguments of ``strong_view`` checked, without a device -> (apply on x's device or None, the host flags strong_any,
+    contrast_any, the largest radius).  Values are read from the host copies (``tables["st_host"]``, as ``TrainAugment.strong_tables``
+    leaves them), from the tables themselves when they live on the CPU, and only for device tables without a host copy through
+    a copy to the host."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{op}: x must be a contiguous float32 tensor [B,3,H,W]")
+    B, _, H, W = (int(v) for v in x.shape)
+    if B < 1 or H < 1 or W < 1 or B * 3 * H * W >= 1 << 31 or B > 65535:
+        raise ValueError(f"{op}: need B, H, W >= 1, B <= 65535 and B*3*H*W < 2^31 (shape {list(x.shape)})")
+    if not isinstance(tables, dict) or set(STRONG_TABLES) - set(tables):
+        raise ValueError(f"{op}: tables must hold {sorted(STRONG_TABLES)}")
+    for name, (dtype, tail) in STRONG_TABLES.items():
+        t = tables[name]
+        if not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != (B,) + tail:
+            raise ValueError(f"{op}: tables[{name!r}] must be a contiguous {dtype} tensor {[B, *tail]}")
+        if t.device != x.device:
+            raise ValueError(f"{op}: tables[{name!r}] is on {t.device}, x on {x.device}")
+    host = tables.get("st_host") or {}
+    h = lambda name: (host[name] if name in host else tables[name].cpu()).numpy()   # small host arrays: numpy is the cheap way to ask
+    codes, flags = h("st_ops"), h("st_flags")
+    if codes.shape != (B, 4) or flags.shape != (B, 2):
+        raise ValueError(f"{op}: the host copies of the tables do not have B={B} rows")
+    if int(codes.min()) < -1 or int(codes.max()) > 3:
+        raise ValueError(f"{op}: operation codes must lie in -1..3 (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none)")
+    has_contrast = (codes == 1).sum(1)
+    if int(has_contrast.max()) > 1:
+        raise ValueError(f"{op}: a sample may hold the contrast operation once")
+    rad = flags[:, 1]
+    if int(rad.min()) < 0 or int(rad.max()) > STRONG_RMAX or int(rad.max()) >= min(H, W):
+        raise ValueError(f"{op}: blur radius must lie in 0..{STRONG_RMAX} and below min(H, W) = {min(H, W)} (reflect border)")
+    on = None
+    if apply is None:
+        apply = tables.get("st_apply")
+        if apply is not None:
+            on = h("st_apply") != 0
+    elif torch.is_tensor(apply):
+        on = apply.cpu().numpy() != 0
+        apply = apply.to(device=x.device, dtype=torch.int32)
+    else:
+        on = torch.tensor([bool(a) for a in apply], dtype=torch.bool)
+        apply = _upload_i32([on.to(torch.int32)], x.device)
+        on = on.numpy()
+    if (on is not None and on.shape != (B,)) or (apply is not None and (tuple(apply.shape) != (B,) or apply.dtype != torch.int32
+                                                                        or not apply.is_contiguous() or apply.device != x.device)):
+        raise ValueError(f"{op}: apply must hold B={B} entries (a contiguous int32 tensor on {x.device}, or a sequence)")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"{op}: out must be a contiguous float32 tensor {list(x.shape)} on {x.device}")
+        n = x.numel() * 4
+        if out.data_ptr() < x.data_ptr() + n and x.data_ptr() < out.data_ptr() + n:
+            raise ValueError(f"{op}: out must not alias x (the op is out of place: the input is the teacher's view)")
+    todo = (codes >= 0).any(1) | (flags != 0).any(1)
+    if on is not None:
+        has_contrast, todo, rad = has_contrast * on, todo & on, rad * on
+    return apply, bool(todo.any()), bool(has_contrast.any()), int(rad.max())
+
+
+def strong_contrast_partials(x: torch.Tensor, tables: dict, apply=None) -> torch.Tensor:
+    """``asis_strong_mean`` alone -> partial float64 [B, nblk]: per sample with a contrast operation the grey sums of its chunks of
+    ``asis_strong_chunk()`` pixels under the operations in front of contrast (rows of other samples are zero); their sum in index
+    order over H*W is the mean ``strong_view`` uses."""
+    from . import _lib_strong
+    op = "strong_contrast_partials"
+    apply, _, _, _ = _strong_args(op, x, tables, apply, None)
+    _dev(x)
+    B, _, H, W = (int(v) for v in x.shape)
+    lib_ = _lib_strong.lib()
+    partial = torch.zeros((B, lib_.asis_strong_nblk(H * W)), device=x.device, dtype=torch.float64)
+    check(lib_.asis_strong_mean(_stream(), x.data_ptr(), tables["st_ops"].data_ptr(), tables["st_fac"].data_ptr(), _p(apply), B, H, W,
+                                partial.data_ptr()), "asis_strong_mean")
+    return partial
+
+
+def strong_view(x: torch.Tensor, tables: dict, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The strong student view (csrc/strongaug.hip, libasis_strong.so) of ``x`` contiguous fp32 [B,3,H,W] in [0,1], the output of
+    ``augment``: per sample colour jitter (brightness, contrast against the sample's grey mean, saturation, hue, in the order of
+    ``st_ops``, each clamped to [0,1]), greyscale, Gaussian blur with a reflect border.  ``tables``: those of
+    ``tools.augment.TrainAugment.strong_tables`` (st_ops int32 [B,4], st_fac fp32 [B,4], st_flags int32 [B,2] = (grey, radius),
+    st_gauss fp32 [B,13], optionally st_apply int32 [B]) on x's device.  ``apply``: per sample, 0 = copied through (default: st_apply
+    of the tables, or every sample).  -> fp32 [B,3,H,W], a fresh buffer or ``out``; never in place, the input survives as the
+    pre-strong (teacher's) view.  A sample without a draw or with apply 0 is copied bit by bit.  At most two launches
+    (``asis_strong_mean`` only with a contrast operation), no host sync, bit-identical from call to call.  When no sample has
+    anything to do the result is ``x`` itself: nothing is launched and the library is not opened."""
+    op = "strong_view"
+    apply, strong, contrast, rmax = _strong_args(op, x, tables, apply, out)
+    if not strong:
+        return x
+    from . import _lib_strong
+    _dev(x)
+    B, _, H, W = (int(v) for v in x.shape)
+    lib_ = _lib_strong.lib()
+    partial = None
+    if contrast:
+        partial = torch.empty((B, lib_.asis_strong_nblk(H * W)), device=x.device, dtype=torch.float64)
+        check(lib_.asis_strong_mean(_stream(), x.data_ptr(), tables["st_ops"].data_ptr(), tables["st_fac"].data_ptr(), _p(apply), B, H,
+                                    W, partial.data_ptr()), "asis_strong_mean")
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib_.asis_strong_view(_stream(), x.data_ptr(), tables["st_ops"].data_ptr(), tables["st_fac"].data_ptr(),
+                                tables["st_flags"].data_ptr(), tables["st_gauss"].data_ptr(), _p(apply), _p(partial), rmax, B, H, W,
+                                out.data_ptr()), "asis_strong_view")
+    return out
+
+
 def nonrigid_map(tables: dict, S: int, return_field: bool = False):
     """The coordinate maps of the non-rigid block (csrc/nonrigid.hip) from the tables of
     ``tools.augment.TrainAugment.nonrigid_tables`` -> int32 [B,S,S,2] = (x, y) source coordinate in 1/32 pixel.

@@ -26,6 +26,14 @@ kernels, whose per-sample flag switches CLAHE off while the tables and / 255 sti
 as published; neither library can be run here, so parity is unpinned as for CLAHE.  Stated deviations: the elastic member's
 ``warpAffine`` + ``remap`` are composed into ONE resample (one interpolation instead of two); its noise is this project's Philox
 stream, not numpy's; the mask is sampled at the rounded QUANTISED coordinate (OpenCV rounds the float map).
+
+Strong view (``strong=dict(...)``; ``csrc/strongaug.hip``, ``ops.strong_view``): the student's view of FixMatch / UniMatch-style
+training, a second stage on the fp32 output of ``ops.augment`` — colour jitter (brightness, contrast, saturation, hue in a drawn
+order, p = 0.8), greyscale (p = 0.2), Gaussian blur (p = 0.5, sigma ~ U(0.1, 2), radius max(1, ceil(3 sigma)) <= 6, reflect
+border).  These are torchvision's tensor semantics (``ColorJitter``, ``RandomGrayscale``, ``gaussian_blur``) restated as published;
+torchvision cannot be run here, so parity is unpinned in the same sense as for CLAHE and the non-rigid block.  Stated deviations:
+the blur radius follows ceil(3 sigma) with a cap of 6 instead of a fixed kernel size, and the blurred value is clamped to [0,1].
+The draws come from a generator of their own, so the base stream is the same with and without the block.
 """
 from __future__ import annotations
 
@@ -130,16 +138,53 @@ def elastic_affine(S: int, pts) -> np.ndarray:
 
 
 def weak_params(params):
-    """The draws ``params`` with the photometric stage neutralised (no CLAHE, identity brightness / contrast / gamma tables) and
-    the geometry kept (crop, flip, rot90, the non-rigid member and its draws): the teacher's view in mean-teacher training."""
-    return [{**p, "clahe": None, "alpha": 1.0, "beta": 0.0, "gamma": None} for p in params]
+    """The draws ``params`` with the photometric stage neutralised (no CLAHE, identity brightness / contrast / gamma tables, no
+    strong view) and the geometry kept (crop, flip, rot90, the non-rigid member and its draws): the teacher's view in mean-teacher
+    training.  Draws without a strong configuration carry no ``strong`` key and gain none."""
+    return [{**p, "clahe": None, "alpha": 1.0, "beta": 0.0, "gamma": None, **({"strong": None} if "strong" in p else {})} for p in params]
+
+
+# ---- strong view: host tables ----------------------------------------------------------------------------------------
+ST_BRIGHTNESS, ST_CONTRAST, ST_SATURATION, ST_HUE = 0, 1, 2, 3
+ST_RMAX = 6       # largest blur radius of asis_strong_view
+ST_SEED = 0x5354524F
+STRONG_DEFAULTS = {"jitter": (0.5, 0.5, 0.5, 0.25), "jitter_p": 0.8, "grey_p": 0.2, "blur_p": 0.5, "sigma": (0.1, 2.0)}
+
+
+def strong_radius(sigma: float) -> int:
+    return min(ST_RMAX, max(1, int(np.ceil(3.0 * float(sigma)))))
+
+
+def strong_gauss(sigma: float, r: int) -> np.ndarray:
+    """weights exp(-i^2 / 2 sigma^2), |i| <= r, normalised to sum 1 in float64 -> fp32 [2 ST_RMAX + 1], centred, zero outside +-r"""
+    i = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 * i * i / (float(sigma) * float(sigma)))
+    out = np.zeros(2 * ST_RMAX + 1, np.float32)
+    out[ST_RMAX - r:ST_RMAX + r + 1] = (w / w.sum()).astype(np.float32)
+    return out
+
+
+def _strong_config(strong) -> dict:
+    if not isinstance(strong, dict) or set(strong) - set(STRONG_DEFAULTS):
+        raise ValueError(f"TrainAugment: strong must be None or a dict with keys out of {sorted(STRONG_DEFAULTS)}")
+    cfg = {**STRONG_DEFAULTS, **strong}
+    jit, sig = tuple(float(v) for v in cfg["jitter"]), tuple(float(v) for v in cfg["sigma"])
+    if len(jit) != 4 or not all(0.0 <= v <= 1.0 for v in jit[:3]) or not 0.0 <= jit[3] <= 0.5:
+        raise ValueError("TrainAugment: strong jitter is (brightness, contrast, saturation, hue) with the first three in [0, 1] "
+                         "and hue in [0, 0.5]")
+    if len(sig) != 2 or not 0.0 < sig[0] <= sig[1]:
+        raise ValueError("TrainAugment: strong sigma is (low, high) with 0 < low <= high")
+    for k in ("jitter_p", "grey_p", "blur_p"):
+        if not 0.0 <= float(cfg[k]) <= 1.0:
+            raise ValueError(f"TrainAugment: strong {k} must be a probability in [0, 1]")
+    return {"jitter": jit, "sigma": sig, "jitter_p": float(cfg["jitter_p"]), "grey_p": float(cfg["grey_p"]), "blur_p": float(cfg["blur_p"])}
 
 
 class TrainAugment:
     def __init__(self, size: int = 588, seed: int = 0, crop_p: float = 0.5, pad_p: float = 1.0, flip_p: float = 0.5,
                  rot_p: float = 0.5, clahe_p: float = 0.8, bc_p: float = 0.8, gamma_p: float = 0.8,
                  min_crop: Optional[int] = None, clahe_clip=(1.0, 4.0), non_rigid_p: float = 0.0,
-                 elastic=(120.0, 6.0, 3.6), grid=(5, 0.3), optical=(2.0, 0.5)):
+                 elastic=(120.0, 6.0, 3.6), grid=(5, 0.3), optical=(2.0, 0.5), strong: Optional[dict] = None):
         if size < 16:
             raise ValueError("TrainAugment: size must be at least 16 (8 x 8 CLAHE tile grid)")
         # A.ElasticTransform(alpha, sigma, alpha_affine), A.GridDistortion(num_steps, distort_limit),
@@ -152,11 +197,14 @@ class TrainAugment:
         self.p_crop = crop_p / (crop_p + pad_p)                                # OneOf normalises its members' p
         self.flip_p, self.rot_p, self.bc_p, self.gamma_p = flip_p, rot_p, bc_p, gamma_p
         self.rng = np.random.RandomState(seed)
+        # the strong view (None: no draw, no key): a generator of its own, so that the base stream does not depend on the block
+        self.strong = None if strong is None else _strong_config(strong)
+        self.strong_rng = None if strong is None else np.random.RandomState((int(seed) ^ ST_SEED) & 0xFFFFFFFF)
 
     # ---- parameter draws (host) -----------------------------------------------------------------------------------
     def draw(self, n: int):
         """-> list of per-sample dicts (crop box or None, flip, rotk, nonrigid: None or the member's draws, clahe, alpha, beta,
-        gamma), drawn in the pipeline's order."""
+        gamma), drawn in the pipeline's order.  With a strong configuration also ``strong``: None, or the draws of that stage."""
         S, r = self.size, self.rng
         out = []
         for _ in range(n):
@@ -181,7 +229,62 @@ class TrainAugment:
                 p["beta"] = 0.0 + r.uniform(-0.2, 0.2)
             if r.random_sample() < self.gamma_p:
                 p["gamma"] = r.uniform(80, 120) / 100.0
+            if self.strong is not None:
+                p["strong"] = self._draw_strong()
             out.append(p)
+        return out
+
+    def _draw_strong(self):
+        """-> None (the sample keeps its pixels) or {"order": the four operation codes in the drawn order or None, "factors": their
+        factors in that order, "grey": bool, "sigma": float or None}"""
+        r, c = self.strong_rng, self.strong
+        d = {"order": None, "factors": None, "grey": False, "sigma": None}
+        if r.random_sample() < c["jitter_p"]:
+            b, ct, s, h = c["jitter"]
+            f = {ST_BRIGHTNESS: r.uniform(1.0 - b, 1.0 + b), ST_CONTRAST: r.uniform(1.0 - ct, 1.0 + ct),
+                 ST_SATURATION: r.uniform(1.0 - s, 1.0 + s), ST_HUE: r.uniform(-h, h)}
+            d["order"] = tuple(int(v) for v in r.permutation(4))
+            d["factors"] = tuple(float(f[o]) for o in d["order"])
+        d["grey"] = bool(r.random_sample() < c["grey_p"])
+        if r.random_sample() < c["blur_p"]:
+            d["sigma"] = float(r.uniform(*c["sigma"]))
+        return d if d["order"] is not None or d["grey"] or d["sigma"] is not None else None
+
+    def strong_tables(self, params, device, apply=None) -> Dict:
+        """The tables of ``ops.strong_view`` for the draws ``params`` (``p.get("strong")`` absent or None = the sample keeps its
+        pixels): st_ops int32 [B,4] (codes in the drawn order, -1 none), st_fac fp32 [B,4], st_flags int32 [B,2] (grey, radius),
+        st_gauss fp32 [B,13] (centred, zero outside +-r), st_apply int32 [B] (``apply``: a sequence of B truth values; default all
+        1), packed on the host and uploaded in ONE non-blocking copy; the host flags strong_any, contrast_any, blur_any (over the
+        samples ``apply`` leaves on) and ``st_host``, the host copies the op checks its values on."""
+        B, G = len(params), 2 * ST_RMAX + 1
+        if apply is not None and len(apply) != B:
+            raise ValueError(f"strong_tables: apply has {len(apply)} entries, the batch has {B} samples")
+        cuda = torch.device(device).type == "cuda"
+        stage = torch.zeros(B * (4 + 4 + 2 + G + 1), dtype=torch.int32, pin_memory=cuda)
+        cut = np.cumsum([0, 4 * B, 4 * B, 2 * B, G * B, B])
+        names, shapes = ("st_ops", "st_fac", "st_flags", "st_gauss", "st_apply"), ((B, 4), (B, 4), (B, 2), (B, G), (B,))
+        part = lambda t, k: t[cut[k]:cut[k + 1]].view(torch.float32 if names[k] in ("st_fac", "st_gauss") else torch.int32).view(shapes[k])
+        host = {n: part(stage, k) for k, n in enumerate(names)}
+        ops_, fac, flags, gauss, app = (host[n].numpy() for n in names)
+        ops_[:] = -1
+        app[:] = 1 if apply is None else [int(bool(a)) for a in apply]
+        for b, p in enumerate(params):
+            st = p.get("strong")
+            if st is None:
+                continue
+            if st["order"] is not None:
+                ops_[b], fac[b] = st["order"], st["factors"]
+            if st["sigma"] is not None:
+                r = strong_radius(st["sigma"])
+                flags[b, 1], gauss[b] = r, strong_gauss(st["sigma"], r)
+            flags[b, 0] = int(st["grey"])
+        on = app != 0
+        dev = stage.to(device, non_blocking=True)
+        out = {n: part(dev, k) for k, n in enumerate(names)}
+        out["st_host"] = host
+        out["contrast_any"] = bool(((ops_ == ST_CONTRAST).any(1) & on).any())
+        out["blur_any"] = bool(((flags[:, 1] > 0) & on).any())
+        out["strong_any"] = bool((((ops_ >= 0).any(1) | (flags != 0).any(1)) & on).any())
         return out
 
     def _draw_nonrigid(self):
@@ -261,10 +364,17 @@ class TrainAugment:
             out.update(self.nonrigid_tables(params, device))
         return out
 
-    def __call__(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, params=None, return_params: bool = False):
+    def __call__(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, params=None, return_params: bool = False,
+                 return_strong: bool = False, strong_apply=None):
         """uint8 [B,S,S,3] + uint8 [B,S,S] on the device -> (fp32 [B,3,S,S] in [0,1], int64 [B,S,S]); ``return_params`` appends the
-        parameters used (the ones drawn when ``params`` is None)."""
+        parameters used (the ones drawn when ``params`` is None).  Parameters that carry strong draws (a strong configuration, or
+        ``params`` with ``strong`` entries) make the image the strong view (``ops.strong_view``, out of place; ``strong_apply``: the
+        samples it is applied to); ``return_strong`` then appends the pre-strong tensor last (the image itself without a draw)."""
         if params is None:
             params = self.draw(img_u8.shape[0])
-        out = ops.augment(img_u8, mask_u8, self.tables(params, img_u8.device))
-        return (*out, params) if return_params else out
+        x, m = ops.augment(img_u8, mask_u8, self.tables(params, img_u8.device))
+        out, pre = (x, m), x
+        if any(p.get("strong") is not None for p in params):
+            out = (ops.strong_view(x, self.strong_tables(params, img_u8.device, strong_apply)), m)
+        out = (*out, params) if return_params else out
+        return (*out, pre) if return_strong else out

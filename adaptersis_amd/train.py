@@ -60,7 +60,10 @@ _AUGMENTERS = {}
 _IDENTITY = {"crop": None, "flip": False, "rotk": 0, "alpha": 1.0, "beta": 0.0, "gamma": None}
 
 
-def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0, weak: bool = False):
+_LAST_STRONG = {"applied": None}   # the share of the last strong batch's samples with a strong draw, counted on the host
+
+
+def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0, weak: bool = False, strong=None, strong_apply=None):
     """Batch from the loader -> (float [B,3,S,S] in [0,1], long [B,S,S]) on the device.  uint8 HWC batches (``tools.dataset.Robomis``
     without a host transform) go through the GPU augmentation pipeline (`train.py:139-163`) when training, and through the same
     kernel with identity parameters (= `/255`, `tools/dataset.py:159`; the reference's val transform is a no-op Resize to the
@@ -68,24 +71,44 @@ def _to_device_batch(inp, target, train: bool, non_rigid_p: float = 0.0, weak: b
     resized on the device first (``ops.frame_resize``, PIL-exact), then takes the same uint8 path.
     ``weak`` (training batches, --distill_weak): -> (inp, target, teacher_inp), the third the same frames under the same drawn
     geometry without the photometric stage (``tools.augment.weak_params``: a second ``ops.augment`` call, no further draw); a batch
-    that does not go through the GPU augmentation has no photometric stage, its ``teacher_inp`` is ``inp`` itself."""
+    that does not go through the GPU augmentation has no photometric stage, its ``teacher_inp`` is ``inp`` itself.
+    ``strong`` (training batches, --aug_strong: the ``strong`` configuration of ``TrainAugment``): -> (inp, target, teacher_inp) as
+    well; ``inp`` is the strong view (``ops.strong_view``, out of place) of the samples ``strong_apply`` names (a sequence of truth
+    values; default all), ``teacher_inp`` the tensor in front of it, or with ``weak`` the geometry-only view as above: the strong
+    stage never reaches a teacher.  The strong draws come from a generator of their own: crop, flip, CLAHE and the tables are those
+    of the call without ``strong``.  A batch that does not go through the GPU augmentation is left alone, as for ``weak``."""
     from .tools.dataset import FrameBatch
     if isinstance(inp, FrameBatch):
         inp, target = _resize_frames(inp)
     inp, target = inp.cuda(non_blocking=True), target.cuda(non_blocking=True)
+    strong = strong if train else None
     if inp.dtype != torch.uint8:
-        return (inp, target, inp) if weak else (inp, target)
+        if strong is not None:
+            _LAST_STRONG["applied"] = 0.0
+        return (inp, target, inp) if weak or strong is not None else (inp, target)
     from .tools.augment import TrainAugment
     S = inp.shape[1]
     aug = _AUGMENTERS.get(S)
-    if aug is None or (train and aug.non_rigid_p != non_rigid_p):     # --aug_non_rigid: training batches only
-        aug = _AUGMENTERS[S] = TrainAugment(size=S, seed=1000 + utils.get_rank(), non_rigid_p=non_rigid_p if train else 0.0)
+    if strong is not None:
+        from .tools.augment import _strong_config
+        strong = _strong_config(strong)
+    # --aug_non_rigid, --aug_strong: training batches only
+    if aug is None or (train and (aug.non_rigid_p != non_rigid_p or aug.strong != strong)):
+        aug = _AUGMENTERS[S] = TrainAugment(size=S, seed=1000 + utils.get_rank(), non_rigid_p=non_rigid_p if train else 0.0,
+                                            strong=strong)
     img, msk = inp.contiguous(), target.to(torch.uint8).contiguous()
-    if not weak:
+    if not weak and strong is None:
         return aug(img, msk, None if train else [dict(_IDENTITY) for _ in range(inp.shape[0])])
     from .tools.augment import weak_params
-    x, y, params = aug(img, msk, None, return_params=True)
-    return x, y, aug(img, msk, weak_params(params))[0]
+    if strong is None:
+        x, y, params = aug(img, msk, None, return_params=True)
+        return x, y, aug(img, msk, weak_params(params))[0]
+    if strong_apply is not None and len(strong_apply) != inp.shape[0]:
+        raise ValueError(f"_to_device_batch: strong_apply has {len(strong_apply)} entries, the batch has {inp.shape[0]} samples")
+    x, y, params, pre = aug(img, msk, None, return_params=True, return_strong=True, strong_apply=strong_apply)
+    drawn = [p.get("strong") is not None and (strong_apply is None or bool(strong_apply[b])) for b, p in enumerate(params)]
+    _LAST_STRONG["applied"] = sum(drawn) / max(1, len(drawn))
+    return x, y, (aug(img, msk, weak_params(params))[0] if weak else pre)
 
 
 def _append_unlabelled(inp, target, frames, masks):
@@ -341,6 +364,47 @@ def _mix_engine_args(args) -> dict:
             "mix_background": bool(getattr(args, "mix_background", False))}
 
 
+STRONG_FLAGS = ("aug_strong_jitter", "aug_strong_grey", "aug_strong_blur")
+
+
+def check_strong_args(args) -> Optional[str]:
+    """What is wrong with the combination of the strong-view flags (--aug_strong, --aug_strong_*), or None.  Needs no device and no
+    process group."""
+    on = getattr(args, "aug_strong_on", None) or "all"
+    if not getattr(args, "aug_strong", False):
+        given = [f for f in STRONG_FLAGS if getattr(args, f, None) is not None]
+        if on != "all":
+            given.append("aug_strong_on")
+        return f"--{given[0]} needs --aug_strong" if given else None
+    jit = getattr(args, "aug_strong_jitter", None)
+    if jit is not None:
+        if len(jit) != 4 or not all(0.0 <= float(v) <= 1.0 for v in jit[:3]) or not 0.0 <= float(jit[3]) <= 0.5:
+            return "--aug_strong_jitter takes B C S H: brightness, contrast and saturation in [0, 1], hue in [0, 0.5]"
+    for f in ("aug_strong_grey", "aug_strong_blur"):
+        v = getattr(args, f, None)
+        if v is not None and not 0.0 <= float(v) <= 1.0:
+            return f"--{f} must be a probability in [0, 1]"
+    if on not in ("all", "unlabelled"):
+        return "--aug_strong_on must be all or unlabelled"
+    if on == "unlabelled" and getattr(args, "unlabelled_path", None) is None:
+        return "--aug_strong_on unlabelled needs --unlabelled_path: without it no sample would get the strong view"
+    return None
+
+
+def _strong_config(args) -> Optional[dict]:
+    """The strong-view flags as the ``strong`` argument of ``tools.augment.TrainAugment``; None without --aug_strong."""
+    if not getattr(args, "aug_strong", False):
+        return None
+    out = {}
+    if getattr(args, "aug_strong_jitter", None) is not None:
+        out["jitter"] = tuple(float(v) for v in args.aug_strong_jitter)
+    if getattr(args, "aug_strong_grey", None) is not None:
+        out["grey_p"] = float(args.aug_strong_grey)
+    if getattr(args, "aug_strong_blur", None) is not None:
+        out["blur_p"] = float(args.aug_strong_blur)
+    return out
+
+
 class _MixEntry:
     """the ``mix`` entry of a checkpoint as ``restart_from_checkpoint`` sees it: the step the next draw is seeded with"""
 
@@ -506,7 +570,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     non_rigid_p = float(getattr(args, "aug_non_rigid", 0.0))
     if not 0.0 <= non_rigid_p <= 1.0:
         raise ValueError("--aug_non_rigid must be a probability in [0, 1]")
-    bad = check_backbone_args(args) or check_distill_args(args) or check_mix_args(args) or check_semi_args(args, loss)
+    bad = (check_backbone_args(args) or check_distill_args(args) or check_mix_args(args) or check_semi_args(args, loss)
+           or check_strong_args(args))
     if bad:
         raise ValueError(bad)
     utils.init_distributed_mode(args)
@@ -540,6 +605,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
     engine.distill_weak = bool(getattr(args, "distill_weak", False))
     engine.mix_rank = utils.get_rank()      # --mix: every rank draws its own tables
     engine.unlabelled = None                # --unlabelled_path: read by train(), like aug_non_rigid
+    engine.aug_strong = _strong_config(args)   # --aug_strong: None, or the strong configuration of the augmenter; read by train()
+    engine.aug_strong_on = getattr(args, "aug_strong_on", None) or "all"
 
     dataset_train, dataset_val, collate = open_datasets(args)
     workers = args.num_workers if collate is not None else 0      # PNG decode runs in loader workers; tensors in memory do not need any
@@ -680,14 +747,21 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
     ragged = parallel.collectives_on() and not isinstance(getattr(loader, "sampler", None),
                                                           torch.utils.data.distributed.DistributedSampler)
     stream = getattr(engine, "unlabelled", None)
+    strong = getattr(engine, "aug_strong", None)
     for (inp, target, idx) in metric_logger.log_every(loader, 20, "Epoch: [{}]".format(epoch)):
         if ragged:
             parallel.set_batch_ratio(int(inp.shape[0]))
         labelled = None
         if stream is not None:   # the labelled batch followed by the unlabelled frames, through the augmentation in one call
             inp, target, labelled = _append_unlabelled(inp, target, *stream.next())
+        skw = {}
+        if strong is not None:   # --aug_strong: the student's view; --aug_strong_on unlabelled: of the unlabelled frames alone
+            only_unl = getattr(engine, "aug_strong_on", "all") == "unlabelled" and labelled is not None
+            skw = {"strong": strong, "strong_apply": [not l for l in labelled] if only_unl else None}
         batch = _to_device_batch(inp, target, train=True, non_rigid_p=getattr(engine, "aug_non_rigid", 0.0),
-                                 weak=engine.teacher is not None and getattr(engine, "distill_weak", False))
+                                 weak=engine.teacher is not None and getattr(engine, "distill_weak", False), **skw)
+        if strong is not None and engine.teacher is None:   # nobody takes the view in front of the strong stage
+            batch = batch[:2]
         if labelled is None:
             loss = engine.train_step(batch[0], batch[1], None, *batch[2:])
         else:
@@ -701,6 +775,8 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
         if engine.mix_sampler is not None:  # the share of the batch's pixels that came from another sample
             pasted = engine.last_mix_pasted
             metric_logger.update(mix_pasted=0.0 if pasted is None else int(pasted.sum()) / batch[1].numel())
+        if strong is not None:              # the share of the samples with a strong draw
+            metric_logger.update(strong_applied=_LAST_STRONG["applied"])
         metric_logger.update(lr=optimizer.param_groups[0]["lr"])
         if with_norm:
             metric_logger.update(grad_norm=optimizer.last_grad_norm)
@@ -766,7 +842,7 @@ class _ArgumentParser(argparse.ArgumentParser):
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
-        bad = check_backbone_args(ns) or check_distill_args(ns) or check_mix_args(ns) or check_semi_args(ns)
+        bad = check_backbone_args(ns) or check_distill_args(ns) or check_mix_args(ns) or check_semi_args(ns) or check_strong_args(ns)
         if bad:
             self.error(bad)
         return ns, rest
@@ -879,6 +955,17 @@ def get_args_parser():
     p.add_argument("--aug_non_rigid", default=0.0, type=float,
                    help="probability of the non-rigid block OneOf([ElasticTransform, GridDistortion, OpticalDistortion]) of the "
                         "GPU augmentation (uint8 datasets, training batches only); 0 = the reference as it stands")
+    # extension: the strong student view of FixMatch / UniMatch-style training (ops.strong_view), after the augmentation
+    p.add_argument("--aug_strong", action="store_true",
+                   help="the student trains on a strong view: colour jitter (p 0.8), greyscale (p 0.2), Gaussian blur (p 0.5) on the "
+                        "device after the augmentation (uint8 datasets, training batches only); a teacher never sees it")
+    p.add_argument("--aug_strong_jitter", default=None, type=float, nargs=4, metavar=("B", "C", "S", "H"),
+                   help="amplitudes of brightness, contrast, saturation (factors in 1 +- a; each in [0, 1]) and hue (shift in +- H; "
+                        "in [0, 0.5]); default 0.5 0.5 0.5 0.25")
+    p.add_argument("--aug_strong_grey", default=None, type=float, metavar="P", help="probability of greyscale (default 0.2)")
+    p.add_argument("--aug_strong_blur", default=None, type=float, metavar="P", help="probability of the Gaussian blur (default 0.5)")
+    p.add_argument("--aug_strong_on", default="all", choices=("all", "unlabelled"),
+                   help="the samples that get the strong view: all, or the unlabelled frames alone (needs --unlabelled_path)")
     return p
 
 
