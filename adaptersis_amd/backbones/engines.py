@@ -18,6 +18,7 @@ Everything is a HIP kernel from libasis_hip.so; torch provides device memory, st
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -231,7 +232,8 @@ class SegEngine(nn.Module):
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, teacher=None, distill_weight: float = 1.0,
                  distill_temperature: float = 1.0, distill_threshold: Optional[float] = None, distill_rampup: int = 0,
                  distill_flip: bool = False, mix: Optional[str] = None, mix_p: float = 1.0, mix_seed: int = 0,
-                 mix_background: bool = False, ignore_index: Optional[int] = None, distill_labelled_weight: float = 1.0):
+                 mix_background: bool = False, ignore_index: Optional[int] = None, distill_labelled_weight: float = 1.0,
+                 distill_class_thresholds=None, distill_adaptive_momentum: float = 0.999):
         """``seg_decoder``: ``FeatureDecoder`` -> the `train.py` flow; ``DecoderMLA`` -> the `train_mla.py` flow
         (block -> CACNN -> CAViT order, the four adapter-stream maps feed the MLA head, `blocks[-2]` is evaluated
         twice and `blocks[-1]` never: `train_mla.py:318,340`).  ``loss``: a key of ``SegEngine.LOSSES``.
@@ -295,7 +297,15 @@ class SegEngine(nn.Module):
         where ``ignore_index`` is None) on the device, the hard loss leaves them out, and the consistency term weighs them 1 and
         the labelled samples ``distill_labelled_weight`` (0: a labelled sample reads none of its teacher maps).  With ``mix`` the
         donors are drawn inside the two groups, and ClassMix takes the classes of an unlabelled donor from the teacher's
-        prediction (``ops.predict_mask_views`` of its maps)."""
+        prediction (``ops.predict_mask_views`` of its maps).
+
+        ``distill_class_thresholds`` (default None: nothing is allocated, opened or launched; it needs a ``teacher`` and excludes
+        ``distill_threshold``): a confidence threshold per class for the consistency term (``ops.consistency_loss(class_threshold=)``,
+        csrc/adapt.hip).  A list of ``num_classes`` finite values: fixed thresholds.  "adaptive": self-adaptive thresholding
+        (``adaptive_threshold.AdaptiveThreshold`` with ``distill_adaptive_momentum``, as ``self.adaptive``): between the teacher's
+        prediction and the student's forward every ``train_step`` takes the statistics of the teacher's unmixed maps over the
+        samples the consistency term weighs above 0, sums them over the ranks and updates the thresholds, so the batch takes part
+        in its own thresholds (``taps``: ``kd_class_thr``, ``kd_conf_sums``)."""
         super().__init__()
         if grad_compress is None:   # default since round 5: bf16 transport for the 1.2 GB backbone bucket (ASIS_GRAD_COMPRESS=none: fp32)
             grad_compress = os.environ.get("ASIS_GRAD_COMPRESS", "bf16").lower()
@@ -437,6 +447,26 @@ class SegEngine(nn.Module):
         self.distill_rampup, self.distill_flip = int(distill_rampup), bool(distill_flip)
         self.distill_step = 0
         self.last_loss_kd = self.last_kd_kept = None
+        self.adaptive = self.class_thresholds = None
+        if distill_class_thresholds is not None:
+            if teacher is None:
+                raise ValueError("distill_class_thresholds gates the consistency term: it needs a teacher")
+            if distill_threshold is not None:
+                raise ValueError("distill_class_thresholds and distill_threshold exclude each other")
+            dev = self.bucket.grad.device
+            if isinstance(distill_class_thresholds, str):
+                if distill_class_thresholds != "adaptive":
+                    raise ValueError("distill_class_thresholds must be None, 'adaptive' or a list of num_classes thresholds")
+                from ..adaptive_threshold import AdaptiveThreshold
+                self.adaptive = AdaptiveThreshold(num_classes, distill_adaptive_momentum, dev, process_group)
+                self.class_thresholds = self.adaptive.thresholds
+            else:
+                vals = [float(v) for v in distill_class_thresholds]
+                if len(vals) != num_classes or not all(math.isfinite(v) for v in vals):
+                    raise ValueError(f"distill_class_thresholds must hold {num_classes} finite values, one per class")
+                if not 1 <= num_classes <= ops.ADAPT_MAX_CLASSES:
+                    raise ValueError(f"distill_class_thresholds: num_classes={num_classes} must be in 1..{ops.ADAPT_MAX_CLASSES}")
+                self.class_thresholds = torch.tensor(vals, dtype=torch.float32).to(dev)
         self.mix_sampler = None
         if mix is not None:
             from ..tools.mix import MixSampler
@@ -510,11 +540,15 @@ class SegEngine(nn.Module):
         scratch = _loss_scratch(self, "_consist_scratch", ops.consistency_scratch_bytes(target.numel()), logits.device)
         kd, kept, _ = ops.consistency_loss(logits, maps, target, flips=flips, temperature=self.distill_temperature,
                                            threshold=self.distill_threshold, sample_weight=sample_weight, grad_scale=S * lam, dz=dz,
-                                           scratch=scratch, mix=mix)
+                                           scratch=scratch, mix=mix,
+                                           **({} if self.class_thresholds is None else {"class_threshold": self.class_thresholds}))
         self.last_loss_kd, self.last_kd_kept = kd, kept
         total = hard + lam * kd
         if taps is not None:
             taps.update(loss_hard=hard, loss_kd=kd, kd_kept=kept, teacher_logits=maps, distill_scale=lam)
+            if self.class_thresholds is not None:
+                taps.update(kd_class_thr=self.class_thresholds.clone(),
+                            kd_conf_sums=None if self.adaptive is None else self.adaptive.sums.clone())
         return total
 
     def _ema_modules(self) -> Dict[str, nn.Module]:
@@ -885,6 +919,8 @@ class SegEngine(nn.Module):
             raise ValueError(f"loss {self.loss_kind!r} has no ignore label: an unlabelled sample needs one of {self.IGNORE_LOSSES}")
         if self.teacher is not None:   # before the student's forward: the teacher's activations are gone when the student's are saved
             tmaps, tflips = self._teacher_maps(inp if teacher_inp is None else teacher_inp)
+            if self.adaptive is not None:   # the batch takes part in its own thresholds: before the student's loss reads them
+                self.adaptive.update(tmaps, tflips, target, self.distill_temperature, sw)
         elif teacher_inp is not None:
             raise ValueError("train_step: teacher_inp without a teacher")
         mixed = None

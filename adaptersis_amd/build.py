@@ -38,9 +38,10 @@ def _hipcc() -> str:
 # (asis_set_error_ / asis_last_error).  The first two are instantiations of one kernel, csrc/soft_target.h, which neither exports;
 # the third holds the batch-mixing kernels and that kernel's instantiation over a mixed batch; the fourth is the fused loss of
 # loss.hip (csrc/seg_loss_body.h) instantiated with an ignore label; the fifth (_lib_strong.py) holds the strong student view (colour
-# jitter, greyscale, blur) that follows the augmentation.
+# jitter, greyscale, blur) that follows the augmentation; the sixth (_lib_adapt.py) is that kernel again with a threshold per
+# class, with the statistics of the teacher's maps and the update of the thresholds from them.
 SIDE_LIBS = {"libasis_distill.so": ("distill.hip",), "libasis_consist.so": ("consist.hip",), "libasis_mix.so": ("mix.hip",),
-             "libasis_semi.so": ("semi.hip",), "libasis_strong.so": ("strongaug.hip",)}
+             "libasis_semi.so": ("semi.hip",), "libasis_strong.so": ("strongaug.hip",), "libasis_adapt.so": ("adapt.hip",)}
 
 
 def sources():
@@ -58,7 +59,9 @@ def _deps_mtime() -> float:
 # per-file additions to FLAGS
 # attention.hip: beside MFMAs a packed f32 op costs several single ones (MI355X_MICROARCH.md): keep the softmax arithmetic of the
 # folded kernel unpacked
-FILE_FLAGS = {"attention.hip": ("-fno-slp-vectorize",), "attn_bwd_pipe.hip": ("-fno-slp-vectorize",)}
+# adapt.hip: the registers and scratch of its kernels are on record; --verbose prints the remarks
+FILE_FLAGS = {"attention.hip": ("-fno-slp-vectorize",), "attn_bwd_pipe.hip": ("-fno-slp-vectorize",),
+              "adapt.hip": ("-Rpass-analysis=kernel-resource-usage",)}
 
 
 def _compile(src: str, verbose: bool) -> str:

@@ -29,19 +29,35 @@ struct StViews {
 
 // every pixel of every sample takes part with weight 1: one partial per workgroup
 struct NoGate {
-  static constexpr bool on = false, mix = false;
+  static constexpr bool on = false, mix = false, cls = false;
 };
 // a pixel takes part where max_c q_c >= threshold, times sample_weight[b] (NULL: 1): two partials per workgroup, loss and kept
 struct Gate {
-  static constexpr bool on = true, mix = false;
+  static constexpr bool on = true, mix = false, cls = false;
   float threshold;
   const float* sample_weight;
 };
 // Gate over a mixed batch (mix.hip): where sel[i] != 0 every teacher map of pixel i is read from sample donor[b], at the same
 // (y, x); the student, the weight and dz are sample b's.  A donor outside 0..B-1 is read as b: it is never an address.
 struct MixGate {
-  static constexpr bool on = true, mix = true;
+  static constexpr bool on = true, mix = true, cls = false;
   float threshold;
+  const float* sample_weight;
+  const uint8_t* sel;
+  const int* donor;
+  int B;
+};
+// Gate and MixGate with a threshold per class (adapt.hip): a pixel takes part where conf >= class_threshold[a], a the lowest
+// index of the largest q_c; class_threshold is fp32 [C] on the device.  The table is read inside the unrolled max loop, at
+// compile-time indices (uniform addresses), never at the per-lane arg-max.
+struct ClassGate {
+  static constexpr bool on = true, mix = false, cls = true;
+  const float* class_threshold;
+  const float* sample_weight;
+};
+struct MixClassGate {
+  static constexpr bool on = true, mix = true, cls = true;
+  const float* class_threshold;
   const float* sample_weight;
   const uint8_t* sel;
   const int* donor;
@@ -91,7 +107,7 @@ __device__ __forceinline__ void zero_row(float* __restrict__ out, int C, int vec
   }
 }
 
-// CB >= C the unrolled class count; EXACT: C == CB (no per-class branch); G: NoGate or Gate.  The order of the statements is part
+// CB >= C the unrolled class count; EXACT: C == CB (no per-class branch); G: a gate type above.  The order of the statements is part
 // of the kernel: with `tiny` in a loop of its own after the gate, or the store of a kept row behind a function, the ungated
 // 9..16-class kernels spill scalar registers or take more vector registers than distill.hip's always did.
 template <int CB, bool EXACT, typename G>
@@ -165,16 +181,24 @@ __global__ __launch_bounds__(RX_THREADS) void st_kernel(const float* __restrict_
       }
       bool tiny = false;
       float conf = 0.f;
+      [[maybe_unused]] float thr = 0.f;
+      if constexpr (G::cls) thr = gate.class_threshold[0];  // no q_c above 0 (a row of NaNs): class 0's, as the scalar gate's 0
 #pragma unroll
       for (int c = 0; c < CB; ++c)
         if (c < C) {
           // a true division: times a rounded 1/V every q_c is off by the same factor, and the loss by T^2 times that
           if (vs.V > 1) q[c] = __fdiv_rn(q[c], (float)vs.V);
           tiny |= q[c] > 0.f && p[c] < ST_TINY;
-          if constexpr (G::on) conf = fmaxf(conf, q[c]);
+          if constexpr (G::cls) {
+            if (q[c] > conf) {  // strictly: the lowest index wins a tie
+              conf = q[c];
+              thr = gate.class_threshold[c];
+            }
+          } else if constexpr (G::on) conf = fmaxf(conf, q[c]);
         }
       if constexpr (G::on) {
-        if (!(conf >= gate.threshold)) {  // the teacher is unsure here
+        if constexpr (!G::cls) thr = gate.threshold;
+        if (!(conf >= thr)) {  // the teacher is unsure here
           if (!accumulate) zero_row<CB>(dz + i * C, C, vec);
           continue;
         }
@@ -274,7 +298,8 @@ int st_loss(const char* op, G gate, void* stream, const float* logits, int B, in
   ASIS_REQUIRE(C >= 1 && C <= MAXC, "%s: C=%d must be in 1..%d", op, C, MAXC);
   ASIS_REQUIRE(B >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "%s: non-positive size B=%d h=%d w=%d H=%d W=%d", op, B, h, w, H, W);
   ASIS_REQUIRE(temperature > 0.f, "%s: temperature=%g must be > 0", op, (double)temperature);
-  if constexpr (G::on)
+  if constexpr (G::cls) ASIS_REQUIRE(gate.class_threshold, "%s: null pointer (class_threshold)", op);
+  else if constexpr (G::on)
     ASIS_REQUIRE(gate.threshold <= 1.f, "%s: threshold=%g must be <= 1 (<= 0 keeps every pixel)", op, (double)gate.threshold);
   if constexpr (G::mix) ASIS_REQUIRE(gate.sel && gate.donor, "%s: null pointer (sel, donor)", op);
   const int64_t N = (int64_t)B * H * W;

@@ -1866,7 +1866,8 @@ def consistency_scratch_bytes(n_pixels: int) -> int:
 
 def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,
                      threshold: Optional[float] = None, sample_weight: Optional[torch.Tensor] = None, grad_scale: float = 1.0,
-                     dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, mix=None):
+                     dz: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None, mix=None,
+                     class_threshold: Optional[torch.Tensor] = None):
     """The consistency term of teacher-student training in one pass (csrc/consist.hip, libasis_consist.so): ``distill_loss`` with a
     per-pixel confidence gate, a per-sample weight and the count of the pixels the gate let through.  ``logits``,
     ``teacher_logits``, ``size_or_target``, ``flips``, ``temperature`` as there.  ``threshold`` (None or <= 0: every pixel is
@@ -1882,8 +1883,17 @@ def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, fl
     ``mix_batch`` (csrc/mix.hip).  ``sel`` contiguous uint8 [B,H,W] on the logits' device; ``donor`` a host int32 tensor or a
     sequence of B samples in 0..B-1 (checked here, on the host).  For pixel i of sample b every teacher map is read from sample
     donor[b] where sel[i] is set and from b elsewhere, at the same (y, x) and through the same flips; the student, the weight, the
-    gate (on the confidence of the mixed q), kept, N and dz are as above."""
+    gate (on the confidence of the mixed q), kept, N and dz are as above.
+    ``class_threshold`` (default None: the call above, libasis_adapt.so is not opened; not together with ``threshold``): a contiguous
+    fp32 [C] tensor on the logits' device, one threshold per class (csrc/adapt.hip).  A pixel takes part where conf >=
+    class_threshold[a], a = the class that holds conf (the lowest index among equal values); an entry <= 0 keeps every pixel of
+    its class, one above 1 drops them all.  With or without ``mix``; a tensor filled with t gives the bits of ``threshold=t``."""
     op = "consistency_loss"
+    if class_threshold is not None and threshold is not None:
+        raise ValueError(f"{op}: threshold and class_threshold exclude each other")
+    if class_threshold is not None and (not torch.is_tensor(class_threshold) or class_threshold.dtype != torch.float32
+                                        or class_threshold.dim() != 1 or not class_threshold.is_contiguous()):
+        raise ValueError(f"{op}: class_threshold must be a contiguous float32 tensor [C]")
     B, h, w, V, H, W, Cc, dev, ptrs, hs, ws, fl = _distill_args(op, logits, teacher_logits, size_or_target, flips, temperature, dz,
                                                                 scratch)
     thr = 0.0 if threshold is None else float(threshold)
@@ -1894,12 +1904,26 @@ def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, fl
         if sample_weight.dtype != torch.float32 or not sample_weight.is_contiguous() or tuple(sample_weight.shape) != (B,) \
                 or sample_weight.device != dev:
             raise ValueError(f"{op}: sample_weight must be a contiguous float32 tensor [B={B}] on {dev}")
+    gate = thr
+    if class_threshold is not None:
+        _dev(class_threshold)
+        if tuple(class_threshold.shape) != (Cc,) or class_threshold.device != dev:
+            raise ValueError(f"{op}: class_threshold must be a contiguous float32 tensor [C={Cc}] on {dev}")
+        gate = class_threshold.data_ptr()
     if mix is None:
-        from . import _lib_consist as binding
-        nblk, entry, gather = "asis_consist_nblk", "asis_consist_loss", ()
+        if class_threshold is None:
+            from . import _lib_consist as binding
+            nblk, entry, gather = "asis_consist_nblk", "asis_consist_loss", ()
+        else:
+            from . import _lib_adapt as binding
+            nblk, entry, gather = "asis_adapt_nblk", "asis_adapt_consist_loss", ()
     else:
-        from . import _lib_mix as binding
-        nblk, entry = "asis_mix_consist_nblk", "asis_mix_consist_loss"
+        if class_threshold is None:
+            from . import _lib_mix as binding
+            nblk, entry = "asis_mix_consist_nblk", "asis_mix_consist_loss"
+        else:
+            from . import _lib_adapt as binding
+            nblk, entry = "asis_adapt_nblk", "asis_adapt_mix_consist_loss"
         sel, donor = _mix_gate_args(op, mix, B, H, W, dev)
         gather = (sel.data_ptr(), donor.data_ptr())
     N, scratch, dz, accumulate = _pixel_loss_buffers(op, logits, H, W, lambda n, c: _soft_scratch_bytes(binding, nblk, n, 2), dz,
@@ -1908,10 +1932,96 @@ def consistency_loss(logits: torch.Tensor, teacher_logits, size_or_target, *, fl
         raise ValueError(f"{op}: scratch must be 8-byte aligned")
     loss = torch.empty((1,), device=dev, dtype=torch.float32)
     kept = torch.empty((1,), device=dev, dtype=torch.int32)
-    check(getattr(binding.lib(), entry)(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature), thr,
+    check(getattr(binding.lib(), entry)(_stream(), logits.data_ptr(), B, h, w, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature), gate,
                                         _p(sample_weight), *gather, float(grad_scale), int(accumulate), scratch.data_ptr(),
                                         loss.data_ptr(), kept.data_ptr(), dz.data_ptr()), entry)
     return loss, kept, dz
+
+
+# --------------------------------------------------------------------------------------------
+# class-adaptive thresholds of the consistency term (csrc/adapt.hip, libasis_adapt.so)
+# --------------------------------------------------------------------------------------------
+ADAPT_MAX_CLASSES = 16
+
+
+def confidence_stats_scratch_bytes(n_pixels: int) -> int:
+    """bytes of caller-owned scratch ``asis_adapt_stats`` needs for ``n_pixels`` = B*H*W at any class count: C + 2 <= 18 doubles
+    per workgroup (needs no GPU)."""
+    from . import _lib_adapt
+    return _soft_scratch_bytes(_lib_adapt, "asis_adapt_stats_nblk", n_pixels, ADAPT_MAX_CLASSES + 2)
+
+
+def confidence_stats(teacher_logits, size_or_target, *, flips=None, temperature: float = 1.0,
+                     sample_weight: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What the adaptive thresholds follow (csrc/adapt.hip, libasis_adapt.so): over the native pixels of the samples with
+    ``sample_weight[b]`` > 0 (None: every sample; each pixel counts 1 whatever the weight's size), with q the teacher's mean
+    distribution as ``consistency_loss`` forms it from ``teacher_logits``, ``size_or_target``, ``flips``, ``temperature``:
+    -> float64 [C + 2] on the device = S_0..S_{C-1} (S_c = sum_i q_i[c]), S_conf = sum_i max_c q_i[c], cnt = the pixels counted.
+    A sample of weight 0 reads none of its maps.  ``out``: a contiguous float64 [C + 2] tensor to write (and return); ``scratch``: a
+    uint8 buffer of at least ``confidence_stats_scratch_bytes(B*H*W)``, 8-byte aligned (default: a fresh one).  No host sync, no
+    atomics: bit-identical from call to call."""
+    import ctypes
+    from . import _lib_adapt
+    op = "confidence_stats"
+    maps = [teacher_logits] if torch.is_tensor(teacher_logits) else teacher_logits
+    V, B, Cc, dev, ptrs, hs, ws = _predict_maps(op, "views", DISTILL_MAX_VIEWS, maps)
+    if not 1 <= Cc <= ADAPT_MAX_CLASSES:
+        raise ValueError(f"{op}: C={Cc} must be in 1..{ADAPT_MAX_CLASSES}")
+    flips = [False] * V if flips is None else [bool(f) for f in flips]
+    if len(flips) != V:
+        raise ValueError(f"{op}: flips has {len(flips)} entries for {V} teacher maps")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"{op}: temperature={temperature} must be > 0")
+    if torch.is_tensor(size_or_target):
+        size = tuple(size_or_target.shape[-2:])
+    else:
+        size = (size_or_target, size_or_target) if isinstance(size_or_target, int) else tuple(size_or_target)
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError(f"{op}: size must be a positive int, (H, W) or a tensor [..., H, W], got {size_or_target!r}")
+    H, W = int(size[0]), int(size[1])
+    if sample_weight is not None and (not torch.is_tensor(sample_weight) or sample_weight.dtype != torch.float32 or not sample_weight.is_contiguous()
+                                      or tuple(sample_weight.shape) != (B,) or sample_weight.device != dev):
+        raise ValueError(f"{op}: sample_weight must be a contiguous float32 tensor [B={B}] on {dev}")
+    if out is not None and (out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (Cc + 2,) or out.device != dev):
+        raise ValueError(f"{op}: out must be a contiguous float64 tensor [C + 2 = {Cc + 2}] on {dev}")
+    _dev(maps[0], sample_weight, out, scratch)
+    nbytes = confidence_stats_scratch_bytes(B * H * W)
+    if scratch is None:
+        scratch = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < nbytes or scratch.device != dev \
+            or scratch.data_ptr() % 8:
+        raise ValueError(f"{op}: scratch must be a contiguous, 8-byte aligned uint8 buffer of at least {nbytes} bytes on {dev}")
+    if out is None:
+        out = torch.empty((Cc + 2,), device=dev, dtype=torch.float64)
+    fl =(ctypes.c_int * V)(*[int(f) for f in flips])
+    check(_lib_adapt.lib().asis_adapt_stats(_stream(), B, ptrs, hs, ws, fl, V, H, W, Cc, float(temperature), _p(sample_weight),
+                                            scratch.data_ptr(), out.data_ptr()), "asis_adapt_stats")
+    return out
+
+
+def adaptive_threshold_update(sums: torch.Tensor, state: torch.Tensor, thr: torch.Tensor, momentum: float = 0.999) -> torch.Tensor:
+    """One step of self-adaptive thresholding on the device (csrc/adapt.hip): ``sums`` float64 [C + 2] as ``confidence_stats``
+    gives them, ``state`` float64 [C + 2] = tau, n_updates, ptilde[C] (updated in place), ``thr`` fp32 [C] (written; returned).  With
+    cnt = sums[C + 1] > 0: tau <- m tau + (1 - m) S_conf / cnt, ptilde_c <- m ptilde_c + (1 - m) S_c / cnt, thr_c = fp32(tau
+    ptilde_c / max ptilde); with cnt == 0 state and thr keep their bits.  ``momentum`` m in [0, 1).  No host sync."""
+    from . import _lib_adapt
+    op = "adaptive_threshold_update"
+    if not torch.is_tensor(thr) or thr.dim() != 1 or thr.dtype != torch.float32 or not thr.is_contiguous():
+        raise ValueError(f"{op}: thr must be a contiguous float32 tensor [C]")
+    Cc = int(thr.shape[0])
+    if not 1 <= Cc <= ADAPT_MAX_CLASSES:
+        raise ValueError(f"{op}: C={Cc} must be in 1..{ADAPT_MAX_CLASSES}")
+    for name, t in (("sums", sums), ("state", state)):
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (Cc + 2,) \
+                or t.device != thr.device:
+            raise ValueError(f"{op}: {name} must be a contiguous float64 tensor [C + 2 = {Cc + 2}] on {thr.device}")
+    if not 0.0 <= float(momentum) < 1.0:
+        raise ValueError(f"{op}: momentum={momentum} must be in [0, 1)")
+    _dev(sums, state, thr)
+    check(_lib_adapt.lib().asis_adapt_update(_stream(), sums.data_ptr(), state.data_ptr(), thr.data_ptr(), Cc, float(momentum)),
+          "asis_adapt_update")
+    return thr
 
 
 # --------------------------------------------------------------------------------------------

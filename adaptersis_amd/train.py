@@ -254,7 +254,8 @@ def check_backbone_args(args) -> Optional[str]:
 
 
 DISTILL_FLAGS = ("distill_teacher_arch", "distill_teacher_ema", "distill_weight", "distill_temperature", "distill_threshold",
-                 "distill_rampup", "distill_flip", "distill_weak")
+                 "distill_rampup", "distill_flip", "distill_weak", "distill_class_thresholds", "distill_adaptive_threshold",
+                 "distill_adaptive_momentum")
 
 
 def check_distill_args(args) -> Optional[str]:
@@ -282,6 +283,21 @@ def check_distill_args(args) -> Optional[str]:
         return "--distill_threshold must be at most 1 (0 or less keeps every pixel)"
     if R is not None and int(R) < 0:
         return "--distill_rampup counts steps: it must be >= 0"
+    ct, ad = getattr(args, "distill_class_thresholds", None), bool(getattr(args, "distill_adaptive_threshold", False))
+    m = getattr(args, "distill_adaptive_momentum", None)
+    if ct is not None and ad:
+        return "--distill_class_thresholds sets the thresholds by hand, --distill_adaptive_threshold adapts them: pick one"
+    if (ct is not None or ad) and th is not None:
+        return "--distill_threshold is one threshold for every class: not with --distill_class_thresholds / --distill_adaptive_threshold"
+    if ct is not None and not all(math.isfinite(float(v)) for v in ct):
+        return "--distill_class_thresholds must be finite (0 or less keeps every pixel of a class, above 1 drops them all)"
+    nc = getattr(args, "num_classes", None)
+    if ct is not None and nc is not None and len(ct) != int(nc):
+        return f"--distill_class_thresholds has {len(ct)} values for --num_classes {int(nc)}"
+    if m is not None and not ad:
+        return "--distill_adaptive_momentum needs --distill_adaptive_threshold"
+    if m is not None and not 0.0 <= float(m) < 1.0:
+        return "--distill_adaptive_momentum must lie in [0, 1)"
     return None
 
 
@@ -291,9 +307,14 @@ def _distill_engine_args(args, teacher) -> dict:
     if teacher is None:
         return {}
     pick = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)
-    return {"teacher": teacher, "distill_weight": float(pick("distill_weight", 1.0)),
-            "distill_temperature": float(pick("distill_temperature", 1.0)), "distill_threshold": getattr(args, "distill_threshold", None),
-            "distill_rampup": int(pick("distill_rampup", 0)), "distill_flip": bool(getattr(args, "distill_flip", False))}
+    out = {"teacher": teacher, "distill_weight": float(pick("distill_weight", 1.0)),
+           "distill_temperature": float(pick("distill_temperature", 1.0)), "distill_threshold": getattr(args, "distill_threshold", None),
+           "distill_rampup": int(pick("distill_rampup", 0)), "distill_flip": bool(getattr(args, "distill_flip", False))}
+    if getattr(args, "distill_adaptive_threshold", False):   # the keywords are passed only with the flags
+        out.update(distill_class_thresholds="adaptive", distill_adaptive_momentum=float(pick("distill_adaptive_momentum", 0.999)))
+    elif getattr(args, "distill_class_thresholds", None) is not None:
+        out.update(distill_class_thresholds=[float(v) for v in args.distill_class_thresholds])
+    return out
 
 
 def teacher_shares_backbone(args, src: dict) -> bool:
@@ -424,6 +445,12 @@ class _DistillEntry:
 
     def load_state_dict(self, entry):
         self.engine.distill_step = int(entry["step"])
+        adaptive = getattr(self.engine, "adaptive", None)
+        if adaptive is not None:   # --distill_adaptive_threshold: tau and the class averages
+            if "adaptive" in entry:
+                adaptive.load_state_dict(entry["adaptive"])
+            else:
+                print("=> the checkpoint's 'distill' entry holds no adaptive thresholds: they start from tau = ptilde = 1 / C")
         return f"<distill step {self.engine.distill_step}>"
 
 
@@ -700,6 +727,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                             train_loader, epoch, args.n_last_blocks, args.avgpool_patchtokens)
         scheduler.step()
         log_stats = {**{f"train_{k}": v for k, v in train_stats.items()}, "epoch": epoch}
+        if getattr(engine, "class_thresholds", None) is not None:   # behind the synchronize of the epoch's last step
+            log_stats["distill_class_thr"] = [float(v) for v in engine.class_thresholds.tolist()]
         if epoch % args.val_freq == 0 or epoch == args.epochs - 1:
             test_stats = validate(val_loader, model, feature_model, backbone_encoder, cross_vit, cross_cnn,
                                           seg_decoder, args.n_last_blocks, args.avgpool_patchtokens)
@@ -722,6 +751,8 @@ def train_seg(args, head: str = "feature", *, num_classes: int = 2, loss: Option
                 ckpt["ema"] = engine.ema_state_dict()
             if engine.teacher is not None:     # --distill_teacher: where the ramp-up of the consistency weight stands
                 ckpt["distill"] = {"step": engine.distill_step}
+                if getattr(engine, "adaptive", None) is not None:   # --distill_adaptive_threshold: tau and the class averages
+                    ckpt["distill"]["adaptive"] = engine.adaptive.state_dict()
             if engine.mix_sampler is not None:  # --mix: the step the next draw is seeded with
                 ckpt["mix"] = {"step": engine.mix_step}
             if engine.unlabelled is not None:   # --unlabelled_path: the epoch of the unlabelled stream
@@ -770,6 +801,8 @@ def train(model, feature_model, backbone_encoder, cross_vit, cross_cnn, seg_deco
         metric_logger.update(loss=loss.item())
         if engine.teacher is not None:     # the soft term and the share of the pixels its confidence gate let through
             metric_logger.update(loss_kd=engine.last_loss_kd.item(), kd_kept=engine.last_kd_kept.item() / batch[1].numel())
+            if getattr(engine, "adaptive", None) is not None:   # the global threshold the class thresholds are scaled from
+                metric_logger.update(kd_tau=engine.adaptive.state[0].item())
         if stream is not None or getattr(engine, "ignore_index", None) is not None:   # the share of the pixels that carry a label
             metric_logger.update(hard_valid=int(engine.last_hard_valid.sum()) / batch[1].numel())
         if engine.mix_sampler is not None:  # the share of the batch's pixels that came from another sample
@@ -919,6 +952,13 @@ def get_args_parser():
     p.add_argument("--distill_temperature", default=None, type=float, help="temperature of both distributions (default 1)")
     p.add_argument("--distill_threshold", default=None, type=float,
                    help="keep a pixel where the teacher's largest class probability (at the temperature) reaches this (default: all)")
+    p.add_argument("--distill_class_thresholds", default=None, type=float, nargs="+", metavar="T",
+                   help="one confidence threshold per class in place of --distill_threshold (--num_classes values)")
+    p.add_argument("--distill_adaptive_threshold", action="store_true",
+                   help="self-adaptive thresholds (FreeMatch): a global threshold that follows the teacher's mean confidence, scaled "
+                        "per class by a moving average of the teacher's class distribution, kept on the device")
+    p.add_argument("--distill_adaptive_momentum", default=None, type=float, metavar="L",
+                   help="momentum of both moving averages of --distill_adaptive_threshold (default 0.999)")
     p.add_argument("--distill_rampup", default=None, type=int, metavar="STEPS",
                    help="ramp the weight up over this many steps by exp(-5 (1 - t / STEPS)^2) (default 0: none)")
     p.add_argument("--distill_flip", action="store_true", help="the teacher also sees the mirrored batch (two views averaged)")
